@@ -11,6 +11,10 @@ fit! epoch: fused data pass over every local row (forward, masked loss, both gra
 gradients, optimizer steps of X and Y, deterministic loss reduction.  The rows are sharded over the N GPUs
 (strong scaling: total work fixed), grad(Y) is all-reduced with RCCL and overlapped with the local X step.
 Inputs are generated on the device and are resident in HBM before the timed region starts.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full also times the other arithmetic mode on the
+same data (`other_precision`) and the CPU baselines (`cpu_baseline*`, unless --no-cpu-baseline).  --dump-outputs DIR
+writes what the timed steps computed, as the caller of the fit receives it, to DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -25,6 +29,16 @@ ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 
 F32_MFMA_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense, = f32 vector peak
+DUMP_ENTRIES = 1 << 22         # --dump-outputs: at most this many entries (16 MiB of float32) per factor matrix
+
+
+def dump_columns(n, k, seed):
+    """Sorted indices of the columns of a k x n factor that --dump-outputs keeps: all of them when k * n fits DUMP_ENTRIES,
+    else a fixed seeded sample, the same in every run with the same arguments and whatever the number of ranks."""
+    cap = max(1, DUMP_ENTRIES // k)
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
 
 
 def device_for_rank(local_rank, visible):
@@ -54,13 +68,21 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--precision", default=os.environ.get("PMF_BENCH_PRECISION", "f32"), choices=["f32", "bf16x3"],
                     help="products of the fused data pass for the HEADLINE numbers: exact f32 MFMA (default) or the opt-in "
-                         "split-bf16 kernel; the other mode is timed afterwards on the same data and reported beside it")
+                         "split-bf16 kernel; with --full the other mode is timed afterwards on the same data and reported "
+                         "beside it")
     ap.add_argument("--store", default=os.environ.get("PMF_BENCH_STORE", "f32"), choices=["f32", "bf16"],
                     help="storage type of the device copy of D (bf16: BASELINE configs[4]; read by the split-bf16 pass only)")
     ap.add_argument("--full-model", action="store_true",
                     help="BASELINE configs[2] / configs[4] flavour (SURVEY 8d C3 / C5): 20 %% Bernoulli columns, column scale / shift, "
                          "BatchArray scale / shift on 2 views x 8 row batches, 10 %% missing entries -- on top of the group-reg X + "
                          "feature-set-ARD Y of the headline workload")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: time the other arithmetic mode on the same data (other_precision) and the CPU "
+                         "baselines (cpu_baseline*, unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what they computed to DIR/<name>.npy: loss (float64, one per timed "
+                         "step), Y and X (float32, K x columns; a fixed seeded sample of the columns beyond "
+                         f"{DUMP_ENTRIES} entries, X over the global rows)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "0") or 0)
@@ -201,6 +223,7 @@ def main():
         ctx.set_optimizer(args.optimizer, lr=lr)
         n_split0 = ctx.get_precision()[1]
         ls = run_epochs(1, args.warmup) if args.warmup > 0 else []
+        n_warm = len(ls)
         ctx.kernel_time(reset=True)
         barrier()
         ctx.synchronize()
@@ -214,13 +237,32 @@ def main():
         ms, n = ctx.kernel_time()
         kern_names[precision] = {0: "pmf_fused_kernel", 1: "pmf_fused_sb_kernel", 2: "pmf_fused_sb2_kernel", 4: "pmf_fused_sb4_kernel",
                                  8: "pmf_fused_sb8_kernel"}.get(ctx.last_kernel(), "?")
-        return t, ms, n, ls, ctx.get_precision()[1] - n_split0
+        return t, ms, n, ls, ctx.get_precision()[1] - n_split0, ls[n_warm:]
 
-    dt, k_ms, k_n, losses, n_split = timed_run(args.precision)
+    def dump_outputs(out_dir, timed_losses):
+        """What the caller of the timed fit receives after its last step: the loss of every timed epoch and the factors
+        (pmf_get_factors).  Columns beyond DUMP_ENTRIES per factor are a fixed seeded sample (dump_columns); the sampled
+        columns of X are picked over the GLOBAL rows and summed to rank 0 (each column lives on exactly one rank)."""
+        X, Y = ctx.get_factors()
+        xc = dump_columns(M, K, seed + 31)
+        own = (xc >= lo) & (xc < hi)
+        Xs = np.zeros((K, len(xc)), np.float32)
+        Xs[:, own] = X[:, xc[own] - lo]
+        if use_dist:
+            ctx.comm_allreduce(Xs)
+        if rank == 0:
+            out_dir.mkdir(parents=True, exist_ok=True)
+            np.save(out_dir / "loss.npy", np.asarray(timed_losses, np.float64))
+            np.save(out_dir / "X.npy", Xs)
+            np.save(out_dir / "Y.npy", np.ascontiguousarray(Y[:, dump_columns(N, K, seed + 37)]))
+
+    dt, k_ms, k_n, losses, n_split, timed_losses = timed_run(args.precision)
+    if args.dump_outputs:
+        dump_outputs(Path(args.dump_outputs), timed_losses)
     other = "bf16x3" if args.precision == "f32" else "f32"
-    have_other = args.store == "f32"   # (a bf16-stored matrix is read by the split-bf16 pass only)
+    have_other = args.full and args.store == "f32"   # (a bf16-stored matrix is read by the split-bf16 pass only)
     if have_other:
-        dt2, k_ms2, k_n2, losses2, n_split2 = timed_run(other)   # the other arithmetic, same data, reported beside the headline
+        dt2, k_ms2, k_n2, losses2, n_split2, _ = timed_run(other)   # the other arithmetic, same data, reported beside the headline
     split_main = args.precision == "bf16x3" and n_split > 0
     cinfo = ctx.comm_info()
     n_chunks = max(1, cinfo["n_chunks"])
@@ -291,7 +333,7 @@ def main():
                 out["roofline"]["traffic_source"] = trk["source"]
         except (OSError, KeyError, ValueError):
             pass
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # CPU ports of the same epoch on this host's cores, bounded row samples (oracle/cpu_baseline.py): the OpenMP
             # loop nest of the C oracle, and an epoch with the structure of the reference's CPU path (three sgemm per row
             # batch + materialised m x N layer passes).  Reported baselines, not targets.

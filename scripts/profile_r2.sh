@@ -18,7 +18,7 @@ prof() {   # name, then the command's arguments (a python script with its argume
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$d/pmc_write" -- python3 "$@" > "$d/pmc_write.log" 2>&1; echo "rc=$?" >> "$d/pmc_write.log"
   echo "[$name] done: $(tail -1 $d/stats.log)"
 }
-B="--steps 4 --warmup 1 --no-cpu-baseline"
+B="--full --steps 4 --warmup 1 --no-cpu-baseline"
 if [ "${PMF_PROFILE_SET:-all}" = "full_model" ]; then   # the full-model flavours only (added late in round 2)
   prof config4_shard_full "$ROOT/bench.py" $B --M 125000 --N 100000 --K 128 --precision bf16x3 --store bf16 --full-model
   prof config2_full "$ROOT/bench.py" $B --M 20000 --N 10000 --K 32 --full-model

@@ -27,6 +27,18 @@ def test_device_for_rank():
         f(0, 0)
 
 
+def test_dump_columns_are_all_or_a_fixed_sample():
+    """--dump-outputs keeps every column of a factor that fits the cap, else the same sorted sample in every run."""
+    b = _bench()
+    assert np.array_equal(b.dump_columns(1500, 64, 7), np.arange(1500))
+    assert np.array_equal(b.dump_columns(b.DUMP_ENTRIES // 64, 64, 7), np.arange(b.DUMP_ENTRIES // 64))
+    c = b.dump_columns(200000, 64, 7)
+    assert len(c) == b.DUMP_ENTRIES // 64 and len(np.unique(c)) == len(c) and np.all(np.diff(c) > 0)
+    assert c[0] >= 0 and c[-1] < 200000
+    assert np.array_equal(c, b.dump_columns(200000, 64, 7)) and not np.array_equal(c, b.dump_columns(200000, 64, 8))
+    assert len(b.dump_columns(100000, 128, 7)) * 128 <= b.DUMP_ENTRIES
+
+
 def test_openmp_team_is_sized_by_the_work():
     from oracle import cpu_baseline as cb
     assert cb.threads_for(500, 200, 4, cap=256) == 1            # configs[0]: 4e5 multiply-adds, one thread
