@@ -148,10 +148,10 @@ struct pmf_ctx {
   hipEvent_t ev_host = nullptr;   // "the epoch's loss has reached the host" (pmf_fit)
   int64_t kind_version = 0;
   float *gy_slabs = nullptr;      // [grid][Kp x N] private per-workgroup gY partial sums of the fused kernel
-  size_t gy_slabs_cap = 0;        // floats
+  size_t gy_slabs_cap = 0;        // floats, the padding tile included
   int precision = PMF_PREC_F32;   // products of the fused data pass: exact f32 MFMA, or split-bf16 (pmf_set_precision)
   char *xsb = nullptr, *ysb = nullptr;   // split-bf16 operand images of X / sigma*Y, rebuilt every epoch (k_sb_split)
-  size_t xsb_cap = 0, ysb_cap = 0;       // bytes
+  size_t xsb_cap = 0, ysb_cap = 0;       // bytes (xsb: its sixteen blocks of padding included)
   float *sb8_scale = nullptr;     // [1 + chunks] power-of-two pre-scales of pmf_fused_sb8_kernel's f16 images: X, then Y per chunk
   uint32_t *sb8_max = nullptr;    // [1 + chunks] bit patterns of max |operand| (k_sb8_absmax)
   int64_t sb_launches = 0;        // fused launches that took the split-bf16 kernel (pmf_get_precision)

@@ -269,9 +269,11 @@ __global__ __launch_bounds__(256, 1) void pmf_fused_sb8_kernel(const FusedArgs a
     //      the transposed operand of all eight row blocks -> LDS (every wave reads its own k rows of it)
     f16x8 xh[RB][FS], xl[RB][FS];
     bf16x8 b3m[NI];   // (B3R: loaded here for the piece; otherwise per tile)
-    // One scalar base for the panel's eight row blocks (the image buffer is padded by eight zeroed blocks, so the blocks of
-    // a ragged last panel need no clamping: their G is zero).  In the per-tile variant the lane offset is made opaque before
-    // the block's stride is added, or hipcc hoists sixteen 64-bit addresses out of the tile loop (32 registers).
+    // One scalar base for the panel's NBLK row blocks, unclamped: sb_split_x writes whole panels, so the absent blocks of a
+    // ragged last panel hold zero images rewritten by every pass (their G is zero, and 0 x a stale NaN left in the buffer by
+    // an earlier pass would not be; the buffer's sixteen blocks of padding hold the rounding up, prepare_fused_pass).  In
+    // the per-tile variant the lane offset is made opaque before the block's stride is added, or hipcc hoists sixteen
+    // 64-bit addresses out of the tile loop (32 registers).
     const char *xt_mid = a.Xsb + rp * (int64_t)NBLK * XBLK + 3 * IMG;
     auto b3m_load = [&](int g) __attribute__((always_inline)) {
       uint32_t o = xtoff[KB == 4 ? (g & 1) : 0];

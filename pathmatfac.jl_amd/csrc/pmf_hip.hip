@@ -1683,12 +1683,15 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
   }
   c->n_macro = grid_sum;                 // loss partials: one per workgroup and chunk
   const int64_t slab_stride = (int64_t)c->Kp * c->N;
-  if (want_gy && (size_t)g.grid_max * (size_t)slab_stride > c->gy_slabs_cap) {
+  // never read before written, EXCEPT by pmf_fused_sb8_kernel, which loads the old values of a ragged last tile's absent
+  // columns without clamping (they are accumulated and never stored): one tile of padding at THIS Kp keeps those loads in
+  // bounds (the capacity counts the padding: a buffer allocated at a smaller Kp has less of it)
+  const size_t gy_need = (size_t)g.grid_max * (size_t)slab_stride + (size_t)PMF_BN * (size_t)c->Kp;
+  if (want_gy && gy_need > c->gy_slabs_cap) {
     dev_free(&c->gy_slabs);
-    // never read before written, EXCEPT by pmf_fused_sb8_kernel, which loads the old values of a ragged last tile's absent
-    // columns without clamping (they are accumulated and never stored): one tile of padding keeps those loads in bounds
-    PMFCHK(dev_alloc(&c->gy_slabs, (size_t)g.grid_max * (size_t)slab_stride + (size_t)PMF_BN * (size_t)c->Kp, false));
-    c->gy_slabs_cap = (size_t)g.grid_max * (size_t)slab_stride;
+    c->gy_slabs_cap = 0;
+    PMFCHK(dev_alloc(&c->gy_slabs, gy_need, false));
+    c->gy_slabs_cap = gy_need;
   }
   if (want_gx && serial_sum != c->gx_serial) {
     // slot map of the gX partial slabs: chunk s owns slots [slot_base, slot_base + pieces); per row panel, its slots in
@@ -1726,9 +1729,11 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
   if (g.sb) {
     const size_t xblk = c->KB == 1 ? SbCfg<1>::BLK : (c->KB == 2 ? std::max<size_t>(SbCfg<2>::BLK, Sb8Cfg<2>::XBLK) : Sb4Cfg<4>::XBLK);
     const size_t yblk = c->KB == 1 ? SbCfg<1>::BLK : (c->KB == 2 ? std::max<size_t>(SbCfg<2>::BLK, Sb8Cfg<2>::YBLK) : std::max<size_t>(Sb4Cfg<4>::YBLK, Sb8Cfg<4>::YBLK));
-    const size_t xb = (size_t)c->nRB * xblk, yb = (size_t)g.n_ct_all * yblk;
-    // (+ sixteen zeroed row blocks: pmf_fused_sb8_kernel reads the blocks of a ragged last panel without clamping)
-    if (xb > c->xsb_cap) { dev_free(&c->xsb); c->xsb_cap = 0; PMFCHK(dev_alloc(&c->xsb, xb + 16 * xblk, true)); c->xsb_cap = xb; }
+    // X images + sixteen row blocks: pmf_fused_sb8_kernel reads every block of its last panel, the absent ones unclamped, so
+    // sb_split_x writes whole panels, roundup(nRB, NBLK) <= nRB + 15 blocks of Sb8Cfg::XBLK <= xblk bytes each.  The
+    // capacity counts the sixteen blocks at THIS xblk (a buffer allocated at another KB may hold fewer bytes of padding).
+    const size_t xb = ((size_t)c->nRB + 16) * xblk, yb = (size_t)g.n_ct_all * yblk;
+    if (xb > c->xsb_cap) { dev_free(&c->xsb); c->xsb_cap = 0; PMFCHK(dev_alloc(&c->xsb, xb, true)); c->xsb_cap = xb; }
     if (yb > c->ysb_cap) { dev_free(&c->ysb); c->ysb_cap = 0; PMFCHK(dev_alloc(&c->ysb, yb, false)); c->ysb_cap = yb; }
     if (g.sb8 && !c->sb8_scale) {
       PMFCHK(dev_alloc(&c->sb8_scale, (size_t)(1 + PMF_MAX_CHUNKS), false));
@@ -1748,7 +1753,13 @@ static int sb8_split(pmf_ctx *c, const float *src, const float4 *colp, int64_t n
   return pmf_launch_sb8_split(c->stream, sp, c->KB);
 }
 static int sb_split_x(pmf_ctx *c, bool sb8) {
-  if (sb8) return sb8_split(c, c->P[0].p, nullptr, c->M, c->nRB, 0, 1, c->xsb);
+  if (sb8) {
+    // whole panels: k_sb8_split writes zero images for the absent row blocks of a ragged last panel, which the kernel reads
+    // unclamped (GEMM3's transposed X fragments; G is zero there, but 0 x a stale NaN is not).  Within the allocation:
+    // roundup(nRB, NBLK) * Sb8Cfg::XBLK <= (nRB + 15) * xblk (prepare_fused_pass)
+    const int64_t nblk = c->KB == 4 ? Sb8Cfg<4>::NBLK : Sb8Cfg<2>::NBLK;
+    return sb8_split(c, c->P[0].p, nullptr, c->M, (c->nRB + nblk - 1) / nblk * nblk, 0, 1, c->xsb);
+  }
   if (c->KB > 2) {
     Sb4SplitArgs s4 = {c->P[0].p, nullptr, c->M, c->nRB, c->Kp, 1, c->xsb};
     return pmf_launch_sb4_split(c->stream, s4);
