@@ -241,7 +241,8 @@ int pmf_comm_info(pmf_ctx *ctx, int *rank, int *nranks, int *transport, int *n_c
                   int64_t *n_collectives);
 
 /* Diagnostics: the batch-layer variant the last data pass took (0 none, 1 LDS table with panel-local slots, 2 per-entry
- * gathers), the last layer pass (1 MFMA layer pass, 2 VALU kernel) and the columns of the dense batch table.  Views with
+ * gathers), the last layer pass (1 MFMA layer pass, 2 VALU kernel) and the columns of the dense batch table as of the
+ * last prepared epoch (16 without batch views, 0 when a view has more than 255 batches and no table is built).  Views with
  * more than 15 batches stay on variant 1 as long as no 256-row (128-row for K > 64) panel holds more than 15 distinct
  * batches of one view (src/batch_array.jl:78-147 places no bound on the batch count). */
 int pmf_debug_last_path(pmf_ctx *ctx, int *bmode, int *layer_path, int *slots);

@@ -110,7 +110,7 @@ struct pmf_ctx {
   float2 *btd = nullptr;          // dense per-column batch table [ceil(N/32)*32][nbs] (fused kernels, layer pass); see k_dense_btab
   int64_t btd_cap = 0;
   bool btd_ok = false;            // the dense table is built (every view has <= 255 batches)
-  int nbs = 16;                   // slots per column of the dense table: 16, or the power of two above the largest batch count
+  int nbs = 16;                   // slots per column of the dense table: 16, or the power of two above the largest batch count (0: no table)
   int64_t colview_cap = 0;
   uint8_t *colview = nullptr;     // [ceil(N/32)*32] view of every column, 255 = none (k_dense_btab)
   std::vector<std::vector<int32_t>> h_bor;   // host copy of batch_of_row per view (panel-local slot maps)

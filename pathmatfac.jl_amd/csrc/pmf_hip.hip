@@ -1232,6 +1232,7 @@ static int prepare(pmf_ctx *c) {
                                                     c->P[4].p, c->P[5].p, c->btab, nbt);
   HIPCHK(hipGetLastError());
   c->btd_ok = false;
+  c->nbs = c->n_bv > 0 ? 0 : 16;   // (0: no dense table; 16: the layer pass's tables without batch views)
   if (c->n_bv > 0) {
     if (!c->d_views) PMFCHK(dev_alloc(&c->d_views, (size_t)PMF_MAXV, false));   // (prepare() runs every layer epoch: no re-allocation)
     if (c->views_dirty) {
@@ -1904,6 +1905,16 @@ static int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy) {
   return 0;
 }
 
+// k_layer_grad / k_stats keep [2][max_nb][64] batch sums in dynamic LDS, on top of the kernel's static LDS (k_layer_grad:
+// block_reduce_sum's slots): past 160 KiB together the launch is refused here, naming the batch count.
+static int check_lds_fits(const void *kern, size_t lds, int max_nb, const char *what) {
+  hipFuncAttributes fa;
+  HIPCHK(hipFuncGetAttributes(&fa, kern));
+  if (lds + fa.sharedSizeBytes > 160 * 1024)
+    return pmf_fail("too many row batches per view (%d) for the %s kernel", max_nb, what);
+  return 0;
+}
+
 static int launch_layer_grad(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) {
   LayerGradArgs a;
   memset(&a, 0, sizeof(a));
@@ -1923,7 +1934,7 @@ static int launch_layer_grad(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
   a.max_nb = max_nb;
   const int gx = nblocks(c->N, 64);
   // ~32 single-wave workgroups per CU hide the FMA / LDS latencies; at least 256 rows per workgroup keep the final
-  // atomics (64 * (2 + 2 nb) per workgroup) negligible
+  // partial stores (64 * (2 + 2 nb) per workgroup, added by k_sum_parts) negligible
   int64_t gy = std::max<int64_t>(1, std::min<int64_t>((32ll * c->n_cu + gx - 1) / gx, (c->M + 255) / 256));
   a.rows_per_block = (int)((c->M + gy - 1) / gy);
   gy = (c->M + a.rows_per_block - 1) / a.rows_per_block;
@@ -1945,8 +1956,6 @@ static int launch_layer_grad(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
     c->lgrad_part_cap = (size_t)(a.part_stride * gy);
   }
   a.part = c->lgrad_part;
-  const size_t lds = sizeof(float) * (size_t)(4 * c->Kp + 2 * max_nb * 64);
-  if (lds > 160 * 1024) return pmf_fail("too many row batches per view (%d) for the layer-gradient kernel", max_nb);
   void (*kern)(const LayerGradArgs) = nullptr;
   switch (c->KB) {
     case 1: kern = k_layer_grad<1>; break;
@@ -1955,6 +1964,8 @@ static int launch_layer_grad(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
     case 4: kern = k_layer_grad<4>; break;
     default: return pmf_fail("unsupported KB=%d", c->KB);
   }
+  const size_t lds = sizeof(float) * (size_t)(4 * c->Kp + 2 * max_nb * 64);
+  PMFCHK(check_lds_fits((const void *)kern, lds, max_nb, "layer-gradient"));
   PMFCHK(ensure_dyn_lds(c, (const void *)kern, lds));
   hipLaunchKernelGGL(kern, dim3(gx, (unsigned)gy), dim3(64), lds, c->stream, a);
   HIPCHK(hipGetLastError());
@@ -1965,8 +1976,10 @@ static int launch_layer_grad(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
   return 0;
 }
 
-// Layer-parameter gradients through the MFMA layer pass (its own loss only in layer-only epochs); K <= 64 and <= 15 batches per view, otherwise the
-// VALU kernel above (PMF_LAYER_OLD=1 forces it, for comparison).  K <= 128; views with <= 15 batches.
+// Layer-parameter gradients through the MFMA layer pass (its own loss only in layer-only epochs) while its LDS, with the
+// unit's [64 columns][nbs] batch table, fits in 160 KiB: up to 127 batches per view at K <= 32 and 65..96 (and at 33..64
+// with PMF_LAYER_NW=4), 63 at 33..64 and 97..128.  Otherwise, and without a dense table (more than
+// 255 batches), the VALU kernel above (PMF_LAYER_OLD=1 forces it, for comparison).
 static int layer_pass_waves(pmf_ctx *c) {   // waves per workgroup of the layer pass
   const char *lnwenv = getenv("PMF_LAYER_NW");
   return (c->KB <= 2 && !(lnwenv && atoi(lnwenv) == 4)) ? 8 : 4;
@@ -1987,8 +2000,9 @@ static int launch_layer_pass(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
   const int64_t n_seg = (n_ct + PMF_LS - 1) / PMF_LS;
   int64_t R = std::max<int64_t>(1, std::min<int64_t>(n_rp, (4ll * c->n_cu + n_seg - 1) / n_seg));
   const int grid = (int)std::min<int64_t>(n_seg * R, c->n_cu);
-  // one private [N][nbs] table per (row range, wave, lane half): plain read-modify-writes instead of float atomics, summed
-  // in fixed order by k_layer_map.  R * N is bounded by ~4 n_cu * 64 columns, so the tables take ~130 MB at nbs = 16.
+  // one private [N][nbs] table per (row range, wave, lane half): plain read-modify-writes, no float atomics, summed in
+  // fixed order by k_layer_reduce.  R <= ceil(4 n_cu / n_seg) keeps R * N near 4 n_cu * 64 columns (~130 MB of tables at
+  // nbs = 16) while n_seg < 4 n_cu; from n_seg >= 4 n_cu on R = 1 and the tables grow with N (2 NW * N * nbs float2).
   const int64_t lg_stride = c->N * nbs, n_parts = R * lnw * 2;
   if (lg_stride * n_parts > c->LG_cap) {
     PMFCHK(dev_alloc(&c->LG, (size_t)(lg_stride * n_parts), false));
@@ -2268,8 +2282,6 @@ extern "C" int pmf_stats(pmf_ctx *c, int use_factors, float *col_n, float *col_s
   a.col_n = part; a.col_sum = part + c->N; a.col_sumsq = part + 2 * c->N; a.col_sqerr = part + 3 * c->N; a.col_ssqg = part + 4 * c->N;
   a.b_n = nbt ? part + 5 * c->N : nullptr;
   a.b_sqerr = nbt ? part + 5 * c->N + nbt : nullptr;
-  const size_t lds = sizeof(float) * (size_t)(4 * c->Kp + 2 * max_nb * 64);
-  if (lds > 160 * 1024) return pmf_fail("too many row batches per view (%d) for the statistics kernel", max_nb);
   void (*kst)(const StatsArgs) = nullptr;
   switch (c->KB) {
     case 1: kst = k_stats<1>; break;
@@ -2278,6 +2290,8 @@ extern "C" int pmf_stats(pmf_ctx *c, int use_factors, float *col_n, float *col_s
     case 4: kst = k_stats<4>; break;
     default: return pmf_fail("unsupported KB=%d", c->KB);
   }
+  const size_t lds = sizeof(float) * (size_t)(4 * c->Kp + 2 * max_nb * 64);
+  PMFCHK(check_lds_fits((const void *)kst, lds, max_nb, "statistics"));
   PMFCHK(ensure_dyn_lds(c, (const void *)kst, lds));
   hipLaunchKernelGGL(kst, dim3(gx, (unsigned)gy), dim3(64), lds, c->stream, a);
   HIPCHK(hipGetLastError());

@@ -209,3 +209,113 @@ def shard_problem(p, lo, hi):
             t["start1"], t["stop1"] = [s[i] for i in keep], [e[i] for i in keep]
             t["w"] = np.asarray(t["w"])[keep]
     return q
+
+
+# ---- a segment-scaled check for the layer-parameter gradients --------------------------------------------------------
+LAYER_TAU = 2e-5
+
+
+def layer_scales(p, cols=4096):
+    """fp64 error scales of the four layer gradients of problem `p`: the per-(batch, column) sums of the magnitudes a
+    kernel rounds on the way to each gradient.  z comes from the fp64 forward of DESIGN section 4.3 (restated here, per
+    noise kind): z1 = sigma_j a_ij, z = z1 delta_bj + mu_j + theta_bj (delta = 1, theta = 0 for rows with batch -1 and for
+    columns outside every batch view), g = w_j (link(z) - y) on observed entries.  Per observed entry
+
+        sG_ij = w_j (|link(z)| + |y| + link'(z) r_ij),   r_ij = sigma_j delta_bj sum_k |X_ki Y_kj| + |mu_j| + |theta_bj|
+        sQ_ij = |z1_ij| sG_ij + |g_ij| sigma_j sum_k |X_ki Y_kj|
+
+    (r bounds what the forward rounds, link' carries it into g; the second term of sQ is the rounding of z1 itself), and
+
+        grad theta[b, j]    ~ sum_{i in b} sG           grad mu[j]       ~ sum_i sG
+        grad logdelta[b, j] ~ delta_bj sum_{i in b} sQ  grad logsigma[j] ~ sigma_j sum_i delta_bj sG
+
+    The scales only set tolerances; the reference value of every gradient stays the oracle's.  Also returns g (M x N)
+    and, as "loss", the sum of the magnitudes of the loss terms: 0.5 w (z - y)^2 (Gaussian: the loss itself),
+    w (softplus(z) + |y z|) (Bernoulli), w (e^z + |y z|) (Poisson) -- the last two cancel term by term.  Works on blocks
+    of `cols` columns (wide problems)."""
+    X = np.asarray(p["X"], np.float64)
+    Y = np.asarray(p["Y"], np.float64)
+    D = p["D"]
+    M, N = D.shape
+    sig_all = np.exp(np.asarray(p["logsigma"], np.float64))
+    mu_all = np.asarray(p["mu"], np.float64)
+    w_all = np.asarray(p["col_weight"], np.float64)
+    kind = np.zeros(N, np.int8)                                   # 0 normal, 1 bernoulli, 2 poisson
+    for (s, e), kd in zip(p["noise_ranges"], p["noise_kinds"]):
+        kind[s - 1:e] = {"normal": 0, "bernoulli": 1, "poisson": 2}[kd]
+    bvs = []
+    for bv in p["batch_views"]:
+        bor = np.asarray(bv["batch_of_row"])
+        nb = np.asarray(bv["logdelta"]).shape[0]
+        bvs.append((bv["start1"] - 1, bv["stop1"], bor, bor >= 0, nb, np.exp(np.asarray(bv["logdelta"], np.float64)),
+                    np.asarray(bv["theta"], np.float64), (bor[:, None] == np.arange(nb)[None, :]).astype(np.float64)))
+    out = dict(mu=np.zeros(N), logsigma=np.zeros(N), theta=[np.zeros((b[4], b[1] - b[0])) for b in bvs],
+               logdelta=[np.zeros((b[4], b[1] - b[0])) for b in bvs], g=np.zeros((M, N)), loss=0.0)
+    for c0 in range(0, N, cols):
+        c1 = min(N, c0 + cols)
+        sig, mu, w, kd = sig_all[c0:c1], mu_all[c0:c1], w_all[c0:c1], kind[c0:c1]
+        A = X.T @ Y[:, c0:c1]
+        Aabs = np.abs(X).T @ np.abs(Y[:, c0:c1])
+        dl = np.ones_like(A)
+        th = np.zeros_like(A)
+        for s, e, bor, has, nb, delta, theta, onehot in bvs:
+            a, b = max(s, c0), min(e, c1)
+            if a < b:
+                dl[np.ix_(has, np.arange(a - c0, b - c0))] = delta[bor[has]][:, a - s:b - s]
+                th[np.ix_(has, np.arange(a - c0, b - c0))] = theta[bor[has]][:, a - s:b - s]
+        z1 = A * sig[None, :]
+        z = z1 * dl + mu[None, :] + th
+        link, dlink = z.copy(), np.ones_like(z)
+        bern, pois = kd == 1, kd == 2
+        sg = 0.5 * (1.0 + np.tanh(0.5 * z[:, bern]))
+        link[:, bern], dlink[:, bern] = sg, sg * (1.0 - sg)
+        link[:, pois] = dlink[:, pois] = np.exp(z[:, pois])
+        Dc = np.asarray(D[:, c0:c1], np.float64)
+        obs = np.isfinite(Dc)
+        y = np.where(obs, Dc, 0.0)
+        g = np.where(obs, w[None, :] * (link - y), 0.0)
+        r = sig[None, :] * Aabs * dl + np.abs(mu)[None, :] + np.abs(th)
+        sG = np.where(obs, w[None, :] * (np.abs(link) + np.abs(y) + dlink * r), 0.0)
+        sQ = np.abs(z1) * sG + np.abs(g) * sig[None, :] * Aabs
+        lm = np.where(kd[None, :] == 0, 0.5 * (z - y) ** 2,
+                      np.where(kd[None, :] == 1, np.logaddexp(0.0, z), np.exp(np.minimum(z, 700.0))) + np.abs(y * z))
+        out["loss"] += float(np.sum(np.where(obs, w[None, :] * lm, 0.0)))
+        out["g"][:, c0:c1] = g
+        out["mu"][c0:c1] = sG.sum(0)
+        out["logsigma"][c0:c1] = sig * (dl * sG).sum(0)
+        for v, (s, e, bor, has, nb, delta, theta, onehot) in enumerate(bvs):   # rows with batch -1: no segment
+            a, b = max(s, c0), min(e, c1)
+            if a < b:
+                out["theta"][v][:, a - s:b - s] = onehot.T @ sG[:, a - c0:b - c0]
+                out["logdelta"][v][:, a - s:b - s] = delta[:, a - s:b - s] * (onehot.T @ sQ[:, a - c0:b - c0])
+    return out
+
+
+def layer_check(p, got, want, tau=LAYER_TAU, tiny=1e-30, scales=None, skip=()):
+    """Worst ratio |got - want| / (tau * scale + tiny) over every (batch, column) segment of grad mu, grad logsigma,
+    grad theta and grad logdelta (<= 1 passes; `skip` names gradients that are not compared, e.g. frozen layers).
+    `got` and `want` are dicts of those arrays (theta and logdelta as per-view lists), `want` normally the fp64 oracle's.
+
+    Unlike rel_err, which divides by the largest entry of a whole array, each segment is held to the rounding of its own
+    terms: a (batch, column) sum that loses one row, or gains one of the neighbouring batch, is off by |g_ij|, far more
+    than tau * scale unless the segment is large or the row's gradient is negligible.  A sum that cancels (M = 31,
+    N = 1) is not held to its tiny result either.  tau = 2e-5 covers sequential f32 sums of a few hundred terms (the f32
+    build of the oracle stays below 1/10 of it on the shapes of tests/test_gpu_layer_edges.py)."""
+    s = layer_scales(p) if scales is None else scales
+    worst = dict()
+    for k in ("mu", "logsigma", "theta", "logdelta"):
+        if k in skip:
+            continue
+        gs, ws, ss = (got[k], want[k], s[k]) if k in ("theta", "logdelta") else ([got[k]], [want[k]], [s[k]])
+        assert len(gs) == len(ws) == len(ss), k
+        r = 0.0
+        for a, b, c in zip(gs, ws, ss):
+            a = np.asarray(a, np.float64)
+            b = np.asarray(b, np.float64)
+            assert a.shape == b.shape == c.shape, (k, a.shape, b.shape, c.shape)
+            if a.size:
+                if not np.isfinite(a).all():
+                    return dict(worst, **{k: np.inf})
+                r = max(r, float(np.max(np.abs(a - b) / (tau * c + tiny))))
+        worst[k] = r
+    return worst

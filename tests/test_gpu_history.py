@@ -10,7 +10,7 @@ oracle.  Only float values are poisoned: indices, ranges and sizes are validated
 import numpy as np
 import pytest
 
-from problems import make_problem, rel_err, to_context, to_oracle
+from problems import layer_check, make_problem, rel_err, to_context, to_oracle
 from test_gpu_parity import GRAD_TOL, LOSS_RTOL, grads_of
 from test_gpu_split_bf16 import bf16_round
 
@@ -36,12 +36,20 @@ TARGETS = {
     "sb8_k100_bf16_store": ("bf16x3", 100, 300, 95, BOTH, 8, dict(store="bf16")),
     "sb8_k40_3_chunks": ("bf16x3", 40, 600, 161, BOTH, 8, dict(chunks=3)),
     "layers_k32_batch": ("f32", 32, 300, 100, dict(update_col_layers=True), None, BATCH),
+    # the layer pass at KB = 3 with a wide (64-slot) table; at KB = 4, 16 slots and bf16 storage; K = 64 with 64 batches
+    # (128 slots do not fit next to eight X panels: k_layer_grad)
+    "layers_k96_40_batches": ("f32", 96, 300, 100, dict(update_col_layers=True), None,
+                              dict(BATCH, n_batches=40, layer_path=1)),
+    "layers_k128_bf16_store": ("f32", 128, 300, 100, dict(update_col_layers=True), None,
+                               dict(BATCH, store="bf16", layer_path=1)),
+    "layers_k64_64_batches": ("f32", 64, 300, 100, dict(update_col_layers=True), None,
+                              dict(BATCH, n_batches=64, layer_path=2)),
 }
 
 
 def target_problem(name):
     prec, K, M, N, flags, fam, extra = TARGETS[name]
-    kw = {k: v for k, v in extra.items() if k not in ("store", "chunks")}
+    kw = {k: v for k, v in extra.items() if k not in ("store", "chunks", "layer_path")}
     p = make_problem(M=M, N=N, K=K, seed=K + M, col_params=True, weights=True, nan_frac=0.05, scale=0.5, **kw)
     if extra.get("store") == "bf16":
         p["D"] = np.asfortranarray(bf16_round(p["D"]))
@@ -66,6 +74,8 @@ def run_target(ctx, name, p):
     if fam is not None:
         assert ctx.last_kernel() == fam, (ctx.last_kernel(), fam)
         assert ctx.get_precision()[1] == n0 + (0 if fam == 0 else extra.get("chunks", 1))
+    if "layer_path" in extra:
+        assert ctx.last_path()["layer_path"] == extra["layer_path"], ctx.last_path()
     # optimizer state is kept across re-marshalling on purpose (test_adapt_lr_keeps_optimizer_state_across_segments):
     # set_optimizer resets it, so the fit does not see the history's
     ctx.set_optimizer("adagrad", lr=0.05)
@@ -142,6 +152,9 @@ def assert_oracle(p, flags, r):
         for w, (u, uo) in enumerate(zip(v, go[k]) if isinstance(v, list) else [(v, go[k])]):
             assert np.isfinite(u).all(), f"non-finite gradient {k}[{w}]"
             assert rel_err(u, uo) <= GRAD_TOL, (k, w, rel_err(u, uo))
+    if "mu" in r["g"]:
+        worst = layer_check(p, r["g"], go)
+        assert max(worst.values()) <= 1.0, worst
 
 
 @pytest.mark.parametrize("name", list(TARGETS))
