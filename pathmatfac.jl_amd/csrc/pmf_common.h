@@ -405,31 +405,17 @@ struct LayerMapArgs {
 };
 
 // ---- launchers exported by the kernel files
-int pmf_launch_fused_exact_11(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_12(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_21(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_31(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_41(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_11_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_12_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_21_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_31_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_exact_41_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_sb_1(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb_2(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb_1_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb_2_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb2(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb2_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb4_4(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb4_4_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb4_3(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
-int pmf_launch_fused_sb4_3_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx, bool want_gy);
+// Fused-kernel launchers, one per family, K-block count (exact kernel: and row blocks per wave) and storage type of D, all
+// of one type: the family table in pmf_hip.hip holds them.  The gradient variant follows a.want_gx / a.want_gy.
+typedef int PmfFusedLaunch(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
+PmfFusedLaunch pmf_launch_fused_exact_11, pmf_launch_fused_exact_12, pmf_launch_fused_exact_21, pmf_launch_fused_exact_31,
+    pmf_launch_fused_exact_41, pmf_launch_fused_exact_11_bf16, pmf_launch_fused_exact_12_bf16, pmf_launch_fused_exact_21_bf16,
+    pmf_launch_fused_exact_31_bf16, pmf_launch_fused_exact_41_bf16;
+PmfFusedLaunch pmf_launch_fused_sb_1, pmf_launch_fused_sb_2, pmf_launch_fused_sb_1_bf16, pmf_launch_fused_sb_2_bf16;
+PmfFusedLaunch pmf_launch_fused_sb2, pmf_launch_fused_sb2_bf16;
+PmfFusedLaunch pmf_launch_fused_sb4_3, pmf_launch_fused_sb4_4, pmf_launch_fused_sb4_3_bf16, pmf_launch_fused_sb4_4_bf16;
+PmfFusedLaunch pmf_launch_fused_sb8_2, pmf_launch_fused_sb8_4, pmf_launch_fused_sb8_2_bf16, pmf_launch_fused_sb8_4_bf16;
 int pmf_launch_sb4_split(hipStream_t stream, const Sb4SplitArgs &a);
-int pmf_launch_fused_sb8_4(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_sb8_4_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_sb8_2(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-int pmf_launch_fused_sb8_2_bf16(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
 int pmf_launch_sb8_split(hipStream_t stream, const Sb8SplitArgs &a, int KB);
 int pmf_launch_sb8_scale(hipStream_t stream, const Sb8ScaleArgs &a);
 int pmf_launch_sb_split_1(hipStream_t stream, const SbSplitArgs &a);

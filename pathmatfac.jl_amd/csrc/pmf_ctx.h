@@ -177,13 +177,13 @@ struct pmf_ctx {
 #define REG_SLOTS 1024
 #define PMF_MAX_CHUNKS 16
 
-// Geometry of one fused data pass: kernel variant, row panels, column chunks.
+// Geometry of one fused data pass: kernel family, row panels, column chunks.
+struct FusedFamily;   // a row of the family table (pmf_hip.hip): kernel, panel height, operand images, launchers
 struct FusedGeom {
-  int NW = 8, RBW = 1, BM = 256, grid_max = 256, S = 1;
+  const FusedFamily *fam = nullptr;
+  int grid_max = 256, S = 1;
   int bmode = 0;      // batch layers: 0 none, 1 LDS table with panel-local slots, 2 per-entry global gathers (fallback)
   PanelSlots *ps = nullptr;
-  bool sb = false;    // split-bf16 products: pmf_fused_sb_kernel (K <= 64) or pmf_fused_sb4_kernel (64 < K <= 128)
-  bool sb8 = false;   // ... of them, pmf_fused_sb8_kernel: 96 < K <= 128, both gradients, 256-row panel
   int64_t n_rp = 0, n_ct_all = 0;
   int64_t ct0[PMF_MAX_CHUNKS], nct[PMF_MAX_CHUNKS];
 };

@@ -1554,51 +1554,91 @@ static int ensure_panel_slots(pmf_ctx *c, int BM, PanelSlots **out) {
   return 0;
 }
 
-// Variant and chunking of a fused data pass.
-//   variant: waves per workgroup NW and 32-row blocks per wave RBW (the workgroup's row panel is 32*NW*RBW rows)
-//     K <= 32 : 8 waves x 2 row blocks (per-tile overheads amortised over twice the MFMA work; x 1 with batch layers)
-//     K <= 64 : 8 waves x 1          K <= 128 : 4 waves x 1 (one wave per SIMD, whole register file)
-//   PMF_RBW=1 forces one row block for K <= 32 (development comparison; 4 waves x 2 blocks at K = 64 measured 3 % slower
-//   than 8 x 1 and was removed)
+// The kernel families of the fused data pass: one row per (family, KB) -- the exact kernel's per (KB, row blocks per wave)
+// -- with everything the host needs to run it.  fused_geometry picks the row; the buffers, the operand images, the launch
+// and the diagnostics of the pass read it.
+enum FusedImages { IMG_NONE, IMG_SB, IMG_SB4, IMG_SB8 };   // operand images: none, k_sb_split, k_sb4_split, k_sb8_split
+struct FusedFamily {
+  int kernel;          // pmf_debug_last_kernel: 0 exact, 1 sb, 2 sb2, 4 sb4, 8 sb8
+  int KB, NW, RBW;     // K blocks; waves x 32-row blocks per wave
+  int max_bv;          // batch views its LDS has room for
+  FusedImages img;     // how its operand images are split (sb_split_x, sb_split_y)
+  int img_kb;          // K blocks of an image row (pmf_fused_sb4_kernel's images have 256-byte rows whatever K)
+  int xblk, yblk;      // image bytes per 32 rows of X / per 32 columns of sigma*Y
+  int nblk;            // X images are split in whole panels of nblk row blocks (pmf_fused_sb8_kernel reads them unclamped)
+  PmfFusedLaunch *launch[2];
+  constexpr int BM() const { return 32 * NW * RBW; }   // row-panel height
+};
+static constexpr FusedFamily fused_families[] = {
+    // kernel, KB, NW, RBW, max_bv, images, img_kb, xblk, yblk, nblk, launchers (D stored as f32, as bf16)
+    {0, 1, 8,             2,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_12, pmf_launch_fused_exact_12_bf16}},
+    {0, 1, 8,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_11, pmf_launch_fused_exact_11_bf16}},
+    {0, 2, 8,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_21, pmf_launch_fused_exact_21_bf16}},
+    {0, 3, 4,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_31, pmf_launch_fused_exact_31_bf16}},
+    {0, 4, 4,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_41, pmf_launch_fused_exact_41_bf16}},
+    {1, 1, SbCfg<1>::NW,  1,             SbCfg<1>::max_bv,  IMG_SB,   1, SbCfg<1>::BLK,   SbCfg<1>::BLK,   1,               {pmf_launch_fused_sb_1, pmf_launch_fused_sb_1_bf16}},
+    {1, 2, SbCfg<2>::NW,  1,             SbCfg<2>::max_bv,  IMG_SB,   2, SbCfg<2>::BLK,   SbCfg<2>::BLK,   1,               {pmf_launch_fused_sb_2, pmf_launch_fused_sb_2_bf16}},
+    {2, 2, 4,             2,             Sb2Cfg::max_bv,    IMG_SB,   2, SbCfg<2>::BLK,   SbCfg<2>::BLK,   1,               {pmf_launch_fused_sb2, pmf_launch_fused_sb2_bf16}},
+    {4, 3, Sb4Cfg<3>::NW, 1,             Sb4Cfg<3>::max_bv, IMG_SB4,  4, Sb4Cfg<3>::XBLK, Sb4Cfg<3>::YBLK, 1,               {pmf_launch_fused_sb4_3, pmf_launch_fused_sb4_3_bf16}},
+    {4, 4, Sb4Cfg<4>::NW, 1,             Sb4Cfg<4>::max_bv, IMG_SB4,  4, Sb4Cfg<4>::XBLK, Sb4Cfg<4>::YBLK, 1,               {pmf_launch_fused_sb4_4, pmf_launch_fused_sb4_4_bf16}},
+    {8, 2, Sb8Cfg<2>::NW, Sb8Cfg<2>::RB, Sb8Cfg<2>::max_bv, IMG_SB8,  2, Sb8Cfg<2>::XBLK, Sb8Cfg<2>::YBLK, Sb8Cfg<2>::NBLK, {pmf_launch_fused_sb8_2, pmf_launch_fused_sb8_2_bf16}},
+    {8, 4, Sb8Cfg<4>::NW, Sb8Cfg<4>::RB, Sb8Cfg<4>::max_bv, IMG_SB8,  4, Sb8Cfg<4>::XBLK, Sb8Cfg<4>::YBLK, Sb8Cfg<4>::NBLK, {pmf_launch_fused_sb8_4, pmf_launch_fused_sb8_4_bf16}},
+};
+constexpr int PMF_XSB_PAD = 16;   // xsb's image blocks beyond nRB: sb_split_x writes the last panel of every family whole
+static_assert([] { for (const FusedFamily &f : fused_families) if (f.nblk - 1 > PMF_XSB_PAD) return false; return true; }(), "PMF_XSB_PAD");
+
+// kernel code, KB and (RBW > 0) row blocks per wave -> the family's row
+static const FusedFamily *find_family(int kernel, int KB, int RBW = 0) {
+  for (const FusedFamily &f : fused_families)
+    if (f.kernel == kernel && f.KB == KB && (RBW == 0 || f.RBW == RBW)) return &f;
+  return nullptr;
+}
+
+// Family and chunking of a fused data pass.
+//   family (a row of fused_families): split-bf16 products (pmf_set_precision), at least one gradient, no PMF_DEBUG_FLAGS:
+//     K <= 32 sb;  32 < K <= 64 sb8 with both gradients unless PMF_SB8=0 or 4, else sb2 (sb under PMF_SB2=0);
+//     64 < K <= 96 sb4;  96 < K <= 128 sb8 with both gradients unless PMF_SB8=0, else sb4.
+//   With batch layers a family also needs the dense batch table, LDS room for the views and at most 15 batches of a view per
+//   row panel of ITS height (panel-local slots): sb8 falls back to sb2 / sb / sb4, these to the exact kernel, which has the
+//   per-entry gathers besides (bmode 2).  Everything else runs the exact kernel, with two row blocks per wave at K <= 32
+//   without batch layers (per-tile overheads amortised over twice the MFMA work; PMF_RBW=1: one; the batch-layer epilogue
+//   of two row blocks does not fit the 256-register budget: it spills and is 1.5x slower).
 //   chunks: the column tiles are walked in S contiguous chunks, one launch each.  S = 1 unless the context has a
 //   communicator with more than one rank (then the all-reduce of chunk s's grad(Y) runs beside the launches of the later
 //   chunks and of the next epoch's earlier ones, pmf_fit) or pmf_comm_set_chunks asked for it.
 FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chunks) {
   FusedGeom g;
-  const char *rbwenv = getenv("PMF_RBW");
-  // (the batch-layer epilogue of two row blocks does not fit the 256-register budget: RBW = 2 spills and is 1.5x slower)
-  g.NW = c->KB <= 2 ? 8 : 4;
-  g.RBW = (c->KB == 1 && c->n_bv == 0) ? 2 : 1;
-  if (rbwenv && c->KB == 1 && atoi(rbwenv) == 1) g.RBW = 1;
-  // split-bf16 products (opt-in, pmf_set_precision): K <= 64; one row block per wave
-  // (batch layers: through the dense LDS table only, i.e. <= 15 batches per view, and as many views as LDS has room for)
-  const int sb_max_bv = c->KB == 1 ? SbCfg<1>::max_bv : (c->KB == 2 ? SbCfg<2>::max_bv : Sb4Cfg<4>::max_bv);
-  // batch layers: the LDS-table path needs the dense table and <= 15 distinct batches per (view, row panel); every
-  // variant with batch layers has one row block per wave, so the panel height is known here
-  if (c->n_bv > 0) {
-    g.bmode = 2;
-    if (c->btd_ok && ensure_panel_slots(c, 32 * g.NW, &g.ps) == 0 && g.ps && g.ps->ok) g.bmode = 1;
-  }
-  const bool sb_batch_ok = c->n_bv == 0 || (g.bmode == 1 && c->n_bv <= sb_max_bv);
-  g.sb = c->precision == PMF_PREC_BF16X3 && sb_batch_ok && (want_gx || want_gy) && !getenv("PMF_DEBUG_FLAGS");
-  if (g.sb) g.RBW = 1;
-  // 96 < K <= 128, both gradients: the 256-row-panel kernel (pmf_fused_sb8.hip.inc: four waves x two row blocks; PMF_SB8=0
-  // keeps pmf_fused_sb4_kernel's 128-row panel).  Batch layers need the panel-local slots of the taller panel.
-  // (also 32 < K <= 64: four waves x four row blocks, 512-row panel; PMF_SB8=4 restricts it to K > 96)
-  {
+  auto batch_fits = [&](const FusedFamily *f) {
+    if (c->n_bv == 0) return true;
+    PanelSlots *ps = nullptr;
+    if (!c->btd_ok || c->n_bv > f->max_bv || ensure_panel_slots(c, f->BM(), &ps) != 0 || !ps || !ps->ok) return false;
+    g.ps = ps;
+    return true;
+  };
+  if (c->precision == PMF_PREC_BF16X3 && (want_gx || want_gy) && !getenv("PMF_DEBUG_FLAGS")) {
+    static const bool sb2_off = getenv("PMF_SB2") && atoi(getenv("PMF_SB2")) == 0;   // (read once per process)
     const char *e8 = getenv("PMF_SB8");
     const int m8 = e8 ? atoi(e8) : 1;
-    g.sb8 = g.sb && want_gx && want_gy && m8 != 0 && (c->KB == 4 || (c->KB == 2 && m8 != 4));
+    const bool both = want_gx && want_gy;
+    int base = 0;       // the family without sb8
+    bool sb8 = false;
+    switch (c->KB) {
+      case 1: base = 1; break;
+      case 2: base = sb2_off ? 1 : 2; sb8 = both && m8 != 0 && m8 != 4; break;
+      case 3: base = 4; break;
+      case 4: base = 4; sb8 = both && m8 != 0; break;
+    }
+    const FusedFamily *f8 = sb8 ? find_family(8, c->KB) : nullptr, *fb = find_family(base, c->KB);
+    g.fam = f8 && batch_fits(f8) ? f8 : (fb && batch_fits(fb) ? fb : nullptr);
+    g.bmode = g.fam && c->n_bv > 0 ? 1 : 0;
   }
-  const int bm8 = c->KB == 4 ? Sb8Cfg<4>::BM : Sb8Cfg<2>::BM;
-  if (g.sb8 && c->n_bv > 0) {
-    PanelSlots *ps8 = nullptr;
-    if (c->n_bv <= (c->KB == 4 ? Sb8Cfg<4>::max_bv : Sb8Cfg<2>::max_bv) && ensure_panel_slots(c, bm8, &ps8) == 0 && ps8 && ps8->ok) g.ps = ps8;
-    else g.sb8 = false;
+  if (!g.fam) {
+    const char *rbwenv = getenv("PMF_RBW");
+    g.fam = find_family(0, c->KB, c->KB == 1 && c->n_bv == 0 && !(rbwenv && atoi(rbwenv) == 1) ? 2 : 1);
+    if (!g.fam) return g;   // (prepare_fused_pass fails)
+    if (c->n_bv > 0) g.bmode = batch_fits(g.fam) ? 1 : 2;
   }
-  if (g.sb8) { g.NW = 4; g.RBW = bm8 / 128; }
-  g.BM = 32 * g.NW * g.RBW;
-  g.n_rp = (c->M + g.BM - 1) / g.BM;
+  g.n_rp = (c->M + g.fam->BM() - 1) / g.fam->BM();
   g.n_ct_all = (c->N + PMF_BN - 1) / PMF_BN;
   int reserve = c->comm.nranks > 1 ? c->comm.reserve_cus : 0;
   if (const char *e = getenv("PMF_RESERVE_CUS")) reserve = std::max(0, std::min(atoi(e), c->n_cu / 2));   // (tests / A-B: a one-rank run with the multi-rank grid)
@@ -1625,9 +1665,9 @@ FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chun
       S = 2;
       while (S < 4 && 30e-6 + bytes / S / algbw > t_pass * (S - 1) / S) ++S;
       // a chunk should give every workgroup a few dozen tiles at least (each launch pays its prologue and its tail).  Counted
-      // in REFERENCE panels of 256 rows, the unit the threshold was calibrated in -- not g.BM: the panel height belongs to the
-      // kernel family THIS rank runs (512 rows for pmf_fused_sb8_kernel at K <= 64, 128 where a rank's batch layout sends it to
-      // pmf_fused_sb2_kernel), and two ranks that disagreed on it chose different S, i.e. different collectives.
+      // in REFERENCE panels of 256 rows, the unit the threshold was calibrated in -- not the family's BM: the panel height belongs
+      // to the kernel family THIS rank runs (512 rows for pmf_fused_sb8_kernel at K <= 64, 256 where a rank's batch layout sends
+      // it to pmf_fused_sb2_kernel), and two ranks that disagreed on it chose different S, i.e. different collectives.
       constexpr int64_t REF_PANEL = 256;
       const int64_t n_rp_ref = (Mref + REF_PANEL - 1) / REF_PANEL;
       const int64_t min_tiles = 32ll * std::max(1, c->n_cu - c->comm.reserve_cus);
@@ -1669,12 +1709,14 @@ static void chunk_segments(pmf_ctx *c, const FusedGeom &g, int s, int &grid, int
 
 // Everything a data pass needs before its first launch: work splits of all chunks (cached), the gX slot map, buffers.
 int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy) {
+  if (!g.fam) return pmf_fail("unsupported KB=%d", c->KB);
+  const FusedFamily &f = *g.fam;
   if ((int)c->splits.size() < g.S) c->splits.resize((size_t)g.S);
   int64_t grid_sum = 0, serial_sum = 0;
   for (int s = 0; s < g.S; ++s) {
     int grid; int64_t tps, n_cseg;
     chunk_segments(c, g, s, grid, tps, n_cseg);
-    PMFCHK(compute_work_split(c, c->splits[(size_t)s], grid, g.n_rp, g.ct0[s], g.nct[s], tps, n_cseg, g.sb));
+    PMFCHK(compute_work_split(c, c->splits[(size_t)s], grid, g.n_rp, g.ct0[s], g.nct[s], tps, n_cseg, f.kernel != 0));
     grid_sum += grid;
   }
   serial_sum = c->split_serial * PMF_MAX_CHUNKS + g.S;   // (split_serial is bumped by every recomputed split)
@@ -1718,7 +1760,7 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     PMFCHK(dev_alloc(&c->gx_idx, idx.size(), false));
     HIPCHK(hipMemcpy(c->gx_off, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->gx_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
-    const size_t need = (size_t)base * (size_t)g.BM * (size_t)c->Kp;
+    const size_t need = (size_t)base * (size_t)f.BM() * (size_t)c->Kp;
     if (need > c->gx_part_cap) {
       dev_free(&c->gx_part);
       PMFCHK(dev_alloc(&c->gx_part, need, false));   // every slot is written whole by its piece before it is read
@@ -1727,16 +1769,17 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     c->gx_serial = serial_sum;
   }
   PMFCHK(ensure_tile_flags(c));
-  if (g.sb) {
-    const size_t xblk = c->KB == 1 ? SbCfg<1>::BLK : (c->KB == 2 ? std::max<size_t>(SbCfg<2>::BLK, Sb8Cfg<2>::XBLK) : Sb4Cfg<4>::XBLK);
-    const size_t yblk = c->KB == 1 ? SbCfg<1>::BLK : (c->KB == 2 ? std::max<size_t>(SbCfg<2>::BLK, Sb8Cfg<2>::YBLK) : std::max<size_t>(Sb4Cfg<4>::YBLK, Sb8Cfg<4>::YBLK));
-    // X images + sixteen row blocks: pmf_fused_sb8_kernel reads every block of its last panel, the absent ones unclamped, so
-    // sb_split_x writes whole panels, roundup(nRB, NBLK) <= nRB + 15 blocks of Sb8Cfg::XBLK <= xblk bytes each.  The
-    // capacity counts the sixteen blocks at THIS xblk (a buffer allocated at another KB may hold fewer bytes of padding).
-    const size_t xb = ((size_t)c->nRB + 16) * xblk, yb = (size_t)g.n_ct_all * yblk;
+  if (f.img != IMG_NONE) {
+    // the image buffers are sized for the largest block of every family whose image rows are as wide as f's
+    size_t xblk = 0, yblk = 0;
+    for (const FusedFamily &o : fused_families)
+      if (o.img_kb == f.img_kb) { xblk = std::max<size_t>(xblk, o.xblk); yblk = std::max<size_t>(yblk, o.yblk); }
+    // X images + PMF_XSB_PAD row blocks: sb_split_x writes whole panels, roundup(nRB, nblk) blocks.  The capacity counts
+    // the padding at THIS xblk (a buffer allocated for narrower images may hold fewer bytes of it).
+    const size_t xb = ((size_t)c->nRB + PMF_XSB_PAD) * xblk, yb = (size_t)g.n_ct_all * yblk;
     if (xb > c->xsb_cap) { dev_free(&c->xsb); c->xsb_cap = 0; PMFCHK(dev_alloc(&c->xsb, xb, true)); c->xsb_cap = xb; }
     if (yb > c->ysb_cap) { dev_free(&c->ysb); c->ysb_cap = 0; PMFCHK(dev_alloc(&c->ysb, yb, false)); c->ysb_cap = yb; }
-    if (g.sb8 && !c->sb8_scale) {
+    if (f.img == IMG_SB8 && !c->sb8_scale) {
       PMFCHK(dev_alloc(&c->sb8_scale, (size_t)(1 + PMF_MAX_CHUNKS), false));
       PMFCHK(dev_alloc(&c->sb8_max, (size_t)(1 + PMF_MAX_CHUNKS)));
     }
@@ -1747,47 +1790,44 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
 // split-bf16 operand images (k_sb_split): X once per pass, sigma*Y per chunk (its columns only: the Y step of a later
 // chunk of the previous epoch may not have run yet when an earlier chunk is launched, pmf_fit)
 // pmf_fused_sb8_kernel's images: the power-of-two pre-scale of the f16 pair first (a device scalar: no host round trip)
-static int sb8_split(pmf_ctx *c, const float *src, const float4 *colp, int64_t n, int64_t nblk, int slot, int transposed, char *out) {
+static int sb8_split(pmf_ctx *c, const FusedFamily &f, const float *src, const float4 *colp, int64_t n, int64_t nblk, int slot,
+                     int transposed, char *out) {
   Sb8ScaleArgs sa = {src, colp, n, c->Kp, c->sb8_max + slot, c->sb8_scale + slot};
   PMFCHK(pmf_launch_sb8_scale(c->stream, sa));
   Sb8SplitArgs sp = {src, colp, c->sb8_scale + slot, n, nblk, transposed, out};
-  return pmf_launch_sb8_split(c->stream, sp, c->KB);
+  return pmf_launch_sb8_split(c->stream, sp, f.KB);
 }
-static int sb_split_x(pmf_ctx *c, bool sb8) {
-  if (sb8) {
+static int sb_split_x(pmf_ctx *c, const FusedFamily &f) {
+  if (f.img == IMG_SB8) {
     // whole panels: k_sb8_split writes zero images for the absent row blocks of a ragged last panel, which the kernel reads
     // unclamped (GEMM3's transposed X fragments; G is zero there, but 0 x a stale NaN is not).  Within the allocation:
-    // roundup(nRB, NBLK) * Sb8Cfg::XBLK <= (nRB + 15) * xblk (prepare_fused_pass)
-    const int64_t nblk = c->KB == 4 ? Sb8Cfg<4>::NBLK : Sb8Cfg<2>::NBLK;
-    return sb8_split(c, c->P[0].p, nullptr, c->M, (c->nRB + nblk - 1) / nblk * nblk, 0, 1, c->xsb);
+    // roundup(nRB, nblk) <= nRB + PMF_XSB_PAD blocks (prepare_fused_pass)
+    return sb8_split(c, f, c->P[0].p, nullptr, c->M, (c->nRB + f.nblk - 1) / f.nblk * f.nblk, 0, 1, c->xsb);
   }
-  if (c->KB > 2) {
+  if (f.img == IMG_SB4) {
     Sb4SplitArgs s4 = {c->P[0].p, nullptr, c->M, c->nRB, c->Kp, 1, c->xsb};
     return pmf_launch_sb4_split(c->stream, s4);
   }
   SbSplitArgs sx = {c->P[0].p, nullptr, c->M, c->nRB, c->xsb};
-  return c->KB == 1 ? pmf_launch_sb_split_1(c->stream, sx) : pmf_launch_sb_split_2(c->stream, sx);
+  return f.KB == 1 ? pmf_launch_sb_split_1(c->stream, sx) : pmf_launch_sb_split_2(c->stream, sx);
 }
-static int sb_split_y(pmf_ctx *c, int64_t ct0, int64_t nct, bool sb8, int chunk) {
-  if (sb8) {
-    const int64_t c0 = ct0 * 32;
-    return sb8_split(c, c->P[1].p + c0 * c->Kp, c->colp + c0, std::min<int64_t>(c->N - c0, nct * 32), nct, 1 + chunk, 0,
-                     c->ysb + (size_t)ct0 * (c->KB == 4 ? Sb8Cfg<4>::YBLK : Sb8Cfg<2>::YBLK));
-  }
-  if (c->KB > 2) {
-    const int64_t c0 = ct0 * 32;
-    Sb4SplitArgs s4 = {c->P[1].p + c0 * c->Kp, c->colp + c0, c->N - c0, nct, c->Kp, 0, c->ysb + (size_t)ct0 * Sb4Cfg<4>::YBLK};
+static int sb_split_y(pmf_ctx *c, const FusedFamily &f, int64_t ct0, int64_t nct, int chunk) {
+  const int64_t c0 = ct0 * 32;
+  const float *src = c->P[1].p + c0 * c->Kp;
+  char *out = c->ysb + (size_t)ct0 * (size_t)f.yblk;
+  if (f.img == IMG_SB8) return sb8_split(c, f, src, c->colp + c0, std::min<int64_t>(c->N - c0, nct * 32), nct, 1 + chunk, 0, out);
+  if (f.img == IMG_SB4) {
+    Sb4SplitArgs s4 = {src, c->colp + c0, c->N - c0, nct, c->Kp, 0, out};
     return pmf_launch_sb4_split(c->stream, s4);
   }
-  const size_t blk = c->KB == 1 ? SbCfg<1>::BLK : SbCfg<2>::BLK;
-  const int64_t col0 = ct0 * 32;
-  SbSplitArgs sy = {c->P[1].p + col0 * c->Kp, c->colp + col0, c->N - col0, nct, c->ysb + (size_t)ct0 * blk};
-  return c->KB == 1 ? pmf_launch_sb_split_1(c->stream, sy) : pmf_launch_sb_split_2(c->stream, sy);
+  SbSplitArgs sy = {src, c->colp + c0, c->N - c0, nct, out};
+  return f.KB == 1 ? pmf_launch_sb_split_1(c->stream, sy) : pmf_launch_sb_split_2(c->stream, sy);
 }
 
 // One chunk of the data pass: the fused kernel over column tiles [ct0, ct0 + nct) and the fixed-order reduction of its
 // private gY slabs; after the LAST chunk, the fixed-order reduction of the gX partial slabs.
 int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool want_gy) {
+  const FusedFamily &f = *g.fam;
   WorkSplit &ws = c->splits[(size_t)s];
   const int grid = ws.grid;
   int grid_dummy; int64_t tiles_per_seg, n_cseg;
@@ -1813,7 +1853,7 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   a.M = c->M; a.N = c->N; a.n_tiles = n_rp * n_ct; a.tps = (int)tiles_per_seg; a.n_ct = (int)n_ct; a.n_cseg = (int)n_cseg;
   a.want_gx = want_gx; a.want_gy = want_gy;
   a.ct0 = (int32_t)g.ct0[s];
-  a.gx_part = c->gx_part; a.piece_base = ws.d_piece_base_abs; a.gx_slot_stride = (int64_t)g.BM * c->Kp;
+  a.gx_part = c->gx_part; a.piece_base = ws.d_piece_base_abs; a.gx_slot_stride = (int64_t)f.BM() * c->Kp;
   {
     const char *dbg = getenv("PMF_DEBUG_FLAGS");
     a.dbg = dbg ? atoi(dbg) : 0;
@@ -1829,11 +1869,11 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
 #endif
   a.views = c->d_views;
   const bool batch = c->n_bv > 0;
-  if (g.sb) {
-    if (s == 0) PMFCHK(sb_split_x(c, g.sb8));
-    PMFCHK(sb_split_y(c, g.ct0[s], n_ct, g.sb8, s));
+  if (f.img != IMG_NONE) {
+    if (s == 0) PMFCHK(sb_split_x(c, f));
+    PMFCHK(sb_split_y(c, f, g.ct0[s], n_ct, s));
     a.Xsb = c->xsb; a.Ysb = c->ysb;
-    if (g.sb8) { a.sb_scale_x = c->sb8_scale; a.sb_scale_y = c->sb8_scale + 1 + s; }
+    if (f.img == IMG_SB8) { a.sb_scale_x = c->sb8_scale; a.sb_scale_y = c->sb8_scale + 1 + s; }
   }
   // timing events
   if (c->ev_used == c->ev_pool.size()) {
@@ -1849,47 +1889,19 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   }
   auto &ev = c->ev_pool[c->ev_used++];
   HIPCHK(hipEventRecord(ev.first, c->stream));
-  int rc = 0;
-  if (g.sb) {
-    const bool d16 = c->store == PMF_STORE_BF16;
-    typedef int (*sb_fn)(PmfDynLds *, hipStream_t, const FusedArgs &, int, bool, bool, bool, bool);
-    // K in 33..64: the four-wave, two-row-block variant (pmf_fused_sb2.hip.inc); PMF_SB2=0 selects the eight-wave one
-    static const bool use_sb2 = !(getenv("PMF_SB2") && atoi(getenv("PMF_SB2")) == 0);
-    const sb_fn fn = c->KB == 1 ? (d16 ? pmf_launch_fused_sb_1_bf16 : pmf_launch_fused_sb_1)
-                   : c->KB == 2 ? (use_sb2 ? (d16 ? pmf_launch_fused_sb2_bf16 : pmf_launch_fused_sb2)
-                                           : (d16 ? pmf_launch_fused_sb_2_bf16 : pmf_launch_fused_sb_2))
-                   : c->KB == 3 ? (d16 ? pmf_launch_fused_sb4_3_bf16 : pmf_launch_fused_sb4_3)
-                                : (d16 ? pmf_launch_fused_sb4_4_bf16 : pmf_launch_fused_sb4_4);
-    c->last_kernel = g.sb8 ? 8 : (c->KB >= 3 ? 4 : (c->KB == 2 && use_sb2 ? 2 : 1));
-    if (g.sb8) rc = (c->KB == 4 ? (d16 ? pmf_launch_fused_sb8_4_bf16 : pmf_launch_fused_sb8_4)
-                                : (d16 ? pmf_launch_fused_sb8_2_bf16 : pmf_launch_fused_sb8_2))(&c->dyn_lds, c->stream, a, grid, batch, c->mixed);
-    else rc = fn(&c->dyn_lds, c->stream, a, grid, batch, c->mixed, want_gx, want_gy);
-    c->sb_launches += 1;
-  } else {
-    typedef int (*ex_fn)(PmfDynLds *, hipStream_t, const FusedArgs &, int, bool, bool);
-    const bool d16 = c->store == PMF_STORE_BF16;
-    ex_fn fn = nullptr;
-    switch (c->KB * 10 + g.RBW) {
-      case 11: fn = d16 ? pmf_launch_fused_exact_11_bf16 : pmf_launch_fused_exact_11; break;
-      case 12: fn = d16 ? pmf_launch_fused_exact_12_bf16 : pmf_launch_fused_exact_12; break;
-      case 21: fn = d16 ? pmf_launch_fused_exact_21_bf16 : pmf_launch_fused_exact_21; break;
-      case 31: fn = d16 ? pmf_launch_fused_exact_31_bf16 : pmf_launch_fused_exact_31; break;
-      case 41: fn = d16 ? pmf_launch_fused_exact_41_bf16 : pmf_launch_fused_exact_41; break;
-      default: return pmf_fail("unsupported KB=%d", c->KB);
-    }
-    c->last_kernel = 0;
-    rc = fn(&c->dyn_lds, c->stream, a, grid, batch, c->mixed);
-  }
+  c->last_kernel = f.kernel;
+  const int rc = f.launch[c->store == PMF_STORE_BF16](&c->dyn_lds, c->stream, a, grid, batch, c->mixed);
+  if (f.kernel != 0) c->sb_launches += 1;
   PMFCHK(rc);
   HIPCHK(hipEventRecord(ev.second, c->stream));   // the events bracket pmf_fused_kernel alone (= rocprofv3's kernel duration)
   if (want_gy && !(a.dbg & 8)) {
     k_gy_reduce<<<dim3((unsigned)n_ct, (unsigned)(32 * c->Kp / 256)), 64, 0, c->stream>>>(c->gy_slabs, slab_stride, ws.c_off, ws.c_idx,
                                                                                       c->Kp, c->N, c->P[1].g, (int)g.ct0[s],
-                                                                                      g.sb8 ? c->colp : nullptr);
+                                                                                      f.img == IMG_SB8 ? c->colp : nullptr);
     HIPCHK(hipGetLastError());
   }
   if (want_gx && s == g.S - 1) {
-    const int64_t panel = (int64_t)g.BM * c->Kp;
+    const int64_t panel = (int64_t)f.BM() * c->Kp;
     k_gx_reduce<<<dim3((unsigned)g.n_rp, (unsigned)((panel / 4 + 255) / 256)), 256, 0, c->stream>>>(
         c->gx_part, panel, c->gx_off, c->gx_idx, panel, (int64_t)c->Kp * c->M, c->P[0].g);
     HIPCHK(hipGetLastError());

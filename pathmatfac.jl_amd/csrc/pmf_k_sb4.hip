@@ -19,11 +19,10 @@
 #define PMF_SB4NAME(kb) PMF_NAME2(pmf_launch_fused_sb4_, kb)
 #endif
 
-int PMF_SB4NAME(PMF_KB)(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed, bool want_gx,
-                        bool want_gy) {
+int PMF_SB4NAME(PMF_KB)(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed) {
   void (*kern)(const FusedArgs) = nullptr;
-#define PMF_SB_PICK_G(MX, BT) (want_gx && want_gy ? pmf_fused_sb4_kernel<PMF_KB, MX, true, true, BT, PMF_DB != 0>                                   \
-                               : want_gx ? pmf_fused_sb4_kernel<PMF_KB, MX, true, false, BT, PMF_DB != 0>                                          \
+#define PMF_SB_PICK_G(MX, BT) (a.want_gx && a.want_gy ? pmf_fused_sb4_kernel<PMF_KB, MX, true, true, BT, PMF_DB != 0>                                 \
+                               : a.want_gx ? pmf_fused_sb4_kernel<PMF_KB, MX, true, false, BT, PMF_DB != 0>                                        \
                                          : pmf_fused_sb4_kernel<PMF_KB, MX, false, true, BT, PMF_DB != 0>)
   kern = batch ? PMF_SB_PICK_G(true, true) : (mixed ? PMF_SB_PICK_G(true, false) : PMF_SB_PICK_G(false, false));
 #undef PMF_SB_PICK_G
