@@ -161,6 +161,32 @@ int pmf_add_yreg_ard(pmf_ctx *ctx, int n_ranges, const int64_t *starts1, const i
                      const float *beta, float p);
 int pmf_add_yreg_fsard(pmf_ctx *ctx, const float *alpha, const float *beta, float p);
 
+/* The pathway-graph regularizers (fit_non_ard!, src/fit.jl:730-745), on X (n = local rows) or Y (n = N).
+ *
+ * One sparse block in 0-based CSR with sorted rows.  AA and BB are symmetric, so a Julia host passes `colptr` and
+ * `rowval .- 1` of its SparseMatrixCSC as they are; the library builds AB' itself. */
+typedef struct pmf_csr { int64_t n_rows, n_cols; const int64_t *rowptr; const int32_t *col; const float *val; } pmf_csr;
+/*   pmf_add_xreg_network / pmf_add_yreg_network : NetworkRegularizer call + rrule (src/regularizers.jl:249-306) with the
+ *     blocks its constructor makes (:189-238): per factor k, AA[k] (n x n), AB[k] (n x v_k), BB[k] (v_k x v_k);
+ *     loss = sum_k 0.5 p_k'AA_k p_k + p_k'AB_k u_k + 0.5 u_k'BB_k u_k with u_k = -BB_k^{-1} AB_k' p_k (`x_virtual[k]`)
+ *     found by conjugate gradients on the device every epoch (stop at |r| <= 1e-6 |AB_k' p_k| or after 2 v_k
+ *     iterations; warm start: the previous epoch's u_k).  v_k = 0 and empty graphs are legal.
+ *     `K` must equal the context's K.  u0: K pointers to initial u_k (or NULL pointers / NULL for zeros); the state
+ *     lives until the regularizer is cleared.  One network term per parameter.  With more than one rank a network
+ *     term on X makes pmf_fit fail (rows are sharded); one on Y is evaluated by every rank alike.
+ *   pmf_get_reg_network_state : u_k (v_k floats; `u` may be NULL) and the CG iterations of the last solve of factor k
+ *     (0-based) of the term on `which` (PMF_PARAM_X | PMF_PARAM_Y): what `nr.x_virtual[k]` holds after a call (:257).
+ *   pmf_add_xreg_l1 / pmf_add_yreg_l1 : sum_k w[k] sum_j |m_kj P_kj|, gradient w[k] sign(m_kj P_kj), sign(0) = 0:
+ *     SelectiveL1Reg (src/regularizers.jl:130-146; mask = l1_idx, K x n column-major bytes) and L1Regularizer
+ *     (:71-82; mask NULL = every entry). */
+int pmf_add_xreg_network(pmf_ctx *ctx, int K, const pmf_csr *AA, const pmf_csr *AB, const pmf_csr *BB,
+                         const float *const *u0, float p);
+int pmf_add_yreg_network(pmf_ctx *ctx, int K, const pmf_csr *AA, const pmf_csr *AB, const pmf_csr *BB,
+                         const float *const *u0, float p);
+int pmf_get_reg_network_state(pmf_ctx *ctx, int which, int k, float *u, int *cg_iters);
+int pmf_add_xreg_l1(pmf_ctx *ctx, const float *w, const uint8_t *mask, float p);
+int pmf_add_yreg_l1(pmf_ctx *ctx, const float *w, const uint8_t *mask, float p);
+
 /* matfac.col_transform_reg = SequenceReg (src/regularizers.jl:896-926):
  *   regs[1], regs[3] : ColParamReg(col_ranges, weights, centers) on logsigma / mu   (:462-487)
  *   regs[2], regs[4] : BatchArrayReg(centers, weights) on logdelta / theta          (:781-815)

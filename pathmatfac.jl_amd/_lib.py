@@ -38,6 +38,22 @@ class FitResult(C.Structure):
                 ("seconds", C.c_double)]
 
 
+class Csr(C.Structure):
+    """pmf_csr: one sparse block in 0-based CSR with sorted rows."""
+    _fields_ = [("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rowptr", C.POINTER(C.c_int64)),
+                ("col", C.POINTER(C.c_int32)), ("val", C.POINTER(C.c_float))]
+
+
+def csr_arrays(A):
+    """A scipy sparse matrix -> (shape, rowptr int64, col int32, val float32) as pmf_csr wants them."""
+    import scipy.sparse as sp
+    A = sp.csr_matrix(A)
+    A.sum_duplicates()
+    A.sort_indices()
+    return (A.shape, np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int32),
+            np.ascontiguousarray(A.data, dtype=np.float32))
+
+
 # every symbol include/pmf_hip.h declares (checked by tests/test_abi.py against the header and the .so)
 EXPORTS = [
     "pmf_last_error", "pmf_version", "pmf_device_count", "pmf_create", "pmf_destroy", "pmf_set_stream", "pmf_synchronize",
@@ -51,6 +67,7 @@ EXPORTS = [
     "pmf_set_precision", "pmf_get_precision",
     "pmf_comm_get_unique_id", "pmf_comm_init", "pmf_comm_init_host", "pmf_comm_destroy", "pmf_comm_set_chunks",
     "pmf_comm_info", "pmf_comm_allreduce", "pmf_get_opt_state", "pmf_fsard_update_A", "pmf_debug_last_path", "pmf_debug_last_kernel",
+    "pmf_add_xreg_network", "pmf_add_yreg_network", "pmf_get_reg_network_state", "pmf_add_xreg_l1", "pmf_add_yreg_l1",
 ]
 
 COMM_ID_BYTES = 128
@@ -282,6 +299,57 @@ class Context:
         if a.shape != (self.N,) or b.shape != (self.K, self.N):
             raise PMFError("FeatureSetARD: alpha must be N, beta K x N")
         self._chk(self.lib.pmf_add_yreg_fsard(self._h, _fp(a), _fp(b), C.c_float(p)))
+
+    def add_reg_network(self, which, AA, AB, BB, u0=None, p=1.0):
+        """NetworkRegularizer: per factor the scipy sparse blocks AA (n x n), AB (n x v_k), BB (v_k x v_k); u0: per factor
+        the initial u_k (the reference's x_virtual) or None for zeros."""
+        K = len(AA)
+        keep, blocks = [], []
+        for mats in (AA, AB, BB):
+            arr = (Csr * K)()
+            for k, A in enumerate(mats):
+                shape, rp, col, val = csr_arrays(A)
+                keep.append((rp, col, val))
+                arr[k] = Csr(shape[0], shape[1], rp.ctypes.data_as(C.POINTER(C.c_int64)),
+                             col.ctypes.data_as(C.POINTER(C.c_int32)), _fp(val))
+            blocks.append(arr)
+        up = None
+        if u0 is not None:
+            us = [_f32(np.asarray(u).ravel()) for u in u0]
+            for k, (u, B) in enumerate(zip(us, BB)):
+                if u.shape != (B.shape[0],):
+                    raise PMFError(f"network regularizer: u0[{k}] has {u.shape[0]} entries, BB[{k}] {B.shape[0]} rows")
+            keep.append(us)
+            up = (C.POINTER(C.c_float) * K)(*[_fp(u) for u in us])
+        f = self.lib.pmf_add_xreg_network if which == "X" else self.lib.pmf_add_yreg_network
+        self._chk(f(self._h, K, blocks[0], blocks[1], blocks[2], up, C.c_float(p)))
+        if not hasattr(self, "_net_v"):
+            self._net_v = {}
+        self._net_v[which] = [int(B.shape[0]) for B in BB]
+
+    def get_reg_network_state(self, which, k):
+        """(u_k, CG iterations of the last solve) of factor k (0-based) of the network term on X / Y."""
+        v = getattr(self, "_net_v", {}).get(which)
+        n = v[k] if v is not None and 0 <= k < len(v) else 0
+        u = np.zeros(n, np.float32)
+        it = C.c_int(0)
+        self._chk(self.lib.pmf_get_reg_network_state(self._h, PARAM[which], int(k), _fp(u) if n else None, C.byref(it)))
+        return u, it.value
+
+    def add_reg_l1(self, which, w, mask=None, p=1.0):
+        """L1Regularizer (mask None) / SelectiveL1Reg (mask = l1_idx, K x n booleans)."""
+        w = _f32(np.asarray(w).ravel())
+        n = self.M if which == "X" else self.N
+        if w.shape != (self.K,):
+            raise PMFError(f"L1 weights must have K = {self.K} entries; got {w.shape}")
+        mp = None
+        if mask is not None:
+            m = np.require(np.asarray(mask, dtype=np.uint8), requirements=["F", "A"])
+            if m.shape != (self.K, n):
+                raise PMFError(f"L1 mask must be K x n = ({self.K}, {n}); got {m.shape}")
+            mp = m.ctypes.data_as(C.POINTER(C.c_uint8))
+        f = self.lib.pmf_add_xreg_l1 if which == "X" else self.lib.pmf_add_yreg_l1
+        self._chk(f(self._h, _fp(w), mp, C.c_float(p)))
 
     def set_layer_regs(self, ranges=None, w_logsigma=None, c_logsigma=None, w_mu=None, c_mu=None,
                        w_logdelta=None, c_logdelta=None, w_theta=None, c_theta=None):

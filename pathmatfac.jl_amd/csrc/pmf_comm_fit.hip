@@ -283,6 +283,10 @@ extern "C" int pmf_fit(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
   PMFCHK(check_ready(c));
   if (!o || !res) return pmf_fail("null opts/result");
   if (c->comm.broken) return pmf_fail("the communicator is unusable after a failed fit: pmf_comm_destroy it on every rank");
+  // rows are sharded: a network term on X would couple rows that live on different ranks.  Every rank holds the same
+  // regularizers and refuses alike, before any collective of this fit is issued (the communicator stays usable).
+  if (o->update_X && c->net[0] && comm_active(c) && c->comm.nranks > 1)
+    return pmf_fail("a NetworkRegularizer on X is not supported with %d ranks: X is sharded by rows and the network couples rows across ranks (drop the term or fit on one rank)", c->comm.nranks);
   const int rc = fit_loop(c, o, res);
   if (rc < 0) {
     const std::string msg = pmf_last_error();
@@ -369,7 +373,10 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
     RegCounts rc;
     for (int q = 0; q < 4; ++q) rc.c[q] = 0;
     // ---- X step (row-local) and the rank-local part of the loss: data term + X regularizer
-    if (ux) PMFCHK(step_param(c, 0, true, true, 0, &rc.c[0]));
+    if (ux) {
+      PMFCHK(netreg_eval(c, 0, &rc.c[0]));
+      PMFCHK(step_param(c, 0, true, true, 0, &rc.c[0]));
+    }
     PMFCHK(launch_loss_reduce(c, rc, 0x03));
     if (cm) {
       PMFCHK(comm_after_compute(c, m.ev_loss_ready));
@@ -377,13 +384,17 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
       PMFCHK(comm_mark(c, m.ev_loss_done));
     }
     in_flight = false;
-    // ---- replicated parameters, chunk by chunk; the next epoch's chunk follows its Y step
+    // ---- replicated parameters, chunk by chunk; the next epoch's chunk follows its Y step.  A network term on Y couples
+    // columns across chunks: it is evaluated here, once, from the whole Y as this epoch's data pass saw it, into a
+    // buffer of its own, before the first chunk is stepped (the Y steps below only read that buffer).
+    if (uy) PMFCHK(netreg_eval(c, 1, &rc.c[1]));
+    const int y_blocks = (REG_SLOTS - rc.c[1]) / S;
     for (int s = 0; s < S; ++s) {
       if (uy) {
         if (cm) PMFCHK(compute_after_comm(c, m.ev_done[(size_t)s]));
         const int64_t col0 = fused ? g.ct0[s] * 32 : 0;
         const int64_t col1 = fused ? std::min<int64_t>(c->N, (g.ct0[s] + g.nct[s]) * 32) : c->N;
-        PMFCHK(step_param_range(c, 1, col0 * c->Kp, (col1 - col0) * c->Kp, true, true, 1, &rc.c[1], REG_SLOTS / S, s == S - 1));
+        PMFCHK(step_param_range(c, 1, col0 * c->Kp, (col1 - col0) * c->Kp, true, true, 1, &rc.c[1], y_blocks, s == S - 1));
       }
       if (s == S - 1) {
         if (ul) {

@@ -3,6 +3,7 @@
 //   pmf_hip.hip       C ABI (marshalling, step-level API, statistics), small kernels, work split, data-pass launches
 //   pmf_comm_fit.hip  cross-rank exchange (RCCL via dlopen / host-staged transport) and the epoch loop pmf_fit
 //   pmf_fsard.hip     the FeatureSetARD update_A! solver (ISTA on the device)
+//   pmf_netreg.hip    NetworkRegularizer (per-factor CG solve + sparse gradient) and the L1 / SelectiveL1 weights
 #ifndef PMF_CTX_H
 #define PMF_CTX_H
 #include <hip/hip_runtime.h>
@@ -26,6 +27,7 @@
 struct ParamBuf {  // one trainable parameter tensor with its gradient, optimizer state and quadratic regularizer
   float *p = nullptr, *g = nullptr, *acc = nullptr, *mom = nullptr;
   float *wq = nullptr, *cq = nullptr;  // dense quadratic weights / centres: 0.5*wq*(p-cq)^2 (nullptr = none)
+  float *wl1 = nullptr;                // dense L1 weights w_k m_kj p: wl1*|p| (L1Regularizer / SelectiveL1Reg; nullptr = none)
   int64_t n = 0;
   float bp1 = 0.f, bp2 = 0.f;  // Adam running beta powers
 };
@@ -77,6 +79,29 @@ struct Comm {
   std::vector<hipEvent_t> ev_ready, ev_done;   // per chunk: gY slice complete / its all-reduce complete
   hipEvent_t ev_loss_ready = nullptr, ev_loss_done = nullptr, ev_layer_ready = nullptr, ev_layer_done = nullptr;
   int64_t n_allreduce = 0;         // collectives issued (diagnostics / tests)
+};
+
+// NetworkRegularizer on X (n = M) or Y (n = N): per factor k the sparse blocks AA_k (n x n), AB_k (n x v_k), AB_k' and
+// BB_k (v_k x v_k), each family concatenated over the factors into one CSR whose row pointers are absolute (factor k's
+// rows start at k * (n + 1) for AA / AB and at voff[k] + k for AB' / BB).  State: u (the reference's x_virtual), kept from
+// epoch to epoch as the warm start of the next solve.  See pmf_netreg.hip.
+struct NetReg {
+  int K = 0;
+  int64_t n = 0, V = 0;            // V = sum of v_k
+  float p = 1.f;                   // mixture weight
+  std::vector<int64_t> h_voff;     // [K + 1]
+  int64_t *voff = nullptr;         // device copy
+  int64_t *aa_rp = nullptr, *ab_rp = nullptr, *abt_rp = nullptr, *bb_rp = nullptr;
+  int32_t *aa_col = nullptr, *ab_col = nullptr, *abt_col = nullptr, *bb_col = nullptr;
+  float *aa_val = nullptr, *ab_val = nullptr, *abt_val = nullptr, *bb_val = nullptr;
+  float *u = nullptr;              // [V]
+  float *work = nullptr;           // [4 V] t, r, d, BB d of the factors whose v_k exceeds the LDS budget
+  float *PT = nullptr;             // [K][n] factor-major copy of the parameter, rebuilt every epoch
+  float *grad = nullptr;           // [Kp * n] p * (AA_k p_k + AB_k u_k), in the parameter's own layout (read by k_reg_step_graph)
+  int32_t *iters = nullptr;        // [K] CG iterations of the last solve
+  double *uloss = nullptr;         // [K] t'u + 0.5 u'BB u of the last solve
+  int rb = 1;                      // row blocks per factor of the gradient kernel (= loss partials per factor)
+  int64_t vmax = 0;                // largest v_k
 };
 
 struct pmf_ctx {
@@ -165,6 +190,7 @@ struct pmf_ctx {
   size_t ev_used = 0;
   double kernel_ms_sum = 0.0;
   int64_t kernel_launches = 0;
+  NetReg *net[2] = {nullptr, nullptr};   // NetworkRegularizer on X / Y (nullptr = none)
   int reg_counts[4] = {0, 0, 0, 0};  // used slots of the regularizer partial slabs (0 X, 1 Y, 2 column layers)
   // scratch
   void *scratch = nullptr;
@@ -239,6 +265,11 @@ int step_layers(pmf_ctx *c, const pmf_fit_opts *o, int *reg_count);
 // fixed-order reduction of the loss partial slabs into d_loss[which] for every bit `which` of mask (0 data term, 1 X reg,
 // 2 Y reg, 3 layer regs, 4 spare)
 int launch_loss_reduce(pmf_ctx *c, const RegCounts &rc, int mask);
+// ---- defined in pmf_netreg.hip
+void netreg_free(pmf_ctx *c, int which);   // drops the network term of X (0) / Y (1) and its state
+// evaluates the network term from the current parameter: u_k, its gradient buffer and its loss partials (appended to
+// slab `which`, *reg_count moved on).  No-op without a term.
+int netreg_eval(pmf_ctx *c, int which, int *reg_count);
 // ---- defined in pmf_comm_fit.hip
 int comm_release(pmf_ctx *c);
 bool comm_active(const pmf_ctx *c);

@@ -43,10 +43,11 @@ static int param_alloc(ParamBuf &b, int64_t n) {
   PMFCHK(dev_alloc(&b.mom, n));
   dev_free(&b.wq);
   dev_free(&b.cq);
+  dev_free(&b.wl1);
   return 0;
 }
 static void param_free(ParamBuf &b) {
-  dev_free(&b.p); dev_free(&b.g); dev_free(&b.acc); dev_free(&b.mom); dev_free(&b.wq); dev_free(&b.cq);
+  dev_free(&b.p); dev_free(&b.g); dev_free(&b.acc); dev_free(&b.mom); dev_free(&b.wq); dev_free(&b.cq); dev_free(&b.wl1);
   b.n = 0;
 }
 
@@ -201,12 +202,19 @@ struct StepArgs {
   int use_reg;
   double *reg_partial;  // [REG_SLOTS]
 };
+struct StepArgsGraph {           // k_reg_step_graph: the same, plus the pathway-graph terms (at least one of them set)
+  StepArgs a;
+  const float *gpre;             // gradient of a term evaluated beforehand (NetworkRegularizer, pmf_netreg.hip; may be null)
+  const float *wl1;              // dense L1 weights (L1Regularizer / SelectiveL1Reg; may be null)
+};
 
 // Regularizer gradient + optimizer step, one pass over a parameter tensor.
 //   quadratic : 0.5*wq*(p-cq)^2  (L2Regularizer regularizers.jl:21-33, GroupRegularizer :423-446,
 //               ColParamReg :482-487, BatchArrayReg :795-815)
 //   ARD       : (0.5+alpha_j) log(1 + (0.5/beta) p^2), grad (alpha_j+0.5) p / (b beta)
 //               (ARDRegularizer :546-585, FeatureSetARDReg featureset_ard.jl:135-150)
+//   network   : gradient read from `gpre`, loss partials written by k_netreg_grad (NetworkRegularizer :249-306)
+//   L1        : wl1 |p|, grad wl1 sign(p), sign(0) = 0  (L1Regularizer :71-82, SelectiveL1Reg :130-146)
 //   AdaGrad   : acc += g^2 ; p -= eta g/(sqrt(acc)+eps)   (optimizers.jl:6-13 ; acc starts at eps)
 //   Adam      : Flux.Optimise.Adam
 __global__ __launch_bounds__(256) void k_reg_step(const StepArgs a) {
@@ -231,6 +239,57 @@ __global__ __launch_bounds__(256) void k_reg_step(const StepArgs a) {
         const float b = 1.f + (0.5f / be) * (p * p);
         lacc += (double)(a.ard_scale * (0.5f + al) * logf(b));
         g += a.ard_scale * ((al + 0.5f) * p / (b * be));
+      }
+    }
+    if (a.do_step) {
+      if (a.opt_kind == PMF_OPT_ADAGRAD) {
+        const float acc = a.acc[e] + g * g;
+        a.acc[e] = acc;
+        p -= g * (a.lr / (sqrtf(acc) + a.eps));
+      } else {
+        const float m = a.b1 * a.mom[e] + (1.f - a.b1) * g;
+        const float v = a.b2 * a.acc[e] + (1.f - a.b2) * g * g;
+        a.mom[e] = m;
+        a.acc[e] = v;
+        p -= m / a.c1 / (sqrtf(v / a.c2) + a.eps) * a.lr;
+      }
+      a.p[e] = p;
+    }
+  }
+  const double s = block_reduce_sum(lacc, sh);
+  if (threadIdx.x == 0 && a.reg_partial) a.reg_partial[blockIdx.x] = s;
+}
+// The same pass with the pathway-graph terms (launched only when one of them is set).  A kernel of its own on purpose:
+// k_reg_step above keeps its arguments and its code exactly, so a context without these terms runs what it always ran.
+__global__ __launch_bounds__(256) void k_reg_step_graph(const StepArgsGraph ga) {
+  const StepArgs &a = ga.a;
+  __shared__ double sh[4];
+  double lacc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < a.n; e += stride) {
+    const int k = (int)(e % a.Kp);
+    if (k >= a.K) continue;
+    float p = a.p[e];
+    float g = a.g[e];
+    if (a.use_reg) {
+      if (a.wq) {
+        const float d = p - (a.cq ? a.cq[e] : 0.f);
+        const float gr = a.wq[e] * d;
+        lacc += 0.5 * (double)(gr * d);
+        g += gr;
+      }
+      if (a.ard_beta) {
+        const int64_t j = e / a.Kp;
+        const float be = a.ard_beta[e], al = a.ard_alpha[j];
+        const float b = 1.f + (0.5f / be) * (p * p);
+        lacc += (double)(a.ard_scale * (0.5f + al) * logf(b));
+        g += a.ard_scale * ((al + 0.5f) * p / (b * be));
+      }
+      if (ga.gpre) g += ga.gpre[e];
+      if (ga.wl1) {
+        const float w = ga.wl1[e];
+        lacc += (double)(w * fabsf(p));
+        g += p > 0.f ? w : p < 0.f ? -w : 0.f;
       }
     }
     if (a.do_step) {
@@ -656,6 +715,8 @@ static int set_K(pmf_ctx *c, int K) {
   c->Kp = 32 * c->KB;
   PMFCHK(param_alloc(c->P[0], (int64_t)c->Kp * c->M));
   PMFCHK(param_alloc(c->P[1], (int64_t)c->Kp * c->N));
+  netreg_free(c, 0);
+  netreg_free(c, 1);
   dev_free(&c->ard_alpha);
   dev_free(&c->ard_beta);
   c->has_ard = false;
@@ -703,6 +764,8 @@ extern "C" int pmf_destroy(pmf_ctx *c) {
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
   for (auto &b : c->P) param_free(b);
+  netreg_free(c, 0);
+  netreg_free(c, 1);
   if (c->D) (void)hipFree(c->D);
   c->D = nullptr;
   dev_free(&c->tflags);
@@ -764,6 +827,8 @@ static int data_shape_changed(pmf_ctx *c, int64_t M, int64_t N) {
   c->M = M;
   c->N = N;
   for (auto &b : c->P) param_free(b);
+  netreg_free(c, 0);
+  netreg_free(c, 1);
   c->K = c->Kp = c->KB = 0;
   PMFCHK(param_alloc(c->P[2], N));
   PMFCHK(param_alloc(c->P[3], N));
@@ -1056,6 +1121,8 @@ static int add_quad_l2(pmf_ctx *c, int which, const float *w, float p) {
 extern "C" int pmf_clear_xreg(pmf_ctx *c) {
   PMFCHK(ctx_bind(c));
   dev_free(&c->P[0].wq);
+  dev_free(&c->P[0].wl1);
+  netreg_free(c, 0);
   return 0;
 }
 extern "C" int pmf_add_xreg_l2(pmf_ctx *c, const float *w, float p) {
@@ -1069,6 +1136,8 @@ extern "C" int pmf_add_xreg_group(pmf_ctx *c, int n, const int64_t *s1, const in
 extern "C" int pmf_clear_yreg(pmf_ctx *c) {
   PMFCHK(ctx_bind(c));
   dev_free(&c->P[1].wq);
+  dev_free(&c->P[1].wl1);
+  netreg_free(c, 1);
   c->has_ard = false;
   return 0;
 }
@@ -2070,6 +2139,9 @@ int step_param_range(pmf_ctx *c, int which, int64_t e0, int64_t n, bool do_step,
   s.Kp = which <= 1 ? c->Kp : 1;
   s.K = which <= 1 ? c->K : 1;
   if (which == 1 && c->has_ard) { s.ard_alpha = c->ard_alpha + e0 / s.Kp; s.ard_beta = c->ard_beta + e0; s.ard_scale = c->ard_scale; }
+  StepArgsGraph sg;
+  sg.gpre = which <= 1 && c->net[which] ? c->net[which]->grad + e0 : nullptr;
+  sg.wl1 = b.wl1 ? b.wl1 + e0 : nullptr;
   s.n = n;
   s.opt_kind = c->opt_kind; s.lr = c->lr; s.eps = c->eps; s.b1 = c->b1; s.b2 = c->b2;
   s.c1 = 1.f - b.bp1; s.c2 = 1.f - b.bp2;
@@ -2077,15 +2149,18 @@ int step_param_range(pmf_ctx *c, int which, int64_t e0, int64_t n, bool do_step,
   const int grid = (int)std::min<int64_t>(max_blocks, nblocks(n, 256));
   s.reg_partial = c->reg_partial + (int64_t)reg_slot * REG_SLOTS + *reg_count;
   if (*reg_count + grid > REG_SLOTS) return pmf_fail("internal: regularizer partial slab overflow");
-  k_reg_step<<<grid, 256, 0, c->stream>>>(s);
+  sg.a = s;
+  if (use_reg && (sg.gpre || sg.wl1)) k_reg_step_graph<<<grid, 256, 0, c->stream>>>(sg);
+  else k_reg_step<<<grid, 256, 0, c->stream>>>(s);
   HIPCHK(hipGetLastError());
   *reg_count += grid;
   if (advance && do_step && c->opt_kind == PMF_OPT_ADAM) { b.bp1 *= c->b1; b.bp2 *= c->b2; }
   return 0;
 }
 int step_param(pmf_ctx *c, int which, bool do_step, bool use_reg, int reg_slot, int *reg_count) {
-  // the four layer parameters share one slab of loss partials: each gets a quarter (k_reg_step is grid-stride)
-  return step_param_range(c, which, 0, c->P[which].n, do_step, use_reg, reg_slot, reg_count, reg_slot == 2 ? REG_SLOTS / 4 : REG_SLOTS, true);
+  // the four layer parameters share one slab of loss partials: each gets a quarter (k_reg_step is grid-stride); X / Y get
+  // what a network term evaluated before the step has left of theirs
+  return step_param_range(c, which, 0, c->P[which].n, do_step, use_reg, reg_slot, reg_count, reg_slot == 2 ? REG_SLOTS / 4 : REG_SLOTS - *reg_count, true);
 }
 // layer l <-> param: 1 logsigma(2), 2 logdelta(4), 3 mu(3), 4 theta(5)
 int step_layers(pmf_ctx *c, const pmf_fit_opts *o, int *reg_count) {
@@ -2148,13 +2223,19 @@ extern "C" int pmf_epoch_begin(pmf_ctx *c, const pmf_fit_opts *o) {
 
 extern "C" int pmf_epoch_step_local(pmf_ctx *c, const pmf_fit_opts *o) {
   PMFCHK(ctx_bind(c));
-  if (o->update_X) PMFCHK(step_param(c, 0, true, true, 0, &c->reg_counts[0]));
+  if (o->update_X) {
+    PMFCHK(netreg_eval(c, 0, &c->reg_counts[0]));
+    PMFCHK(step_param(c, 0, true, true, 0, &c->reg_counts[0]));
+  }
   return 0;
 }
 
 extern "C" int pmf_epoch_step_shared(pmf_ctx *c, const pmf_fit_opts *o) {
   PMFCHK(ctx_bind(c));
-  if (o->update_Y) PMFCHK(step_param(c, 1, true, true, 1, &c->reg_counts[1]));
+  if (o->update_Y) {
+    PMFCHK(netreg_eval(c, 1, &c->reg_counts[1]));
+    PMFCHK(step_param(c, 1, true, true, 1, &c->reg_counts[1]));
+  }
   if (o->update_col_layers) PMFCHK(step_layers(c, o, &c->reg_counts[2]));
   return 0;
 }

@@ -343,6 +343,14 @@ def _reorder_reg(reg, p):  # reorder_reg! (regularizers.jl:5, 53-55, 449-452; fe
         reg.weights[...] = reg.weights[p]
     elif isinstance(reg, GroupRegularizer):
         reg.group_weights = tuple(w[p] for w in reg.group_weights)
+    elif isinstance(reg, _R.L1Regularizer):                     # regularizers.jl:98-100
+        reg.weights[...] = reg.weights[p]
+    elif isinstance(reg, _R.SelectiveL1Reg):                    # :161-163 (the mask moves, the weights stay)
+        reg.l1_idx[...] = reg.l1_idx[p, :]
+    elif isinstance(reg, _R.NetworkRegularizer):                # :330-338
+        for name in ("AA", "AB", "BB", "x_virtual"):
+            setattr(reg, name, tuple(getattr(reg, name)[k] for k in p))
+        reg.cur_weights[...] = reg.cur_weights[p]
     elif isinstance(reg, FeatureSetARDReg):
         reg.beta[...] = reg.beta[p, :]
         for A in reg.A:
@@ -370,6 +378,27 @@ def reweight_eb_(reg, P, mixture_p=1.0):
         reg.group_weights = tuple(new)
     elif isinstance(reg, ARDRegularizer):
         reg.reweight_eb_(P)
+    elif isinstance(reg, _R.L1Regularizer):
+        # regularizers.jl:88-92: weights = mixture_p / var(row), Julia's `var` = sample variance (n - 1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            reg.weights[...] = mixture_p / np.var(P.astype(np.float64), axis=1, ddof=1)
+    elif isinstance(reg, _R.SelectiveL1Reg):
+        # :149-159: Laplace scale from the population variance of the masked row (zeros included); non-finite -> 1
+        sel = reg.l1_idx * P.astype(np.float64)
+        var = np.mean(sel * sel, axis=1) - np.mean(sel, axis=1) ** 2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            w = mixture_p * np.sqrt(2.0 / var)
+        w[~np.isfinite(w)] = 1.0
+        reg.weight[...] = w
+    elif isinstance(reg, _R.NetworkRegularizer):
+        # :313-328: every block of factor k rescaled by (mixture_p / var(row k)) / cur_weights[k]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            row_precs = mixture_p / np.var(P.astype(np.float64), axis=1, ddof=1)
+        ratio = row_precs / reg.cur_weights
+        reg.AA = tuple(A * r for A, r in zip(reg.AA, ratio))
+        reg.AB = tuple(A * r for A, r in zip(reg.AB, ratio))
+        reg.BB = tuple(A * r for A, r in zip(reg.BB, ratio))
+        reg.cur_weights[...] = row_precs
     elif isinstance(reg, _R.CompositeRegularizer):
         for r, p in zip(reg.regularizers, reg.mixture_p):
             reweight_eb_(r, P, mixture_p=p * mixture_p)

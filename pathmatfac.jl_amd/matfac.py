@@ -155,4 +155,7 @@ def fit_(mf, ctx, opt=None, lr=0.01, update_X=False, update_Y=False, update_col_
     else:
         h = ctx.fit(capacity=capacity, **kw)
     unmarshal(mf, ctx, update_X, update_Y, update_col_layers)
+    for reg, which, on in ((mf.X_reg, "X", update_X), (mf.Y_reg, "Y", update_Y)):
+        if on and hasattr(reg, "read_back"):      # the network term's virtual nodes (NetworkRegularizer.x_virtual)
+            reg.read_back(ctx, which)
     return h

@@ -1,12 +1,14 @@
 """Regularizers (src/regularizers.jl, src/featureset_ard.jl): host-side descriptors.
 
-Their value and gradient are evaluated on the device by k_reg_step (csrc/pmf_hip.hip); the classes below hold the
+Their value and gradient are evaluated on the device by k_reg_step / k_reg_step_graph (csrc/pmf_hip.hip); the classes below hold the
 parameters, mirror the reference's constructors and freeze bookkeeping, and know how to marshal themselves
-through the C ABI.  Network / L1 / SelectiveL1 regularizers are out of scope and raise."""
+through the C ABI.  The pathway-graph family (NetworkRegularizer, SelectiveL1Reg, L1Regularizer) builds its sparse
+blocks on the host (scipy) exactly as the reference's constructors do; the per-epoch solve for the virtual nodes runs
+on the device (csrc/pmf_netreg.hip)."""
 import numpy as np
 
 from .layers import BatchScale, BatchShift, ColScale, ColShift, FrozenLayer, Identity
-from .util import UnitRange, featuresets_to_dense, ids_to_ranges, unique
+from .util import UnitRange, featuresets_to_dense, ids_to_ranges, unique, value_to_idx
 
 
 class ZeroReg:
@@ -23,6 +25,96 @@ class L2Regularizer:  # regularizers.jl:11-55
 
     def add_to(self, ctx, which, p=1.0):
         ctx.add_reg_l2(which, self.weights, p)
+
+
+class L1Regularizer:  # regularizers.jl:60-100
+    def __init__(self, K_or_weights, w=None):
+        self.weights = (np.full(int(K_or_weights), float(w), dtype=np.float32) if w is not None
+                        else np.asarray(K_or_weights, dtype=np.float32))
+
+    def add_to(self, ctx, which, p=1.0):
+        ctx.add_reg_l1(which, self.weights, None, p)
+
+
+def get_all_nodes(edgelist):  # util.jl:420-428
+    nodes = set()
+    for e in edgelist:
+        nodes.add(e[0])
+        nodes.add(e[1])
+    return nodes
+
+
+def compute_nongraph_nodes(nodes, edgelists):  # util.jl:436-446
+    all_nodes = set(nodes)
+    return [all_nodes - get_all_nodes(el) for el in edgelists]
+
+
+class SelectiveL1Reg:  # regularizers.jl:106-163
+    def __init__(self, feature_ids, edgelists, weight=1.0):
+        l1_features = compute_nongraph_nodes(feature_ids, edgelists)
+        self.l1_idx = np.array([[f in l1 for f in feature_ids] for l1 in l1_features], dtype=bool).reshape(
+            len(l1_features), len(feature_ids))
+        self.weight = np.full(len(l1_features), float(weight), dtype=np.float32)
+
+    def add_to(self, ctx, which, p=1.0):
+        ctx.add_reg_l1(which, self.weight, self.l1_idx, p)
+
+
+def edgelist_to_spmat(edgelist, node_to_idx, epsilon=0.0):
+    """util.jl:269-314: symmetric matrix with -w off the diagonal and epsilon + sum |w| on it; of repeated edges the
+    last one counts.  `node_to_idx` is 1-based, like the reference's."""
+    import scipy.sparse as sp
+    N = len(node_to_idx)
+    edges = {}
+    for e in edgelist:
+        e1, e2 = node_to_idx[e[0]] - 1, node_to_idx[e[1]] - 1
+        edges[(max(e1, e2), min(e1, e2))] = float(e[2])
+    diag = np.full(N, float(epsilon))
+    I, J, V = [], [], []
+    for (i, j), v in edges.items():
+        I += [i, j]
+        J += [j, i]
+        V += [-v, -v]
+        diag[i] += abs(v)
+        diag[j] += abs(v)
+    I = np.concatenate([np.arange(N), np.asarray(I, dtype=np.int64)])
+    J = np.concatenate([np.arange(N), np.asarray(J, dtype=np.int64)])
+    V = np.concatenate([diag, np.asarray(V, dtype=np.float64)])
+    return sp.csr_matrix(sp.coo_matrix((V, (I, J)), shape=(N, N)))     # (duplicates are summed, as `sparse` does)
+
+
+def _sort_nodes(nodes):
+    try:
+        return sorted(nodes)
+    except TypeError:          # ids of mixed types have no order in Python: fall back to their text
+        return sorted(nodes, key=repr)
+
+
+class NetworkRegularizer:  # regularizers.jl:169-338
+    """AA / AB / BB: per factor the observed x observed, observed x virtual and virtual x virtual blocks (scipy CSR, f64);
+    x_virtual: the virtual nodes' values, found by CG on the device every epoch and read back after a fit."""
+
+    def __init__(self, feature_ids, edgelists, epsilon=0.1, weight=1.0):
+        N = len(feature_ids)
+        fset = set(feature_ids)
+        AA, AB, BB, xv = [], [], [], []
+        for edgelist in edgelists:
+            virtual = _sort_nodes(get_all_nodes(edgelist) - fset)                  # :203-208
+            node_to_idx = value_to_idx(list(feature_ids) + virtual)
+            spmat = edgelist_to_spmat(edgelist, node_to_idx, epsilon=epsilon) * float(weight)   # :212-213
+            AA.append(spmat[:N, :N].tocsr())                                        # csc_select, :222-224
+            AB.append(spmat[:N, N:].tocsr())
+            BB.append(spmat[N:, N:].tocsr())
+            xv.append(np.zeros(len(virtual), dtype=np.float64))
+        self.AA, self.AB, self.BB, self.x_virtual = tuple(AA), tuple(AB), tuple(BB), tuple(xv)
+        self.cur_weights = np.full(len(edgelists), float(weight), dtype=np.float64)
+
+    def add_to(self, ctx, which, p=1.0):
+        ctx.add_reg_network(which, self.AA, self.AB, self.BB, u0=self.x_virtual, p=p)
+
+    def read_back(self, ctx, which):
+        """x_virtual <- the device's u_k, so that the next stage warm-starts as the reference's object does (:257)."""
+        self.x_virtual = tuple(ctx.get_reg_network_state(which, k)[0].astype(np.float64) for k in range(len(self.AA)))
 
 
 class GroupRegularizer:  # regularizers.jl:345-359
@@ -108,6 +200,11 @@ class CompositeRegularizer:  # regularizers.jl:616-643
         for r, q in zip(self.regularizers, self.mixture_p):
             r.add_to(ctx, which, p * q)
 
+    def read_back(self, ctx, which):
+        for r in self.regularizers:
+            if hasattr(r, "read_back"):
+                r.read_back(ctx, which)
+
 
 def construct_composite_reg(regs, mixture_p):  # regularizers.jl:625-631
     if len(regs) == 0:
@@ -128,7 +225,7 @@ def construct_X_reg(K, M, sample_ids, sample_conditions, sample_graphs, lambda_X
     if sample_conditions is not None:
         regs[1], mix[1] = GroupRegularizer(sample_conditions, weight=lambda_X_condition, K=K), 1
     if sample_graphs is not None:
-        raise NotImplementedError("NetworkRegularizer (sample_graphs) is out of scope of the HIP path (SURVEY section 2)")
+        regs[2], mix[2] = NetworkRegularizer(sample_ids, sample_graphs, weight=lambda_X_graph), 1
     mix = mix / mix.sum() if mix.sum() > 0 else mix      # the reference divides by zero here (NaN weights on x->0 terms)
     return construct_composite_reg(regs, mix)
 
@@ -145,8 +242,10 @@ def construct_Y_reg(K, N, feature_ids, feature_views, feature_sets_dict, feature
     if lambda_Y_l2 is not None:
         regs[0], mix[0] = GroupRegularizer(feature_views, K=K, weight=lambda_Y_l2), 1
     if feature_ids is not None and feature_graphs is not None:
-        if lambda_Y_selective_l1 is not None or lambda_Y_graph is not None:
-            raise NotImplementedError("SelectiveL1Reg / NetworkRegularizer (feature_graphs) are out of scope of the HIP path")
+        if lambda_Y_selective_l1 is not None:
+            regs[1], mix[1] = SelectiveL1Reg(feature_ids, feature_graphs, weight=lambda_Y_selective_l1), 1
+        if lambda_Y_graph is not None:
+            regs[2], mix[2] = NetworkRegularizer(feature_ids, feature_graphs, weight=lambda_Y_graph), 1
     s = mix.sum() or 1
     return construct_composite_reg(regs, mix / s)
 
