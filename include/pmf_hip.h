@@ -304,7 +304,9 @@ int pmf_stats(pmf_ctx *ctx, int use_factors, float *col_n, float *col_sum, float
  * optimiser's accumulator (in / out, persists across calls like A_opts); A and ssq_grad are L x K with the factor index
  * contiguous (A[l*K + k]).  On return A = A_best, *best_loss its loss, *epochs_run the updates performed, and
  * beta[:, cr] = (alpha0 - 1) (v0 + A'S) (:292) is written to beta_out (K x N_v column-major, may be NULL) and into the
- * device copy of the Y regularizer's beta when one is attached (pmf_add_yreg_fsard). */
+ * device copy of the Y regularizer's beta when one is attached (pmf_add_yreg_fsard).
+ * Refused before anything is launched: an empty or out-of-range column range, L < 1, L * K > 16384, max_epochs < 0 and
+ * term_iter < 1 (the reference's loop makes its first update before it looks at the counter). */
 int pmf_fsard_update_A(pmf_ctx *ctx, int64_t col_start1, int64_t col_stop1, int L, const float *S, const float *alpha,
                        const float *lambda, float alpha0, float v0, float lr, float *ssq_grad, float *A, int max_epochs,
                        int term_iter, double atol, double *best_loss, int *epochs_run, float *beta_out);

@@ -154,6 +154,7 @@ struct pmf_ctx {
   float *ard_alpha = nullptr, *ard_beta = nullptr;
   float ard_scale = 0.f;
   bool has_ard = false;
+  bool ard_is_fsard = false;       // the attached term came from pmf_add_yreg_fsard (the only kind pmf_fsard_update_A writes beta into)
   // optimizer
   int opt_kind = PMF_OPT_ADAGRAD;
   float lr = 1.f, eps = 1e-8f, b1 = 0.9f, b2 = 0.999f;

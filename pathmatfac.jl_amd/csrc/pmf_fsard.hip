@@ -11,7 +11,7 @@
 //   k_fsard_step  : (one workgroup) fixed-order sum of the partials, loss bookkeeping exactly as update_A_inner!
 //                   (best loss, A_best, termination counter), then the ISTA update of A unless the loop has ended.
 // Y stays where the fit left it (the context's device copy); beta = beta0 (v0 + A'S) is written straight into the
-// Y regularizer's device array (featureset_ard.jl:292) as well as returned.
+// device array of an attached FeatureSetARD term (featureset_ard.jl:292; never into a plain ARD term's) as well as returned.
 // ------------------------------------------------------------------------------------------------
 struct FsardArgs {
   const float *Y;          // context Y, Kp x N, column j at Y + j*Kp
@@ -23,7 +23,7 @@ struct FsardArgs {
   double *lpart;           // [n_wg] partial data losses
   double *state;           // [0] best loss, [1] loss of the last evaluated A, [4] calibration constant (unused)
   int32_t *istate;         // [0] done, [1] term_count, [2] evaluations so far, [3] max_epochs, [4] term_iter
-  float *beta_dev;         // ard_beta + c0*Kp (may be null)
+  float *beta_dev;         // the FeatureSetARD term's ard_beta + c0*Kp, or a temporary (may be null)
   int64_t c0, Nv;
   int32_t L, K, Kp, CW, n_wg;
   float alpha0, v0, lr;
@@ -187,6 +187,9 @@ extern "C" int pmf_fsard_update_A(pmf_ctx *c, int64_t col_start1, int64_t col_st
   if (c->K == 0) return pmf_fail("factors not set");
   if (col_start1 < 1 || col_stop1 > c->N || col_start1 > col_stop1) return pmf_fail("bad column range %lld:%lld", (long long)col_start1, (long long)col_stop1);
   if (L <= 0 || !S || !alpha || !lambda || !ssq_grad || !A) return pmf_fail("null / empty argument");
+  // the reference's loop makes its first update before it looks at term_iter, this one would end at "Iteration 0": a
+  // count below 1 is refused, like a negative number of epochs
+  if (max_epochs < 0 || term_iter < 1) return pmf_fail("max_epochs must be >= 0 and term_iter >= 1 (got %d, %d)", max_epochs, term_iter);
   const int K = c->K;
   const int64_t Nv = col_stop1 - col_start1 + 1, n = (int64_t)L * K;
   if (n > 64 * 256) return pmf_fail("L x K = %lld exceeds the ISTA kernel's capacity (16384)", (long long)n);
@@ -221,7 +224,7 @@ extern "C" int pmf_fsard_update_A(pmf_ctx *c, int64_t col_start1, int64_t col_st
     FsardArgs a;
     memset(&a, 0, sizeof(a));
     a.Y = c->P[1].p; a.S = dS; a.alpha = dal; a.lambda = dlam; a.A = dA; a.A_best = dAb; a.ssq = dssq; a.gpart = dgp; a.lpart = dlp;
-    a.state = dst; a.istate = dis; a.beta_dev = (c->has_ard && c->ard_beta) ? c->ard_beta + (col_start1 - 1) * c->Kp : nullptr;
+    a.state = dst; a.istate = dis; a.beta_dev = (c->has_ard && c->ard_is_fsard && c->ard_beta) ? c->ard_beta + (col_start1 - 1) * c->Kp : nullptr;
     a.c0 = col_start1 - 1; a.Nv = Nv; a.L = L; a.K = K; a.Kp = c->Kp; a.CW = CW; a.n_wg = n_wg;
     a.alpha0 = alpha0; a.v0 = v0; a.lr = lr; a.atol = atol;
     const size_t lds = (size_t)(n + (int64_t)K * (CW + 1)) * 4;

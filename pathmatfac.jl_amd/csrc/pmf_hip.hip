@@ -720,6 +720,7 @@ static int set_K(pmf_ctx *c, int K) {
   dev_free(&c->ard_alpha);
   dev_free(&c->ard_beta);
   c->has_ard = false;
+  c->ard_is_fsard = false;
   c->state_init = false;
   return 0;
 }
@@ -1139,6 +1140,7 @@ extern "C" int pmf_clear_yreg(pmf_ctx *c) {
   dev_free(&c->P[1].wl1);
   netreg_free(c, 1);
   c->has_ard = false;
+  c->ard_is_fsard = false;
   return 0;
 }
 extern "C" int pmf_add_yreg_l2(pmf_ctx *c, const float *w, float p) {
@@ -1174,6 +1176,7 @@ extern "C" int pmf_add_yreg_ard(pmf_ctx *c, int n_ranges, const int64_t *s1, con
   dev_free(&ds); dev_free(&de); dev_free(&da); dev_free(&db);
   c->ard_scale = p;
   c->has_ard = true;
+  c->ard_is_fsard = false;
   return 0;
 }
 extern "C" int pmf_add_yreg_fsard(pmf_ctx *c, const float *alpha, const float *beta, float p) {
@@ -1186,6 +1189,7 @@ extern "C" int pmf_add_yreg_fsard(pmf_ctx *c, const float *alpha, const float *b
   PMFCHK(upload_padded(c, c->ard_beta, beta, c->N, 1.f));
   c->ard_scale = p;
   c->has_ard = true;
+  c->ard_is_fsard = true;
   return 0;
 }
 

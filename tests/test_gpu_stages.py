@@ -3,6 +3,7 @@ initialisers and the batch-effect EM built on it, the FeatureSetARD outer loop (
 import numpy as np
 import pytest
 
+import fsard_ref as fr
 from oracle import fsard_oracle as fo
 from problems import make_problem, rel_err, to_context, to_oracle
 from test_gpu_host import reference_fit_setup
@@ -81,6 +82,11 @@ def test_batch_effect_initialisation_recovers_shifts(pkg):
 
 
 def test_update_A_matches_numpy_restatement(pkg):
+    """update_A_ (host driver + pmf_fsard_update_A) on two small views, 200 epochs, against the float64 oracle within the
+    bounds derived in fsard_ref.py (20 x the float32 restatement's discrepancy).  The oracle's trace is all "improved by
+    more than atol": the loss falls monotonically, by at least 4.8e-4 (view 2) per epoch against atol = 1e-5 and a loss of
+    46 (1.0e-5 of it: less than the 1000 x the loss discrepancy that fsard_ref.MARGIN asks of the edge tables, and far more
+    than the device's error on a 60-term loss), so A_best is the last iterate and the termination counter never moves."""
     rng = np.random.default_rng(34)
     K, N, L = 4, 30, 5
     sets = [[list(range(1 + 3 * l, 4 + 3 * l)) for l in range(L)], [list(range(16 + 3 * l, 19 + 3 * l)) for l in range(L)]]
@@ -90,16 +96,22 @@ def test_update_A_matches_numpy_restatement(pkg):
     pkg.update_lambda_(reg, Y)
     reg.lambda_ = tuple((l * 1e-3).astype(np.float32) for l in reg.lambda_)   # weak L1 so that A stays non-trivial
     lam = [l.copy() for l in reg.lambda_]
-    pkg.update_A_(reg, Y, max_epochs=200, term_iter=50, verbosity=0)
+    losses = pkg.update_A_(reg, Y, max_epochs=200, term_iter=50, verbosity=0)
     for v, cr in enumerate(reg.col_ranges):
         A = np.zeros((L, K))
         ssq = np.full((L, K), 1e-8)
-        fo.update_A_inner(A, reg.S[v].astype(np.float64), Y[:, cr.slice0()].astype(np.float64),
-                          reg.alpha[cr.slice0()].astype(np.float64), float(reg.alpha0), float(reg.v0), float(reg.lr),
-                          lam[v].astype(np.float64), ssq, max_epochs=200, term_iter=50)
-        assert rel_err(reg.A[v], A) < 5e-3
+        best, epochs, trace = fo.update_A_inner(A, reg.S[v].astype(np.float64), Y[:, cr.slice0()].astype(np.float64),
+                                                reg.alpha[cr.slice0()].astype(np.float64), float(reg.alpha0), float(reg.v0),
+                                                float(reg.lr), lam[v].astype(np.float64), ssq, max_epochs=200, term_iter=50,
+                                                trace=True)
+        assert epochs == 200 and all(s["branch"] == "w" for s in trace)
+        assert min(s["best"] - s["new"] for s in trace) > 40 * 1e-5                 # no improvement is near atol
         beta = (float(reg.alpha0) - 1) * (float(reg.v0) + A.T @ reg.S[v].astype(np.float64))
-        assert rel_err(reg.beta[:, cr.slice0()], beta) < 5e-3      # featureset_ard.jl:292
+        got = dict(A=reg.A[v], ssq=reg.ssq_grad[v], beta=reg.beta[:, cr.slice0()], best=losses[v])
+        e = fr.errors(got, dict(A=A, ssq=ssq, beta=beta, best=best), np.full((L, K), 1e-8, np.float32))
+        print(f"FSARD_ERR stages_small_view{v} " + " ".join(f"{k}={x:.3e}" for k, x in e.items()))
+        for k, x in e.items():
+            assert x <= fr.TOL[k], (v, k, x)                                         # beta: featureset_ard.jl:292
     assert max(float(A.max()) for A in reg.A) > 0          # a non-trivial assignment matrix was compared
 
 
@@ -124,7 +136,8 @@ def test_full_fit_orchestration_featureset_ard(pkg):
 def test_update_A_kernel_on_a_wide_view_matches_numpy_restatement(pkg, ctx):
     """pmf_fsard_update_A at a realistic shape (40 feature sets x K = 64 over a 3000-column view inside a 5000-column
     model: several column slices per workgroup, sparse S), the ISTA loop entirely on the device, against
-    oracle/fsard_oracle.py in float64: A_best, the optimiser's accumulator, beta and the best loss."""
+    oracle/fsard_oracle.py in float64: A_best, the optimiser's accumulator entry by entry, beta, the best loss and
+    epochs_run, within the bounds derived in fsard_ref.py (20 x the float32 restatement's discrepancy)."""
     rng = np.random.default_rng(35)
     K, N, L, c0, c1 = 64, 5000, 40, 1001, 4000
     Nv = c1 - c0 + 1
@@ -146,13 +159,21 @@ def test_update_A_kernel_on_a_wide_view_matches_numpy_restatement(pkg, ctx):
     A, beta, best, epochs = ctx.fsard_update_A(c0, c1, S, alpha, lam, alpha0, v0, lr, ssq, max_epochs=150, term_iter=30, atol=1e-5)
     Ao = np.zeros((L, K))
     ssqo = np.full((L, K), 1e-8)
-    best_o = fo.update_A_inner(Ao, S.astype(np.float64), Y[:, c0 - 1:c1].astype(np.float64), alpha.astype(np.float64), alpha0, v0,
-                               lr, lam.astype(np.float64), ssqo, max_epochs=150, term_iter=30, atol=1e-5)
+    best_o, epochs_o, trace = fo.update_A_inner(Ao, S.astype(np.float64), Y[:, c0 - 1:c1].astype(np.float64),
+                                                alpha.astype(np.float64), alpha0, v0, lr, lam.astype(np.float64), ssqo,
+                                                max_epochs=150, term_iter=30, atol=1e-5, trace=True)
+    # the oracle's loss falls at every epoch, by at least 0.24 against atol = 1e-5: every epoch is "improved by more than
+    # atol", A_best is the last iterate and the counter never moves.  (0.24 is 9e-7 of the loss, below fsard_ref.MARGIN:
+    # a device loss off by that much would only matter at the last epoch, where it would pick the iterate before.)
+    assert all(s["branch"] == "w" for s in trace) and min(s["best"] - s["new"] for s in trace) > 0.2
     assert float(Ao.max()) > 0.05 and epochs >= 30
-    assert abs(best - best_o) <= 2e-5 * abs(best_o), (best, best_o)
-    assert rel_err(A, Ao) <= 5e-3, rel_err(A, Ao)
-    assert rel_err(ssq, ssqo) <= 5e-3
-    assert rel_err(beta, (alpha0 - 1) * (v0 + Ao.T @ S.astype(np.float64))) <= 5e-3
+    got = dict(A=A, ssq=ssq, beta=beta, best=best)
+    want = dict(A=Ao, ssq=ssqo, beta=(alpha0 - 1) * (v0 + Ao.T @ S.astype(np.float64)), best=best_o)
+    e = fr.errors(got, want, np.full((L, K), 1e-8, np.float32))
+    print("FSARD_ERR stages_wide " + " ".join(f"{k}={x:.3e}" for k, x in e.items()) + f" epochs={epochs}/{epochs_o}")
+    assert epochs == epochs_o == 150
+    for k, x in e.items():
+        assert x <= fr.TOL[k], (k, x)
     # ... and the regularizer's device beta took the view's columns (the next epoch's k_reg_step reads it): one
     # Y-regularizer evaluation must equal the closed form with the new beta inside the view and the old one outside
     ctx.set_optimizer("adagrad", lr=1e-6)
