@@ -179,6 +179,8 @@ def _add_term(ctx, which, t):
         ctx.add_yreg_ard(list(zip(t["start1"], t["stop1"])), t["a"], t["b"], t.get("p", 1.0))
     elif t["kind"] == "fsard":
         ctx.add_yreg_fsard(t["alpha"], t["beta"], t.get("p", 1.0))
+    elif t["kind"] == "l1":
+        ctx.add_reg_l1(which, t["w"], t.get("mask"), t.get("p", 1.0))
     else:
         raise ValueError(t["kind"])
 
