@@ -33,6 +33,12 @@
 //   VALU rate and does NOT co-execute with VALU instructions -- every VALU instruction issued by either wave of a
 //   SIMD costs ~3.5 cycles of matrix time (LDS reads are free, ds_write_b128 ~13, global_load_dwordx4 ~18).  The
 //   design therefore minimises the NUMBER of VALU / LDS-store / VMEM instructions per tile, not their placement.
+//
+// XW (KB = 2, NW = 8, RBW = 1, both gradients) splits GEMM3 over the waves by OUTPUT block instead of by rows: the waves
+// publish their G tiles (by tile parity, in the space of the slabs), and after the tile's single barrier wave w contracts
+// one 16 k x 16 j block of gY over all 256 rows of the panel with v_mfma_f32_16x16x4_f32 (A = the X panels, B = the G
+// tiles, both b32 LDS reads), scales it by sigma_j and adds it straight to the private gY slab in HBM.  No per-wave
+// slabs, no 8-way reduction between the forward's MFMAs and no second barrier (DESIGN.md section 4.1).
 
 // RBW = 32-row blocks per wave.  RBW = 2 amortises everything that is per (wave, tile) but not per row -- the slab
 // write, the cross-wave reduction, the Y staging, the barriers -- over twice the MFMA work; it is used where that
@@ -65,7 +71,7 @@ struct FusedCfg {
 // steady-state loop is branch-free apart from the loop itself, which lets hipcc emit exact counted s_waitcnt vmcnt(N)
 // instead of draining the queue at every join (the run-time variant measured 2x slower on grad(Y)-only epochs).
 // BMODE: 0 = no batch layers, 1 = batch tables staged through LDS (<= 15 batches per view), 2 = global gathers
-template <int KB, int NW, int RBW, int BMODE, bool MIXED, int GM, bool DB>
+template <int KB, int NW, int RBW, int BMODE, bool MIXED, int GM, bool DB, bool XW = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fused_kernel(const FusedArgs a) {
   using Cfg = FusedCfg<KB, NW, RBW>;
   constexpr bool FULL = GM != 3;   // no run-time flags
@@ -82,6 +88,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
   constexpr int YV = (BN * Kp / 4 + NT - 1) / NT;  // float4 per thread per Y tile
   constexpr int RV4 = (BN * Kp / 4 + NT - 1) / NT; // gY float4 per thread in the slab reduction
   constexpr int NBT = (BN * 16 + NT - 1) / NT;     // float2 of the dense batch table per thread and tile
+  static_assert(!XW || (KB == 2 && NW == 8 && RBW == 1 && GM == 0 && NYB == 2 && RV4 == 1 && 2 * NW * 1024 <= NW * SLAB),
+                "cross-wave GEMM3: 8 waves x one row block, Kp = 64, both gradients");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float *Ys = reinterpret_cast<float *>(smem);        // [NYB][BN*KpS]      sigma_j * Y[k,j]
@@ -117,7 +125,65 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     // the first G^T tile aliases the LAST k-block of the slab (which is written last); the others have their own space
     T[rb] = rb == 0 ? Sw + (KB - 1) * 1024 : Tt + (w * (RBW - 1) + rb - 1) * 1024;
   }
+  // (XW) The G tiles live in the slab space as [tile parity][wave][1024].  Wave w owns the block (16 k from 16 (w >> 1),
+  // 16 j from 16 (w & 1)) of the tile's gY; lane (g = lane >> 4, c = lane & 15) supplies, at step s of row block p, row
+  // i = 4 g + (s >> 1) + 16 (s & 1) of the block to both operands (A[k = c][i] from the X panel, B[i][j = c] from the G
+  // tile: the two 16-lane groups of a 32-lane half then sit on opposite halves of the 32 banks in both reads) and ends
+  // with k = xw_k .. xw_k + 3 of column xw_j in its four accumulator registers: one 16-B element of the slab.
+  const int xw_j = 16 * (w & 1) + (lane & 15), xw_k = 16 * (w >> 1) + 4 * (lane >> 4);
+  const int xw_e = xw_j * Kp + xw_k;                           // this lane's float4 of the [32 j][Kp] gY tile
+  const int xw_x = 4 * (lane >> 4) * KpS + 16 * (w >> 1) + (lane & 15);
+  int xw_g[4];
+  // the four X read bases as LDS byte addresses the compiler cannot re-derive inside the tile loop (it would, one VALU
+  // instruction per base and tile): every X read of GEMM3 is base + a compile-time offset
+  typedef const __attribute__((address_space(3))) float *lds_cptr;
+  unsigned xw_xa[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int i = 4 * (lane >> 4) + u;
+    xw_g[u] = i * 32 + 4 * ((xw_j >> 2) ^ (i & 7)) + (xw_j & 3);
+    xw_xa[u] = (unsigned)(uintptr_t)(lds_cptr)(Xs + xw_x + u * KpS);
+    if (XW) asm volatile("" : "+v"(xw_xa[u]));
+  }
 
+  // (HOIST: the KB = 2 instances) Tile-invariant addressing.  The lane-dependent part of the Y, column-parameter and
+  // old-slab load addresses is the same for every full tile and differs only in the matrix's last, ragged column tile
+  // (the clamps that keep dead columns' loads in bounds).  Both sets are byte offsets computed once per launch and
+  // pinned in registers; a tile selects one by a wave-uniform condition and adds it to a scalar base, so that a load
+  // costs one VALU instruction instead of the clamp, the shifts and a 64-bit add.
+  // (Not where the eight registers would only add to an instance's spills: the run-time-flag builds and the per-wave-slab
+  // builds with batch layers, which already exceed the 256-register budget.)
+  constexpr bool HOIST = KB == 2 && NW == 8 && RBW == 1 && GM != 3 && (XW || GM != 0 || BMODE == 0);
+  unsigned ho_y[2][YV], ho_s[2][YV], ho_c[2], ho_g[2][RV4];
+  if (HOIST) {
+#pragma unroll
+    for (int z = 0; z < 2; ++z) {
+      const int ncol = z == 0 || N % BN == 0 ? BN : (int)(N % BN);   // z = 1: the live columns of the ragged tile
+#pragma unroll
+      for (int q = 0; q < YV; ++q) {
+        int e4 = tid + NT * q;
+        if (e4 > BN * Kp / 4 - 1) e4 = BN * Kp / 4 - 1;
+        int jl = (e4 * 4) / Kp;
+        if (jl >= ncol) { jl = ncol - 1; e4 = jl * (Kp / 4); }
+        ho_y[z][q] = 16u * e4;
+        ho_s[z][q] = 16u * jl;
+        asm volatile("" : "+v"(ho_y[z][q]), "+v"(ho_s[z][q]));
+      }
+      ho_c[z] = 16u * (tid < ncol ? tid : ncol - 1);
+      asm volatile("" : "+v"(ho_c[z]));
+#pragma unroll
+      for (int q = 0; q < RV4; ++q) {
+        int e = xw_e;
+        if (!XW) {
+          const int f = tid + NT * q, ff = f < BN * Kp / 4 ? f : 0;   // (slab_map below)
+          e = ((ff % (BN * 8)) / 8) * Kp + 32 * (ff / (BN * 8)) + 4 * (ff % 8);
+        }
+        ho_g[z][q] = 4u * (e < ncol * Kp ? e : e % Kp);
+        asm volatile("" : "+v"(ho_g[z][q]));
+      }
+    }
+  }
+  auto ho_at = [](const void *base, unsigned off) { return reinterpret_cast<const char *>(base) + off; };
 #ifdef PMF_STAMPS
   unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long st_prev = __builtin_amdgcn_s_memtime();
@@ -198,6 +264,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       const float *yb = a.Y + jt * Kp;       // the BN x Kp tile is contiguous in Y
       const float4 *cb = a.colp + jt;
       const int64_t rem = N - jt;
+      if (HOIST) {
+        const bool rag = rem < BN;
+        yv[q] = *reinterpret_cast<const float4 *>(ho_at(yb, rag ? ho_y[1][q] : ho_y[0][q]));
+        sgv[q] = *reinterpret_cast<const float *>(ho_at(cb, rag ? ho_s[1][q] : ho_s[0][q]));
+        return;
+      }
       const int ncol = rem > BN ? BN : (int)rem;  // live columns of this tile (>= 1)
       int e4 = tid + NT * q;
       if (e4 > BN * Kp / 4 - 1) e4 = BN * Kp / 4 - 1;
@@ -209,6 +281,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     auto stage_load_c = [&](int64_t jt, float4 &cv) {
       const float4 *cb = a.colp + jt;
       const int64_t rem = N - jt;
+      if (HOIST) {
+        cv = *reinterpret_cast<const float4 *>(ho_at(cb, rem < BN ? ho_c[1] : ho_c[0]));
+        return;
+      }
       const int ncol = rem > BN ? BN : (int)rem;
       cv = cb[tid < ncol ? tid : ncol - 1];
     };
@@ -281,9 +357,14 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     auto slab_prefetch_one = [&](int64_t jt, int q) {
       const float *sb = myslab + jt * Kp;
       const int64_t rem = N - jt;
+      if (HOIST) {
+        gold[q] = pmf_load_stream(reinterpret_cast<const float4 *>(ho_at(sb, rem < BN ? ho_g[1][q] : ho_g[0][q])));
+        return;
+      }
       const int nel = (rem > BN ? BN : (int)rem) * Kp;   // live elements of this gY tile (>= Kp)
       int so, e;
-      slab_map(q, so, e);
+      if (XW) e = xw_e;
+      else slab_map(q, so, e);
       gold[q] = pmf_load_stream(reinterpret_cast<const float4 *>(sb + (e < nel ? e : (e % Kp))));
     };
     // forward: acc[j,i] = mu_j + sum_k sigma_j Y[k,j] X[k,i]   (A = Y tile, B = X panel, both b128 LDS reads; the RBW
@@ -420,6 +501,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     //   -- barrier B1: slabs complete, Y(t+1) visible --
     //   reduce slabs(t) -> private gY slab (plain RMW) | forward(t+1)
     //   -- barrier B2: slabs free --
+    // XW:  epilogue(t) -> G tile [t & 1] | issue loads of tile t+1 | GEMM2(t) | publish Y(t+1)
+    //   -- the tile's barrier: the eight G tiles complete, Y(t+1) visible --
+    //   cross-wave GEMM3(t) -> private gY slab (plain RMW) | forward(t+1)
     for (int t = 0; t < ntiles; ++t) {
       const int par = t & 1;
       const int cur = NYB == 2 ? par : 0, nxt = NYB == 2 ? (par ^ 1) : 0;
@@ -433,6 +517,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       int btv[NBT];
       float sgnext[YV];
       PMF_STAMP(0);   // (loop overhead / previous B2 exit)
+      // (XW) sigma of this lane's gY column, read BEFORE the tile's barrier: past it a faster wave may already be
+      // staging tile t+2's column parameters into this parity
+      const float xw_sg = XW ? Csg[par * BN + xw_j] : 0.f;
 
       // ---- epilogue: (batch layers,) masked loss, dloss/dZ in place (acc becomes G).  G is also written, transposed,
       //      to the wave-private tile T, 16 B (four registers) at a time: element (i, j) lives at
@@ -589,7 +676,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
         if (want_gy) {
 #pragma unroll
           for (int c4 = 0; c4 < 4; ++c4)
-            *reinterpret_cast<float4 *>(T[rb] + l31 * 32 + 4 * ((2 * c4 + h) ^ (l31 & 7))) =
+            *reinterpret_cast<float4 *>((XW ? Sl + (par * NW + w) * 1024 : T[rb]) + l31 * 32 + 4 * ((2 * c4 + h) ^ (l31 & 7))) =
                 make_float4(acc[rb][4 * c4], acc[rb][4 * c4 + 1], acc[rb][4 * c4 + 2], acc[rb][4 * c4 + 3]);
         }
       }
@@ -633,7 +720,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       // ---- GEMM3: gY[j,k] = sum_i G[j,i] * X[k,i] over the wave's 32*RBW rows; results go to this wave's slab
       //      [kb][j][32] with plain stores (the last k block overwrites the first transposed tile, which it has just
       //      consumed: same wave, in-order LDS)
-      if (want_gy) {
+      if (want_gy && !XW) {
         __builtin_amdgcn_wave_barrier();
         // all KB k-blocks advance together: KB independent accumulator chains, and the A operand (one element of a
         // transposed tile) is read once per step instead of once per k block
@@ -686,13 +773,63 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       }
       // ---- forward of tile t+1 with the reduction of tile t's slabs into the private gY slab inside it
       slab_first = pidx == 0 || (pidx == 1 && ti0 + t < t0_first);
-      if (FULL || have_next) forward_reduce(acc, nxt, par ^ 1, want_gy && !(dbg & 1), j0);
-      else if (want_gy && !(dbg & 1)) { f32x16 dummy[RBW]; forward_reduce(dummy, nxt, par ^ 1, true, j0); }
-      PMF_STAMP(8);   // forward + slab reduce
-      // B2: slabs (and the transposed tiles, and the batch table) are free again; a grad(X)-only launch has none of them
-      if ((GM != 1 || bt_lds) && !(dbg & 16)) __syncthreads();
-      PMF_STAMP(9);   // B2 wait
+      if (XW) {
+        // ---- cross-wave GEMM3: gY[xw_j, xw_k..+3] = sum over the panel's 256 rows of X[k, i] G[i, j].  64 MFMAs in two
+        //      independent accumulator chains (32-cycle issue, 40-cycle dependent latency), operands read XW_AHEAD steps
+        //      ahead into a ring of registers; every step is fenced so that the order written is the order issued.
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        constexpr int XW_RING = 8, XW_AHEAD = 6;
+        const float *Gp = Sl + par * (NW * 1024);
+        float xa[XW_RING], xb[XW_RING];
+        // steps q = 8 p + 2 u + hi: rows i and i + 16 of one block are read together -- both strides (16 rows of X or G, one
+        // block of either) are multiples of 256 B, so every read is one half of a ds_read2st64_b32 off four bases per operand
+        auto xw_read = [&](int q) __attribute__((always_inline)) {
+          const int p = q >> 3, u = (q >> 1) & 3;
+#pragma unroll
+          for (int hi = 0; hi < 2; ++hi) {
+            xa[(q + hi) % XW_RING] = *(lds_cptr)(uintptr_t)(xw_xa[u] + 4 * (p * Cfg::XP + 16 * hi * KpS));
+            xb[(q + hi) % XW_RING] = Gp[p * 1024 + xw_g[u] + 512 * hi];
+          }
+        };
+#pragma unroll
+        for (int q = 0; q < XW_AHEAD; q += 2) xw_read(q);
+        f32x4 gy0 = {0.f, 0.f, 0.f, 0.f}, gy1 = {0.f, 0.f, 0.f, 0.f};
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 8 * NW; q += 2) {
+          if (q + XW_AHEAD < 8 * NW) xw_read(q + XW_AHEAD);
+          gy0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q % XW_RING], xb[q % XW_RING], gy0, 0, 0, 0);
+          gy1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[(q + 1) % XW_RING], xb[(q + 1) % XW_RING], gy1, 0, 0, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        // make the (long finished) D loads count as consumed BEFORE the store below is issued: otherwise the next
+        // epilogue's wait for them becomes vmcnt(0) and also waits for this store
+        dcur[0].touch();
+        const int64_t rem = N - j0;
+        const int nel = (rem > BN ? BN : (int)rem) * Kp;
+        float4 v = make_float4((gy0[0] + gy1[0]) * xw_sg, (gy0[1] + gy1[1]) * xw_sg, (gy0[2] + gy1[2]) * xw_sg, (gy0[3] + gy1[3]) * xw_sg);
+        if (!slab_first) { v.x += gold[0].x; v.y += gold[0].y; v.z += gold[0].z; v.w += gold[0].w; }
+        if (xw_e < nel) pmf_store_stream(reinterpret_cast<float4 *>(myslab + j0 * Kp + xw_e), v);
+        PMF_STAMP(4);   // GEMM3 + gY store
+        // forward of tile t+1 (unconditional, as everything in this loop: a piece's last tile repeats its own, and a
+        // branch would cost the sixteen register copies of a conditional acc per tile).  G(t+2) and Y(t+2) overwrite
+        // G(t) and Y(t) only after the barrier of tile t+1, which every wave reaches after this GEMM3(t) and its
+        // GEMM2(t+1); the LDS batch table has one buffer and keeps the second barrier
+        forward_reduce(acc, nxt, par ^ 1, false, 0);
+        PMF_STAMP(8);   // forward
+        if (bt_lds) __syncthreads();
+        PMF_STAMP(9);
+      } else {
+        if (FULL || have_next) forward_reduce(acc, nxt, par ^ 1, want_gy && !(dbg & 1), j0);
+        else if (want_gy && !(dbg & 1)) { f32x16 dummy[RBW]; forward_reduce(dummy, nxt, par ^ 1, true, j0); }
+        PMF_STAMP(8);   // forward + slab reduce
+        // B2: slabs (and the transposed tiles, and the batch table) are free again; a grad(X)-only launch has none of them
+        if ((GM != 1 || bt_lds) && !(dbg & 16)) __syncthreads();
+        PMF_STAMP(9);   // B2 wait
+      }
     }
+    // (XW) the next piece's prologue overwrites this wave's X panel, which the other waves read in the last GEMM3
+    if (XW && !bt_lds) __syncthreads();
 
     PMF_STAMP(10);
     // ---- flush gX (lane = factor index k, register = row): plain stores of the piece's whole BM x Kp partial to its own

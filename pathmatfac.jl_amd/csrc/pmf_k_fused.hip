@@ -24,6 +24,16 @@ static int launch_fused_t(PmfDynLds *cache, hipStream_t stream, const FusedArgs 
   else if (gm == 0) kern = mixed ? pmf_fused_kernel<KB, NW, RBW, 2, true, 0, PMF_DB != 0> : pmf_fused_kernel<KB, NW, RBW, 2, false, 0, PMF_DB != 0>;
   else kern = mixed ? pmf_fused_kernel<KB, NW, RBW, 2, true, 3, PMF_DB != 0> : pmf_fused_kernel<KB, NW, RBW, 2, false, 3, PMF_DB != 0>;
 #undef PMF_PICK_G
+  // cross-wave GEMM3 (pmf_fused.hip.inc, XW): this geometry with both gradients, whatever the epilogue.  PMF_XGEMM3=0 (read at
+  // every pass, like PMF_SB8) keeps the per-wave slabs: the A/B inside one library, bisecting, tests/test_gpu_exact_xwave.py.
+  if constexpr (KB == 2 && NW == 8 && RBW == 1) {
+    const char *xe = getenv("PMF_XGEMM3");
+    if (gm == 0 && !(xe && atoi(xe) == 0)) {
+#define PMF_PICK_XW(BM) (mixed ? pmf_fused_kernel<KB, NW, RBW, BM, true, 0, PMF_DB != 0, true> : pmf_fused_kernel<KB, NW, RBW, BM, false, 0, PMF_DB != 0, true>)
+      kern = bmode == 0 ? PMF_PICK_XW(0) : (bmode == 1 ? PMF_PICK_XW(1) : PMF_PICK_XW(2));
+#undef PMF_PICK_XW
+    }
+  }
   PMFCHK(pmf_ensure_dyn_lds(cache, (const void *)kern, lds));
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), lds, stream, a);
   HIPCHK(hipGetLastError());
