@@ -284,6 +284,40 @@ int pmf_get_grad(pmf_ctx *ctx, int which, int view, float *out);
 /* MF.forward(matfac) (src/simulate_params.jl:247): Z = layers(X'Y) for all local rows, M x N column-major */
 int pmf_forward(pmf_ctx *ctx, float *Z_host);
 
+/* impute(model; include_batch_effects=false) (src/impute.jl:37-56) and the per-noise inverse links it ends with
+ * (src/impute.jl:3-13, 27-35): the model's predictions from the context's CURRENT X, Y, column parameters, batch views and
+ * noise ranges.  Per entry, with a = sum_k X[k,i] Y[k,j]:
+ *     z = a sigma_j + mu_j                                       (flags = 0: the reference's default)
+ *     z = a sigma_j delta_v[b,j] + mu_j + theta_v[b,j]           (PMF_IMPUTE_BATCH: layers 2 and 4 as everywhere else in
+ *                                                                 this library; a row in no batch has delta = 1, theta = 0)
+ *     normal -> z ; bernoulli -> 1 / (1 + e^-z) ; poisson -> e^z  (PMF_IMPUTE_LINK: z itself for every column)
+ * PMF_IMPUTE_KEEP_OBSERVED returns the finite entries of the data matrix as stored on the device (bf16-rounded under
+ * PMF_STORE_BF16) and predicts only the missing ones.
+ *   pmf_impute          : local rows row_start1..row_stop1 (1-based, inclusive) x all N columns into a HOST matrix, column-major
+ *                         with leading dimension ld >= rows.  Computed in row chunks through a staging buffer of at most
+ *                         256 MiB that the context owns (PMF_IMPUTE_CHUNK_ROWS=n, read at every call, overrides the chunk
+ *                         height); elements of out_host between the rows of a column (ld > rows) are not written.
+ *   pmf_impute_device   : the same into DEVICE memory, one launch, no staging.
+ *   pmf_impute_entries  : the predictions at n listed entries (rows1[e], cols1[e], 1-based; duplicates are legal): held-out
+ *                         scoring without an M x N temporary.  n = 0 succeeds and does nothing.
+ * The arithmetic is exact f32 (v_mfma_f32_32x32x2_f32 / fmaf) whatever pmf_set_precision says.  An entry's value does not
+ * depend on the row range, the chunking, ld, or what the context ran before.  The calls change nothing a later pmf_fit
+ * reads: no optimizer state, no gradient, no parameter.  LOCAL ROWS ONLY: no communicator traffic; the host of a sharded
+ * fit calls them on every rank for that rank's rows.
+ * A data matrix must have been set (it fixes M and N); its values are read only for PMF_IMPUTE_KEEP_OBSERVED.
+ * Refused before anything is launched (the context stays usable): a null output, unknown flag bits, an empty or
+ * out-of-range row range, ld below the row count, factors not set, PMF_IMPUTE_KEEP_OBSERVED without data or passed to
+ * pmf_impute_entries, an entry outside 1..M x 1..N.
+ *   pmf_debug_impute_offset : the 64-bit element offset of (0-based row of the range, 0-based column) in an output of
+ *                         leading dimension ld, by the function the kernels use (tests). */
+#define PMF_IMPUTE_BATCH 1          /* apply layers 2 and 4 (batch scale / shift): include_batch_effects=true */
+#define PMF_IMPUTE_LINK 2           /* return z itself, no inverse link */
+#define PMF_IMPUTE_KEEP_OBSERVED 4  /* entries of D that are finite are returned as stored; only missing ones are predicted */
+int pmf_impute(pmf_ctx *ctx, int flags, int64_t row_start1, int64_t row_stop1, float *out_host, int64_t ld);
+int pmf_impute_device(pmf_ctx *ctx, int flags, int64_t row_start1, int64_t row_stop1, float *out_device, int64_t ld);
+int pmf_impute_entries(pmf_ctx *ctx, int flags, int64_t n, const int64_t *rows1, const int64_t *cols1, float *out_host);
+int pmf_debug_impute_offset(int64_t row, int64_t col, int64_t ld, int64_t *offset);
+
 /* Masked column statistics for the closed-form initialisers that sit between the GD stages (local rows only; a
  * multi-GPU host sums them across ranks).  All outputs are optional (NULL = not wanted).
  *   col_n[N]        MF.column_nonnan                         (src/fit.jl:140, 447; src/regularizers.jl:765)

@@ -17,6 +17,7 @@ NOISE = {"normal": 0, "bernoulli": 1, "poisson": 2}
 OPT = {"adagrad": 0, "adam": 1}
 STORE = {"f32": 0, "bf16": 1}
 TERM = {0: "max_epochs", 1: "loss_increase", 2: "abs_tol", 3: "rel_tol", 4: "nonfinite"}
+IMPUTE_BATCH, IMPUTE_LINK, IMPUTE_KEEP_OBSERVED = 1, 2, 4
 PARAM = {"X": 0, "Y": 1, "logsigma": 2, "mu": 3, "logdelta": 4, "theta": 5}
 
 
@@ -68,6 +69,7 @@ EXPORTS = [
     "pmf_comm_get_unique_id", "pmf_comm_init", "pmf_comm_init_host", "pmf_comm_destroy", "pmf_comm_set_chunks",
     "pmf_comm_info", "pmf_comm_allreduce", "pmf_get_opt_state", "pmf_fsard_update_A", "pmf_debug_last_path", "pmf_debug_last_kernel",
     "pmf_add_xreg_network", "pmf_add_yreg_network", "pmf_get_reg_network_state", "pmf_add_xreg_l1", "pmf_add_yreg_l1",
+    "pmf_impute", "pmf_impute_device", "pmf_impute_entries", "pmf_debug_impute_offset",
 ]
 
 COMM_ID_BYTES = 128
@@ -469,6 +471,47 @@ class Context:
         Z = np.zeros((self.M, self.N), np.float32, order="F")
         self._chk(self.lib.pmf_forward(self._h, _fp(Z)))
         return Z
+
+    # ---- predictions
+    @staticmethod
+    def impute_flags(include_batch_effects=False, link=False, keep_observed=False):
+        return ((IMPUTE_BATCH if include_batch_effects else 0) | (IMPUTE_LINK if link else 0)
+                | (IMPUTE_KEEP_OBSERVED if keep_observed else 0))
+
+    def impute(self, flags=0, row_start1=1, row_stop1=None, out=None, out_row=0):
+        """pmf_impute: the predictions of rows row_start1..row_stop1 (1-based, inclusive; default all) x all columns.
+        `out` (optional): a float32 Fortran-ordered array with N columns; the block is written to its rows out_row ..
+        out_row + rows - 1 with its row count as the leading dimension, and nothing else in it is touched.
+        Returns the rows x N block."""
+        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
+        rows = max(row_stop1 - int(row_start1) + 1, 0)
+        if out is None:
+            out, out_row = np.zeros((rows, self.N), np.float32, order="F"), 0
+        elif out.dtype != np.float32 or out.ndim != 2 or not out.flags.f_contiguous or out.shape[1] != self.N:
+            raise PMFError("impute: out must be a Fortran-ordered float32 array with N columns")
+        if out_row < 0 or out_row + rows > out.shape[0]:
+            raise PMFError("impute: the block does not fit in out")
+        ptr = C.c_void_p(out.ctypes.data + 4 * int(out_row)) if out.size else None
+        self._chk(self.lib.pmf_impute(self._h, int(flags), C.c_int64(row_start1), C.c_int64(row_stop1), ptr,
+                                      C.c_int64(out.shape[0])))
+        return out[out_row:out_row + rows]
+
+    def impute_device(self, ptr, flags=0, row_start1=1, row_stop1=None, ld=None):
+        """pmf_impute_device: the same into device memory at address `ptr` (e.g. a torch tensor's data_ptr())."""
+        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
+        ld = row_stop1 - int(row_start1) + 1 if ld is None else int(ld)
+        self._chk(self.lib.pmf_impute_device(self._h, int(flags), C.c_int64(row_start1), C.c_int64(row_stop1),
+                                             C.c_void_p(ptr), C.c_int64(ld)))
+
+    def impute_entries(self, rows1, cols1, flags=0):
+        """pmf_impute_entries: the predictions at the listed (row, column) entries, 1-based."""
+        r = np.ascontiguousarray(rows1, dtype=np.int64).ravel()
+        c = np.ascontiguousarray(cols1, dtype=np.int64).ravel()
+        if r.shape != c.shape:
+            raise PMFError("impute_entries: rows and columns must have the same length")
+        out = np.zeros(max(r.size, 1), np.float32)
+        self._chk(self.lib.pmf_impute_entries(self._h, int(flags), C.c_int64(r.size), _i64p(r), _i64p(c), _fp(out)))
+        return out[:r.size]
 
     def stats(self, use_factors=False):
         """Masked column and (batch, column) statistics (pmf_stats).  Returns a dict of float32 arrays."""

@@ -5,6 +5,7 @@
 //   pmf_k_fused.hip    pmf_fused_kernel (pmf_fused.hip.inc), once per (K blocks, row blocks per wave)
 //   pmf_k_sb.hip       pmf_fused_sb_kernel + k_sb_split (pmf_fused_sb.hip.inc), once per K-block count
 //   pmf_k_layers.hip   pmf_layer_kernel + k_layer_map (pmf_layers.hip.inc)
+//   pmf_k_impute.hip   pmf_impute_kernel + k_impute_entries (pmf_impute.hip.inc)
 #ifndef PMF_COMMON_H
 #define PMF_COMMON_H
 #include <hip/hip_runtime.h>
@@ -404,6 +405,39 @@ struct LayerMapArgs {
   int64_t val_off[PMF_MAXV];
 };
 
+// ---- impute (pmf_impute.hip.inc)
+// Element offset of (row r of the requested range, column j), both 0-based, in a column-major output of leading dimension
+// ld.  m N exceeds 2^31 at the headline size: every operand is 64-bit before the product is formed.
+__host__ __device__ __forceinline__ int64_t pmf_impute_off(int64_t r, int64_t j, int64_t ld) { return j * ld + r; }
+
+struct ImputeArgs {
+  const float *X, *Y;
+  const float4 *colp;
+  const int32_t *bor;      // n_bv x M row -> batch (or -1); read with PMF_IMPUTE_BATCH only
+  const float2 *btab;      // {delta, theta}, view v at views[v].tab_off, nb x Nv column-major
+  const ViewDesc *views;   // device array [n_bv]
+  const void *D;           // tile-major f32 or bf16; read with PMF_IMPUTE_KEEP_OBSERVED only
+  int64_t nRB;
+  float *out;              // column-major, rows row0 .. row1 - 1 of the matrix, leading dimension ld
+  int64_t ld;
+  int64_t M, N;
+  int64_t row0, row1;      // 0-based, [row0, row1)
+  int64_t rp0, n_rp;       // the 32 NW-row panels (absolute numbering) that meet the row range
+  int32_t n_bv, n_ct, n_seg, R, flags;
+};
+
+struct ImputeEntriesArgs {
+  const float *X, *Y;
+  const float4 *colp;
+  const int32_t *bor;
+  const float2 *btab;
+  const ViewDesc *views;
+  const int64_t *rows1, *cols1;   // 1-based, validated on the host
+  float *out;
+  int64_t n, M;
+  int32_t Kp, K, flags;
+};
+
 // ---- launchers exported by the kernel files
 // Fused-kernel launchers, one per family, K-block count (exact kernel: and row blocks per wave) and storage type of D, all
 // of one type: the family table in pmf_hip.hip holds them.  The gradient variant follows a.want_gx / a.want_gy.
@@ -423,4 +457,7 @@ int pmf_launch_sb_split_2(hipStream_t stream, const SbSplitArgs &a);
 size_t pmf_layer_pass_lds(int KB, int lnw, int nbs);   // dynamic LDS of the layer pass (<= 160 KiB: eligible)
 int pmf_launch_layer_pass(PmfDynLds *cache, hipStream_t stream, int KB, int lnw, bool mixed, int grid, const LayerPassArgs &a);   // (a.d_bf16 picks the storage variant)
 int pmf_launch_layer_map(hipStream_t stream, const LayerMapArgs &m);
+int pmf_impute_waves(int KB);   // waves per workgroup of pmf_impute_kernel: 8 up to K = 64, 4 above
+int pmf_launch_impute(PmfDynLds *cache, hipStream_t stream, int KB, bool d_bf16, int grid, const ImputeArgs &a);
+int pmf_launch_impute_entries(hipStream_t stream, const ImputeEntriesArgs &a);
 #endif

@@ -196,6 +196,10 @@ struct pmf_ctx {
   // scratch
   void *scratch = nullptr;
   size_t scratch_bytes = 0;
+  // staging buffer of pmf_impute / pmf_impute_entries (at most 256 MiB unless one row of N predictions is larger), grown
+  // lazily; not `scratch`, which those calls leave alone
+  void *impute_stage = nullptr;
+  size_t impute_stage_bytes = 0;
   // largest dynamic-LDS size set so far per kernel ON THIS CONTEXT'S DEVICE (hipFuncSetAttribute is per device: a
   // process-wide cache would leave a second GPU's kernels without the attribute)
   PmfDynLds dyn_lds;

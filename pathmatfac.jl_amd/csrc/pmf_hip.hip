@@ -781,6 +781,7 @@ extern "C" int pmf_destroy(pmf_ctx *c) {
   dev_free(&c->gy_slabs); dev_free(&c->xsb); dev_free(&c->ysb); dev_free(&c->sb8_scale); dev_free(&c->sb8_max); dev_free(&c->loss_partial); dev_free(&c->reg_partial); dev_free(&c->d_loss);
   if (c->h_loss) (void)hipHostFree(c->h_loss);
   if (c->scratch) (void)hipFree(c->scratch);
+  if (c->impute_stage) (void)hipFree(c->impute_stage);
   for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -2338,6 +2339,133 @@ extern "C" int pmf_forward(pmf_ctx *c, float *Z_host) {
   }
   (void)hipFree(Z);
   return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// impute (src/impute.jl): predictions from the current parameters, whole rows or listed entries
+// ------------------------------------------------------------------------------------------------
+#define PMF_IMPUTE_STAGE_MAX ((size_t)256 << 20)   // the bound of pmf_set_data's upload chunks
+
+static int ensure_impute_stage(pmf_ctx *c, size_t bytes) {
+  if (c->impute_stage_bytes >= bytes) return 0;
+  if (c->impute_stage) HIPCHK(hipFree(c->impute_stage));
+  c->impute_stage = nullptr;
+  c->impute_stage_bytes = 0;
+  HIPCHK(hipMalloc(&c->impute_stage, bytes));
+  c->impute_stage_bytes = bytes;
+  return 0;
+}
+
+// what every impute call checks before it touches the device.  The context needs M, N (a data matrix has been set: it is
+// what fixes them), factors and complete batch views; the values of D only for PMF_IMPUTE_KEEP_OBSERVED.
+static int impute_check(pmf_ctx *c, const char *fn, int flags, const void *out, bool entries) {
+  if (!out) return pmf_fail("%s: null output pointer", fn);
+  if (flags & ~(PMF_IMPUTE_BATCH | PMF_IMPUTE_LINK | PMF_IMPUTE_KEEP_OBSERVED)) return pmf_fail("%s: unknown flag bits 0x%x", fn, flags);
+  if (entries && (flags & PMF_IMPUTE_KEEP_OBSERVED)) return pmf_fail("%s: PMF_IMPUTE_KEEP_OBSERVED is not accepted here (the caller holds the observed entries)", fn);
+  if ((flags & PMF_IMPUTE_KEEP_OBSERVED) && !c->D) return pmf_fail("%s: PMF_IMPUTE_KEEP_OBSERVED needs the data matrix (data not set)", fn);
+  if (c->K == 0 || c->M <= 0 || c->N <= 0) return pmf_fail("%s: factors not set", fn);
+  for (int v = 0; v < c->n_bv; ++v)
+    if (c->views[v].nb == 0) return pmf_fail("%s: batch view %d declared but not set", fn, v);
+  return 0;
+}
+
+static int impute_check_range(pmf_ctx *c, const char *fn, int64_t s1, int64_t e1, int64_t ld) {
+  if (s1 < 1 || e1 > c->M || s1 > e1) return pmf_fail("%s: empty or out-of-range row range %lld:%lld (rows 1..%lld)", fn, (long long)s1, (long long)e1, (long long)c->M);
+  if (ld < e1 - s1 + 1) return pmf_fail("%s: ld=%lld is below the row count %lld", fn, (long long)ld, (long long)(e1 - s1 + 1));
+  return 0;
+}
+
+// rows [row0, row1) (0-based) into out_dev (leading dimension ld); prepare() has run
+static int impute_launch(pmf_ctx *c, int flags, int64_t row0, int64_t row1, float *out_dev, int64_t ld) {
+  const int nw = pmf_impute_waves(c->KB);
+  const int64_t BM = 32 * nw;
+  ImputeArgs a;
+  memset(&a, 0, sizeof(a));
+  a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
+  a.D = c->D; a.nRB = c->nRB; a.out = out_dev; a.ld = ld; a.M = c->M; a.N = c->N; a.row0 = row0; a.row1 = row1;
+  a.rp0 = row0 / BM;
+  a.n_rp = (row1 - 1) / BM + 1 - a.rp0;
+  a.n_bv = c->n_bv; a.flags = flags;
+  const int64_t n_ct = (c->N + PMF_BN - 1) / PMF_BN, n_seg = (n_ct + PMF_LS - 1) / PMF_LS;
+  if (n_ct >= (1ll << 31)) return pmf_fail("pmf_impute: N too large");
+  // a unit = (column segment, 1/R of the panels); R as in the layer pass: a few units per CU, consecutive units share a segment
+  const int64_t R = std::max<int64_t>(1, std::min<int64_t>(a.n_rp, (4ll * c->n_cu + n_seg - 1) / n_seg));
+  a.n_ct = (int)n_ct; a.n_seg = (int)n_seg; a.R = (int)R;
+  if (n_seg * R >= (1ll << 31)) return pmf_fail("pmf_impute: too many units");
+  const int grid = (int)std::min<int64_t>(n_seg * R, c->n_cu);
+  return pmf_launch_impute(&c->dyn_lds, c->stream, c->KB, c->store == PMF_STORE_BF16, grid, a);
+}
+
+extern "C" int pmf_impute_device(pmf_ctx *c, int flags, int64_t row_start1, int64_t row_stop1, float *out_device, int64_t ld) {
+  PMFCHK(ctx_bind(c));
+  PMFCHK(impute_check(c, "pmf_impute_device", flags, out_device, false));
+  PMFCHK(impute_check_range(c, "pmf_impute_device", row_start1, row_stop1, ld));
+  PMFCHK(prepare(c));
+  PMFCHK(impute_launch(c, flags, row_start1 - 1, row_stop1, out_device, ld));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int pmf_impute(pmf_ctx *c, int flags, int64_t row_start1, int64_t row_stop1, float *out_host, int64_t ld) {
+  PMFCHK(ctx_bind(c));
+  PMFCHK(impute_check(c, "pmf_impute", flags, out_host, false));
+  PMFCHK(impute_check_range(c, "pmf_impute", row_start1, row_stop1, ld));
+  const int64_t rows = row_stop1 - row_start1 + 1;
+  // chunk height: what 256 MiB hold of N-column rows (whole 32-row blocks when there are that many), at least one row
+  const int64_t cap = std::max<int64_t>(1, (int64_t)(PMF_IMPUTE_STAGE_MAX / sizeof(float)) / c->N);
+  int64_t ch = cap >= 32 ? cap - cap % 32 : cap;
+  if (const char *e = getenv("PMF_IMPUTE_CHUNK_ROWS")) {
+    const long long v = atoll(e);
+    if (v > 0) ch = std::min<int64_t>(v, cap);
+  }
+  ch = std::min(ch, rows);
+  PMFCHK(ensure_impute_stage(c, sizeof(float) * (size_t)(ch * c->N)));
+  PMFCHK(prepare(c));
+  float *stage = (float *)c->impute_stage;
+  for (int64_t r0 = row_start1 - 1; r0 < row_stop1; r0 += ch) {
+    const int64_t nr = std::min(ch, row_stop1 - r0);
+    PMFCHK(impute_launch(c, flags, r0, r0 + nr, stage, nr));
+    HIPCHK(hipMemcpy2DAsync(out_host + (r0 - (row_start1 - 1)), sizeof(float) * (size_t)ld, stage, sizeof(float) * (size_t)nr,
+                            sizeof(float) * (size_t)nr, (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+
+extern "C" int pmf_impute_entries(pmf_ctx *c, int flags, int64_t n, const int64_t *rows1, const int64_t *cols1, float *out_host) {
+  PMFCHK(ctx_bind(c));
+  if (n < 0) return pmf_fail("pmf_impute_entries: n=%lld", (long long)n);
+  if (n == 0) return 0;
+  PMFCHK(impute_check(c, "pmf_impute_entries", flags, out_host, true));
+  if (!rows1 || !cols1) return pmf_fail("pmf_impute_entries: null index pointer");
+  for (int64_t e = 0; e < n; ++e)
+    if (rows1[e] < 1 || rows1[e] > c->M || cols1[e] < 1 || cols1[e] > c->N)
+      return pmf_fail("pmf_impute_entries: entry %lld = (%lld, %lld) is outside 1..%lld x 1..%lld", (long long)e, (long long)rows1[e],
+                      (long long)cols1[e], (long long)c->M, (long long)c->N);
+  const int64_t ch = std::min<int64_t>(n, 1ll << 22);   // 20 bytes of staging per entry
+  PMFCHK(ensure_impute_stage(c, (size_t)ch * (2 * sizeof(int64_t) + sizeof(float))));
+  PMFCHK(prepare(c));
+  int64_t *d_rows = (int64_t *)c->impute_stage, *d_cols = d_rows + ch;
+  float *d_out = (float *)(d_cols + ch);
+  for (int64_t e0 = 0; e0 < n; e0 += ch) {
+    const int64_t ne = std::min(ch, n - e0);
+    HIPCHK(hipMemcpyAsync(d_rows, rows1 + e0, sizeof(int64_t) * (size_t)ne, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_cols, cols1 + e0, sizeof(int64_t) * (size_t)ne, hipMemcpyHostToDevice, c->stream));
+    ImputeEntriesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
+    a.rows1 = d_rows; a.cols1 = d_cols; a.out = d_out; a.n = ne; a.M = c->M; a.Kp = c->Kp; a.K = c->K; a.flags = flags;
+    PMFCHK(pmf_launch_impute_entries(c->stream, a));
+    HIPCHK(hipMemcpyAsync(out_host + e0, d_out, sizeof(float) * (size_t)ne, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+
+extern "C" int pmf_debug_impute_offset(int64_t row, int64_t col, int64_t ld, int64_t *offset) {
+  if (!offset) return pmf_fail("null output");
+  *offset = pmf_impute_off(row, col, ld);
+  return 0;
 }
 
 extern "C" int pmf_synth_data(pmf_ctx *c, uint64_t seed, float noise, float frac_nan) {

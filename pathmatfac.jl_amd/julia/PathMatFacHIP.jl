@@ -291,6 +291,20 @@ function unmarshal!(ctx, mf, update_X, update_Y, update_col_layers)
     end
 end
 
+"""impute(model; include_batch_effects=false) (src/impute.jl:37-56) on the device: pmf_impute over the model's current
+parameters.  `link=true` returns Z itself, `keep_observed=true` returns the observed entries of model.data and predicts
+only the missing ones; `rows` (a UnitRange) bounds the host matrix.  Returns length(rows) x N Float32."""
+function impute(model::PM.PathMatFacModel; include_batch_effects=false, link=false, keep_observed=false,
+                rows::UnitRange=1:size(model.data, 1))
+    ctx = context!(model)
+    marshal!(ctx, model.matfac)
+    flags = Cint((include_batch_effects ? 1 : 0) | (link ? 2 : 0) | (keep_observed ? 4 : 0))
+    out = zeros(Float32, length(rows), size(model.data, 2))
+    GC.@preserve out chk(ccall((:pmf_impute, LIB[]), Cint, (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Cfloat}, Int64),
+                               ctx, flags, rows.start, rows.stop, out, length(rows)))
+    return out
+end
+
 """Point PathMatFac's drop-in boundary at the HIP library."""
 function install!(libpath::AbstractString="libpmf_hip.so")
     LIB[] = libpath
