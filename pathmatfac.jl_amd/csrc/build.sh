@@ -6,4 +6,7 @@ HERE="$(cd "$(dirname "$0")" && pwd)"
 EXTRA="$*"
 if [[ -n "${PMF_KEEP_TEMPS:-}" ]]; then mkdir -p "$PMF_KEEP_TEMPS"; EXTRA="$EXTRA -save-temps=obj"; fi
 make -s -j"${PMF_BUILD_JOBS:-8}" -C "$HERE" EXTRA="$EXTRA" ${PMF_LIB:+LIB="$PMF_LIB"} ${PMF_BUILD_DIR:+B="$PMF_BUILD_DIR"}
-if [[ -n "${PMF_KEEP_TEMPS:-}" ]]; then cp "$HERE"/.build/*.s "$PMF_KEEP_TEMPS"/ 2>/dev/null || true; fi
+if [[ -n "${PMF_KEEP_TEMPS:-}" ]]; then
+  bd="${PMF_BUILD_DIR:-.build}"; [[ "$bd" = /* ]] || bd="$HERE/$bd"   # (make -C: a relative build directory is relative to csrc)
+  cp "$bd"/*.s "$PMF_KEEP_TEMPS"/ || echo "build.sh: no device assembly (.s) found in $bd" >&2
+fi
