@@ -110,6 +110,20 @@ struct FusedArgs {
 __device__ __forceinline__ int pmf_rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 __device__ __forceinline__ bool pmf_finite(float y) { return fabsf(y) <= 3.402823466e38f; }  // false for NaN, +-Inf
 
+// ---- what the model computes for one entry, for the scalar kernels (the fused kernels keep forms of their own)
+// colp[j].w = meta_j = kind | (view + 1) << 2
+__host__ __device__ __forceinline__ int pmf_meta_kind(int meta) { return meta & 3; }
+__host__ __device__ __forceinline__ int pmf_meta_view(int meta) { return (meta >> 2) - 1; }   // -1: the column is in no view
+// (column j, batch b) in a view's nb x Nv column-major table: inside the table (logdelta / theta at val_off[view]), in btab
+__host__ __device__ __forceinline__ int64_t pmf_view_index(const ViewDesc &vd, int64_t j, int b) { return (j - vd.c0) * vd.nb + b; }
+__host__ __device__ __forceinline__ int64_t pmf_btab_index(const ViewDesc &vd, int64_t j, int b) { return vd.tab_off + pmf_view_index(vd, j, b); }
+// batch of row i in view v (-1: the row is in no batch, or the column in no view)
+__device__ __forceinline__ int pmf_row_batch(const int32_t *bor, int64_t M, int v, int64_t i) { return v >= 0 ? bor[(int64_t)v * M + i] : -1; }
+// {delta, theta} of (column j of view vd, batch b); the identity for a row in no batch
+__device__ __forceinline__ float2 pmf_batch_dt(const ViewDesc &vd, const float2 *btab, int64_t j, int b) {
+  return b >= 0 ? btab[pmf_btab_index(vd, j, b)] : make_float2(1.f, 0.f);
+}
+
 // loss and dloss/dz of one entry.  SELF-SPECIFIED noise models (MatFac is un-vendored):
 //   normal 0.5 w (z-y)^2 ; bernoulli w (softplus(z) - y z) ; poisson w (exp(z) - y z)
 __device__ __forceinline__ void pmf_noise(int kind, float z, float y, float w, float &l, float &g) {

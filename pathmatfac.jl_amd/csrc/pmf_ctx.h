@@ -97,7 +97,7 @@ struct NetReg {
   float *u = nullptr;              // [V]
   float *work = nullptr;           // [4 V] t, r, d, BB d of the factors whose v_k exceeds the LDS budget
   float *PT = nullptr;             // [K][n] factor-major copy of the parameter, rebuilt every epoch
-  float *grad = nullptr;           // [Kp * n] p * (AA_k p_k + AB_k u_k), in the parameter's own layout (read by k_reg_step_graph)
+  float *grad = nullptr;           // [Kp * n] p * (AA_k p_k + AB_k u_k), in the parameter's own layout (read by k_reg_step<true>)
   int32_t *iters = nullptr;        // [K] CG iterations of the last solve
   double *uloss = nullptr;         // [K] t'u + 0.5 u'BB u of the last solve
   int rb = 1;                      // row blocks per factor of the gradient kernel (= loss partials per factor)

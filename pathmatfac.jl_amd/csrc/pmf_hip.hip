@@ -107,8 +107,8 @@ __global__ void k_dense_btab(const DenseBtabArgs a) {
   float2 out = make_float2(1.f, 0.f);
   int v = -1;
   if (j < a.N) {
-    v = (a.colmeta[j] >> 2) - 1;
-    if (v >= 0 && b < a.views[v].nb && b < (1 << a.nbs_shift) - 1) out = a.btab[a.views[v].tab_off + (j - a.views[v].c0) * a.views[v].nb + b];
+    v = pmf_meta_view(a.colmeta[j]);
+    if (v >= 0 && b < a.views[v].nb && b < (1 << a.nbs_shift) - 1) out = a.btab[pmf_btab_index(a.views[v], j, b)];
   }
   a.btd[e] = out;
   if (b == 0) a.colview[j] = (uint8_t)(v < 0 ? 255 : v);
@@ -202,8 +202,7 @@ struct StepArgs {
   int use_reg;
   double *reg_partial;  // [REG_SLOTS]
 };
-struct StepArgsGraph {           // k_reg_step_graph: the same, plus the pathway-graph terms (at least one of them set)
-  StepArgs a;
+struct StepArgsGraph : StepArgs {   // k_reg_step<true>: the same, plus the pathway-graph terms (at least one of them set)
   const float *gpre;             // gradient of a term evaluated beforehand (NetworkRegularizer, pmf_netreg.hip; may be null)
   const float *wl1;              // dense L1 weights (L1Regularizer / SelectiveL1Reg; may be null)
 };
@@ -217,7 +216,10 @@ struct StepArgsGraph {           // k_reg_step_graph: the same, plus the pathway
 //   L1        : wl1 |p|, grad wl1 sign(p), sign(0) = 0  (L1Regularizer :71-82, SelectiveL1Reg :130-146)
 //   AdaGrad   : acc += g^2 ; p -= eta g/(sqrt(acc)+eps)   (optimizers.jl:6-13 ; acc starts at eps)
 //   Adam      : Flux.Optimise.Adam
-__global__ __launch_bounds__(256) void k_reg_step(const StepArgs a) {
+// GRAPH: the instance with the pathway-graph terms (network, L1), launched only when one of them is set.  The plain
+// instance neither takes nor tests them: a context without these terms runs the arguments and the code it always ran.
+template <bool GRAPH>
+__global__ __launch_bounds__(256) void k_reg_step(const std::conditional_t<GRAPH, StepArgsGraph, StepArgs> a) {
   __shared__ double sh[4];
   double lacc = 0.0;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -240,56 +242,13 @@ __global__ __launch_bounds__(256) void k_reg_step(const StepArgs a) {
         lacc += (double)(a.ard_scale * (0.5f + al) * logf(b));
         g += a.ard_scale * ((al + 0.5f) * p / (b * be));
       }
-    }
-    if (a.do_step) {
-      if (a.opt_kind == PMF_OPT_ADAGRAD) {
-        const float acc = a.acc[e] + g * g;
-        a.acc[e] = acc;
-        p -= g * (a.lr / (sqrtf(acc) + a.eps));
-      } else {
-        const float m = a.b1 * a.mom[e] + (1.f - a.b1) * g;
-        const float v = a.b2 * a.acc[e] + (1.f - a.b2) * g * g;
-        a.mom[e] = m;
-        a.acc[e] = v;
-        p -= m / a.c1 / (sqrtf(v / a.c2) + a.eps) * a.lr;
-      }
-      a.p[e] = p;
-    }
-  }
-  const double s = block_reduce_sum(lacc, sh);
-  if (threadIdx.x == 0 && a.reg_partial) a.reg_partial[blockIdx.x] = s;
-}
-// The same pass with the pathway-graph terms (launched only when one of them is set).  A kernel of its own on purpose:
-// k_reg_step above keeps its arguments and its code exactly, so a context without these terms runs what it always ran.
-__global__ __launch_bounds__(256) void k_reg_step_graph(const StepArgsGraph ga) {
-  const StepArgs &a = ga.a;
-  __shared__ double sh[4];
-  double lacc = 0.0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < a.n; e += stride) {
-    const int k = (int)(e % a.Kp);
-    if (k >= a.K) continue;
-    float p = a.p[e];
-    float g = a.g[e];
-    if (a.use_reg) {
-      if (a.wq) {
-        const float d = p - (a.cq ? a.cq[e] : 0.f);
-        const float gr = a.wq[e] * d;
-        lacc += 0.5 * (double)(gr * d);
-        g += gr;
-      }
-      if (a.ard_beta) {
-        const int64_t j = e / a.Kp;
-        const float be = a.ard_beta[e], al = a.ard_alpha[j];
-        const float b = 1.f + (0.5f / be) * (p * p);
-        lacc += (double)(a.ard_scale * (0.5f + al) * logf(b));
-        g += a.ard_scale * ((al + 0.5f) * p / (b * be));
-      }
-      if (ga.gpre) g += ga.gpre[e];
-      if (ga.wl1) {
-        const float w = ga.wl1[e];
-        lacc += (double)(w * fabsf(p));
-        g += p > 0.f ? w : p < 0.f ? -w : 0.f;
+      if constexpr (GRAPH) {
+        if (a.gpre) g += a.gpre[e];
+        if (a.wl1) {
+          const float w = a.wl1[e];
+          lacc += (double)(w * fabsf(p));
+          g += p > 0.f ? w : p < 0.f ? -w : 0.f;
+        }
       }
     }
     if (a.do_step) {
@@ -332,32 +291,106 @@ int launch_loss_reduce(pmf_ctx *c, const RegCounts &rc, int mask) {
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Layer-parameter gradient pass (update_col_layers stages S2/S7: init_theta! fit.jl:106-122, fit_joint :987-1000).
-// thread = column, sequential over a chunk of rows; per-(batch, column) sums live in LDS (no contention:
-// a thread only touches its own column).  Pull-backs as coded in the reference:
-//   theta_bar[b,j]    = sum_{i in b} g                      (batch_array.jl:141-143)
-//   mu_bar[j]         = sum_i g                             (layers.jl:83)
-//   logdelta_bar[b,j] = delta[b,j] * sum_{i in b} g * (a*sigma_j)   (batch_array.jl:203-204, 250)
-//   logsigma_bar[j]   = sigma_j * sum_i g * delta           (layers.jl:40-41; Q1: omits the input factor)
-// ------------------------------------------------------------------------------------------------
-struct LayerGradArgs {
+// ---- the column walk k_layer_grad<KB> and k_stats<KB> share.  One wave per workgroup: thread = column (64 consecutive
+// columns), sequential over a chunk of rows.  The column of Y lives in registers (32*KB floats), four rows of X at a time are
+// staged in LDS and read back as broadcast 16-B reads (a single wave needs no barrier: LDS operations of one wave complete
+// in order), per-(batch, column) sums in LDS (no contention: a thread only touches its own column), one plain store per
+// (batch, column) per workgroup at the end (private partials per block row, added in fixed order by k_sum_parts).
+struct ColWalkArgs {
   const void *D;
   int d_bf16;
   const float *X, *Y;
   const float4 *colp;
   const int32_t *bor;
   const float2 *btab;
+  int64_t M, N, nRB;
+  int Kp, K, rows_per_block, max_nb;
+  ViewDesc views[PMF_MAXV];
+  int64_t val_off[PMF_MAXV];
+};
+#define PMF_WALK_RG 4   // rows of X per group
+// dynamic LDS: [RG][Kp] current rows of X | [2][max_nb][64] per-(batch, column) sums
+__host__ __device__ constexpr size_t col_walk_lds(int Kp, int max_nb) { return sizeof(float) * (size_t)(PMF_WALK_RG * Kp + 2 * max_nb * 64); }
+
+template <int KB>
+struct ColWalk {
+  static constexpr int Kp = 32 * KB, RG = PMF_WALK_RG;
+  const ColWalkArgs &a;
+  float *xs, *bacc;
+  int tid;
+  int64_t j, jc, r0, r1;   // column, column clamped to the matrix, row range of this block row
+  bool col_ok;
+  float4 cp;
+  int kind, v;
+  ViewDesc vd;
+  float4 yr[Kp / 4];
+
+  __device__ __forceinline__ ColWalk(const ColWalkArgs &a_, char *smem) : a(a_) {
+    xs = reinterpret_cast<float *>(smem);
+    bacc = xs + RG * Kp;
+    tid = threadIdx.x;
+    j = blockIdx.x * 64 + tid;
+    col_ok = j < a.N;
+    jc = col_ok ? j : a.N - 1;
+    r0 = (int64_t)blockIdx.y * a.rows_per_block;
+    r1 = r0 + a.rows_per_block;
+    if (r1 > a.M) r1 = a.M;
+    cp = a.colp[jc];
+    const int meta = __float_as_int(cp.w);
+    kind = pmf_meta_kind(meta);
+    v = pmf_meta_view(meta);
+    vd = a.views[v >= 0 ? v : 0];
+    for (int e = tid; e < 2 * a.max_nb * 64; e += 64) bacc[e] = 0.f;
+    const float4 *y4 = reinterpret_cast<const float4 *>(a.Y + jc * Kp);
+#pragma unroll
+    for (int q = 0; q < Kp / 4; ++q) yr[q] = y4[q];
+  }
+  // stage RG rows of X (contiguous in memory: X is Kp x M column-major); rows past the chunk are clamped
+  __device__ __forceinline__ void stage_x(int64_t ib) const {
+    __builtin_amdgcn_wave_barrier();
+    for (int e4 = tid; e4 < RG * Kp / 4; e4 += 64) {
+      const int rr = (e4 * 4) / Kp;
+      const int64_t i = ib + rr < r1 ? ib + rr : r1 - 1;
+      reinterpret_cast<float4 *>(xs)[e4] = reinterpret_cast<const float4 *>(a.X + i * Kp)[(e4 * 4 % Kp) / 4];
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  // x_i . y_j of staged row rr
+  __device__ __forceinline__ float dot(int rr) const {
+    const float4 *x4 = reinterpret_cast<const float4 *>(xs + rr * Kp);
+    float acc0 = 0.f, acc1 = 0.f;
+#pragma unroll
+    for (int q = 0; q < Kp / 4; ++q) {
+      const float4 xv = x4[q];
+      acc0 = fmaf(xv.x, yr[q].x, acc0);
+      acc1 = fmaf(xv.y, yr[q].y, acc1);
+      acc0 = fmaf(xv.z, yr[q].z, acc0);
+      acc1 = fmaf(xv.w, yr[q].w, acc1);
+    }
+    return acc0 + acc1;
+  }
+  __device__ __forceinline__ int batch(int64_t i) const { return pmf_row_batch(a.bor, a.M, v, i); }
+  __device__ __forceinline__ float2 batch_dt(int b) const { return pmf_batch_dt(vd, a.btab, jc, b); }
+  __device__ __forceinline__ float data(int64_t i) const { return pmf_d_get(a.D, i, jc, a.nRB, a.d_bf16); }
+  __device__ __forceinline__ float &sum(int which, int b) const { return bacc[(which * a.max_nb + b) * 64 + tid]; }   // which = 0, 1
+  __device__ __forceinline__ int64_t val_index(int b) const { return a.val_off[v] + pmf_view_index(vd, j, b); }   // in logdelta / theta
+};
+
+// ------------------------------------------------------------------------------------------------
+// Layer-parameter gradient pass (update_col_layers stages S2/S7: init_theta! fit.jl:106-122, fit_joint :987-1000).
+// Pull-backs as coded in the reference:
+//   theta_bar[b,j]    = sum_{i in b} g                      (batch_array.jl:141-143)
+//   mu_bar[j]         = sum_i g                             (layers.jl:83)
+//   logdelta_bar[b,j] = delta[b,j] * sum_{i in b} g * (a*sigma_j)   (batch_array.jl:203-204, 250)
+//   logsigma_bar[j]   = sigma_j * sum_i g * delta           (layers.jl:40-41; Q1: omits the input factor)
+// ------------------------------------------------------------------------------------------------
+struct LayerGradArgs : ColWalkArgs {
   float *g_logsigma, *g_mu, *g_logdelta, *g_theta;  // any may be null (only nullness is used by the kernel: see part)
   // per block row (blockIdx.y) one private vector [mu N][logsigma N][theta nbt][logdelta nbt] of part_stride floats, every entry
   // written by exactly one thread; k_sum_parts adds the block rows in fixed order (no float atomics: bitwise reproducible)
   float *part;
   int64_t part_stride, nbt;
   double *loss_partial;                             // may be null; one slot per block (flattened grid)
-  int64_t M, N, nRB;
-  int Kp, K, rows_per_block, max_nb;
-  ViewDesc views[PMF_MAXV];
-  int64_t val_off[PMF_MAXV];
 };
 
 // out[e] = sum over p = 0 .. n_parts-1, in that order, of part[p * stride + e]
@@ -375,235 +408,108 @@ static int sum_parts(pmf_ctx *c, const float *part, int64_t stride, int n_parts,
   return 0;
 }
 
-// One wave per workgroup: thread = column (64 consecutive columns), sequential over a chunk of rows.  The column of Y
-// lives in registers (32*KB floats), four rows of X at a time are staged in LDS and read back as broadcast 16-B reads
-// (a single wave needs no barrier: LDS operations of one wave complete in order), per-(batch, column) sums in LDS
-// (no contention), one plain store per (batch, column) per workgroup at the end (private partials, see LayerGradArgs).
 template <int KB>
 __global__ __launch_bounds__(64) void k_layer_grad(const LayerGradArgs a) {
-  constexpr int Kp = 32 * KB;
-  constexpr int RG = 4;   // rows per group
   extern __shared__ __attribute__((aligned(16))) char smem_lg[];
-  float *xs = reinterpret_cast<float *>(smem_lg);  // [RG][Kp] current rows of X (broadcast)
-  float *bacc = xs + RG * Kp;                      // [2][max_nb][64] per-(batch,column) sums
   __shared__ double sh[4];
-  const int tid = threadIdx.x;
-  const int64_t j = blockIdx.x * 64 + tid;
-  const bool col_ok = j < a.N;
-  const int64_t jc = col_ok ? j : a.N - 1;
-  const int64_t r0 = (int64_t)blockIdx.y * a.rows_per_block;
-  int64_t r1 = r0 + a.rows_per_block;
-  if (r1 > a.M) r1 = a.M;
-  const float4 cp = a.colp[jc];
-  const int meta = __float_as_int(cp.w);
-  const int kind = col_ok ? (meta & 3) : 3;
-  const int v = (meta >> 2) - 1;
-  ViewDesc vd = a.views[v >= 0 ? v : 0];
-  for (int e = tid; e < 2 * a.max_nb * 64; e += 64) bacc[e] = 0.f;
+  ColWalk<KB> w(a, smem_lg);
+  const int kind = w.col_ok ? w.kind : 3;   // (pad columns: the Poisson branch, zeroed below)
+  const float4 cp = w.cp;
   float smu = 0.f, sls = 0.f;
   double lacc = 0.0;
-  float4 yr[Kp / 4];
-  {
-    const float4 *y4 = reinterpret_cast<const float4 *>(a.Y + jc * Kp);
+  for (int64_t ib = w.r0; ib < w.r1; ib += w.RG) {
+    w.stage_x(ib);
 #pragma unroll
-    for (int q = 0; q < Kp / 4; ++q) yr[q] = y4[q];
-  }
-  for (int64_t ib = r0; ib < r1; ib += RG) {
-    // stage RG rows of X (contiguous in memory: X is Kp x M column-major); rows past the chunk are clamped
-    __builtin_amdgcn_wave_barrier();
-    for (int e4 = tid; e4 < RG * Kp / 4; e4 += 64) {
-      const int rr = (e4 * 4) / Kp;
-      const int64_t i = ib + rr < r1 ? ib + rr : r1 - 1;
-      reinterpret_cast<float4 *>(xs)[e4] = reinterpret_cast<const float4 *>(a.X + i * Kp)[(e4 * 4 % Kp) / 4];
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int rr = 0; rr < RG; ++rr) {
+    for (int rr = 0; rr < w.RG; ++rr) {
       const int64_t i = ib + rr;
-      if (i >= r1) break;
-      const float4 *x4 = reinterpret_cast<const float4 *>(xs + rr * Kp);
-      float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-      for (int q = 0; q < Kp / 4; ++q) {
-        const float4 xv = x4[q];
-        acc0 = fmaf(xv.x, yr[q].x, acc0);
-        acc1 = fmaf(xv.y, yr[q].y, acc1);
-        acc0 = fmaf(xv.z, yr[q].z, acc0);
-        acc1 = fmaf(xv.w, yr[q].w, acc1);
-      }
-      const float acc = acc0 + acc1;
-      float dl = 1.f, th = 0.f;
-      int b = -1;
-      if (v >= 0) {
-        b = a.bor[(int64_t)v * a.M + i];
-        if (b >= 0) {
-          const float2 dt = a.btab[vd.tab_off + (jc - vd.c0) * vd.nb + b];
-          dl = dt.x;
-          th = dt.y;
-        }
-      }
-      const float yv = pmf_d_get(a.D, i, jc, a.nRB, a.d_bf16);
+      if (i >= w.r1) break;
+      const float acc = w.dot(rr);
+      const int b = w.batch(i);
+      const float2 dt = w.batch_dt(b);
+      const float yv = w.data(i);
       const float z1 = acc * cp.x;
-      const float z = fmaf(z1, dl, cp.y + th);
+      const float z = fmaf(z1, dt.x, cp.y + dt.y);
       float l, g;
-      if (kind == PMF_NOISE_NORMAL) {
-        const float d = z - yv;
-        g = cp.z * d;
-        l = 0.5f * g * d;
-      } else if (kind == PMF_NOISE_BERNOULLI) {
-        const float e = __expf(-fabsf(z));
-        const float sp = fmaxf(z, 0.f) + __logf(1.f + e);
-        const float r = __frcp_rn(1.f + e);
-        const float sg = z >= 0.f ? r : e * r;
-        l = cp.z * (sp - yv * z);
-        g = cp.z * (sg - yv);
-      } else {
-        const float e = __expf(z);
-        l = cp.z * (e - yv * z);
-        g = cp.z * (e - yv);
-      }
-      const bool ok = (kind != 3) && (fabsf(yv) <= 3.402823466e38f);
+      pmf_noise(kind, z, yv, cp.z, l, g);
+      const bool ok = (kind != 3) && pmf_finite(yv);
       if (!ok) { l = 0.f; g = 0.f; }
       lacc += (double)l;
       smu += g;
-      sls += g * dl;
+      sls += g * dt.x;
       if (b >= 0) {
-        bacc[b * 64 + tid] += g;
-        bacc[(a.max_nb + b) * 64 + tid] += g * z1;
+        w.sum(0, b) += g;
+        w.sum(1, b) += g * z1;
       }
     }
   }
-  if (col_ok) {
+  if (w.col_ok) {
     float *pp = a.part + (int64_t)blockIdx.y * a.part_stride;
-    if (a.g_mu) pp[j] = smu;
-    if (a.g_logsigma) pp[a.N + j] = sls * cp.x;
-    if (v >= 0) {
-      for (int b = 0; b < vd.nb; ++b) {
-        const int64_t e = a.val_off[v] + (j - vd.c0) * vd.nb + b;
-        if (a.g_theta) pp[2 * a.N + e] = bacc[b * 64 + tid];
-        if (a.g_logdelta) {
-          const float dlt = a.btab[vd.tab_off + (j - vd.c0) * vd.nb + b].x;
-          pp[2 * a.N + a.nbt + e] = bacc[(a.max_nb + b) * 64 + tid] * dlt;
-        }
+    if (a.g_mu) pp[w.j] = smu;
+    if (a.g_logsigma) pp[a.N + w.j] = sls * cp.x;
+    if (w.v >= 0) {
+      for (int b = 0; b < w.vd.nb; ++b) {
+        const int64_t e = w.val_index(b);
+        if (a.g_theta) pp[2 * a.N + e] = w.sum(0, b);
+        if (a.g_logdelta) pp[2 * a.N + a.nbt + e] = w.sum(1, b) * a.btab[pmf_btab_index(w.vd, w.j, b)].x;
       }
     }
   }
   const double s = block_reduce_sum(lacc, sh);
-  if (tid == 0 && a.loss_partial) a.loss_partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+  if (w.tid == 0 && a.loss_partial) a.loss_partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
-// Called a handful of times per fit, not per epoch.
+// Column and batch statistics.  Called a handful of times per fit, not per epoch.
 // ------------------------------------------------------------------------------------------------
-struct StatsArgs {
-  const void *D;
-  int d_bf16;
-  const float *X, *Y;
-  const float4 *colp;
-  const int32_t *bor;
-  const float2 *btab;
+struct StatsArgs : ColWalkArgs {
   float *col_n, *col_sum, *col_sumsq, *col_sqerr, *col_ssqg;  // N each: block row 0's vector of the PRIVATE partials -- block row y
   float *b_n, *b_sqerr;                                       // writes at + y * part_stride; flat like theta (may be null)
   int64_t part_stride;                                        // k_sum_parts adds the block rows in fixed order (no float atomics)
-  int64_t M, N, nRB;
-  int Kp, K, rows_per_block, max_nb, use_factors;
-  ViewDesc views[PMF_MAXV];
-  int64_t val_off[PMF_MAXV];
+  int use_factors;                                            // 0: the prediction without the factor term (no staging, no product)
 };
 
-// Same structure as k_layer_grad<KB>: one wave per workgroup, thread = column, Y column in registers, four rows of X
-// at a time through LDS (broadcast 16-B reads, no barrier), per-(batch, column) sums in LDS.
 template <int KB>
 __global__ __launch_bounds__(64) void k_stats(const StatsArgs a) {
-  constexpr int Kp = 32 * KB;
-  constexpr int RG = 4;
   extern __shared__ __attribute__((aligned(16))) char smem_st[];
-  float *xs = reinterpret_cast<float *>(smem_st);   // [RG][Kp]
-  float *bacc = xs + RG * Kp;                        // [2][max_nb][64]
-  const int tid = threadIdx.x;
-  const int64_t j = blockIdx.x * 64 + tid;
-  const bool col_ok = j < a.N;
-  const int64_t jc = col_ok ? j : a.N - 1;
-  const int64_t r0 = (int64_t)blockIdx.y * a.rows_per_block;
-  int64_t r1 = r0 + a.rows_per_block;
-  if (r1 > a.M) r1 = a.M;
-  const float4 cp = a.colp[jc];
-  const int meta = __float_as_int(cp.w);
-  const int kind = meta & 3;
-  const int v = (meta >> 2) - 1;
-  const ViewDesc vd = a.views[v >= 0 ? v : 0];
-  for (int e = tid; e < 2 * a.max_nb * 64; e += 64) bacc[e] = 0.f;
+  ColWalk<KB> w(a, smem_st);
+  const float4 cp = w.cp;
   float sn = 0.f, s1 = 0.f, s2 = 0.f, se = 0.f, sg = 0.f;
-  float4 yr[Kp / 4];
-  {
-    const float4 *y4 = reinterpret_cast<const float4 *>(a.Y + jc * Kp);
+  for (int64_t ib = w.r0; ib < w.r1; ib += w.RG) {
+    if (a.use_factors) w.stage_x(ib);
 #pragma unroll
-    for (int q = 0; q < Kp / 4; ++q) yr[q] = y4[q];
-  }
-  for (int64_t ib = r0; ib < r1; ib += RG) {
-    if (a.use_factors) {
-      __builtin_amdgcn_wave_barrier();
-      for (int e4 = tid; e4 < RG * Kp / 4; e4 += 64) {
-        const int rr = (e4 * 4) / Kp;
-        const int64_t i = ib + rr < r1 ? ib + rr : r1 - 1;
-        reinterpret_cast<float4 *>(xs)[e4] = reinterpret_cast<const float4 *>(a.X + i * Kp)[(e4 * 4 % Kp) / 4];
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-#pragma unroll
-    for (int rr = 0; rr < RG; ++rr) {
+    for (int rr = 0; rr < w.RG; ++rr) {
       const int64_t i = ib + rr;
-      if (i >= r1) break;
+      if (i >= w.r1) break;
       float acc = 0.f;
-      if (a.use_factors) {
-        const float4 *x4 = reinterpret_cast<const float4 *>(xs + rr * Kp);
-        float acc0 = 0.f, acc1 = 0.f;
-#pragma unroll
-        for (int q = 0; q < Kp / 4; ++q) {
-          const float4 xv = x4[q];
-          acc0 = fmaf(xv.x, yr[q].x, acc0);
-          acc1 = fmaf(xv.y, yr[q].y, acc1);
-          acc0 = fmaf(xv.z, yr[q].z, acc0);
-          acc1 = fmaf(xv.w, yr[q].w, acc1);
-        }
-        acc = acc0 + acc1;
-      }
-      float dl = 1.f, th = 0.f;
-      int b = -1;
-      if (v >= 0) {
-        b = a.bor[(int64_t)v * a.M + i];
-        if (b >= 0) {
-          const float2 dt = a.btab[vd.tab_off + (jc - vd.c0) * vd.nb + b];
-          dl = dt.x;
-          th = dt.y;
-        }
-      }
-      const float yv = pmf_d_get(a.D, i, jc, a.nRB, a.d_bf16);
-      if (!(fabsf(yv) <= 3.402823466e38f)) continue;
-      const float z = fmaf(acc * cp.x, dl, cp.y + th);
+      if (a.use_factors) acc = w.dot(rr);
+      const int b = w.batch(i);
+      const float2 dt = w.batch_dt(b);
+      const float yv = w.data(i);
+      if (!pmf_finite(yv)) continue;
+      const float z = fmaf(acc * cp.x, dt.x, cp.y + dt.y);
       float pred, g;
-      if (kind == PMF_NOISE_NORMAL) { pred = z; g = cp.z * (z - yv); }
-      else if (kind == PMF_NOISE_BERNOULLI) { pred = 1.f / (1.f + __expf(-z)); g = cp.z * (pred - yv); }
+      if (w.kind == PMF_NOISE_NORMAL) { pred = z; g = cp.z * (z - yv); }
+      else if (w.kind == PMF_NOISE_BERNOULLI) { pred = 1.f / (1.f + __expf(-z)); g = cp.z * (pred - yv); }
       else { pred = __expf(z); g = cp.z * (pred - yv); }
       const float r = pred - yv;
       sn += 1.f; s1 += yv; s2 += yv * yv; se += r * r; sg += g * g;
       if (b >= 0) {
-        bacc[b * 64 + tid] += 1.f;
-        bacc[(a.max_nb + b) * 64 + tid] += r * r;
+        w.sum(0, b) += 1.f;
+        w.sum(1, b) += r * r;
       }
     }
   }
-  if (col_ok) {
-    const int64_t po = (int64_t)blockIdx.y * a.part_stride;
+  if (w.col_ok) {
+    const int64_t po = (int64_t)blockIdx.y * a.part_stride, j = w.j;
     if (a.col_n) a.col_n[po + j] = sn;
     if (a.col_sum) a.col_sum[po + j] = s1;
     if (a.col_sumsq) a.col_sumsq[po + j] = s2;
     if (a.col_sqerr) a.col_sqerr[po + j] = se;
     if (a.col_ssqg) a.col_ssqg[po + j] = sg;
-    if (v >= 0 && a.b_n) {
-      for (int b = 0; b < vd.nb; ++b) {
-        const int64_t e = a.val_off[v] + (j - vd.c0) * vd.nb + b;
-        a.b_n[po + e] = bacc[b * 64 + tid];
-        a.b_sqerr[po + e] = bacc[(a.max_nb + b) * 64 + tid];
+    if (w.v >= 0 && a.b_n) {
+      for (int b = 0; b < w.vd.nb; ++b) {
+        const int64_t e = w.val_index(b);
+        a.b_n[po + e] = w.sum(0, b);
+        a.b_sqerr[po + e] = w.sum(1, b);
       }
     }
   }
@@ -643,18 +549,10 @@ __global__ __launch_bounds__(256) void k_forward(const ForwardArgs a) {
   for (int k = 0; k < a.K; ++k) acc = fmaf(x[k], ys[k], acc);
   const float4 cp = a.colp[j];
   const int meta = __float_as_int(cp.w);
-  const int v = (meta >> 2) - 1;
-  float dl = 1.f, th = 0.f;
-  if (v >= 0) {
-    const ViewDesc vd = a.views[v];
-    const int b = a.bor[(int64_t)v * a.M + i];
-    if (b >= 0) {
-      const float2 dt = a.btab[vd.tab_off + (j - vd.c0) * vd.nb + b];
-      dl = dt.x;
-      th = dt.y;
-    }
-  }
-  float z = fmaf(acc * cp.x, dl, cp.y + th);
+  const int v = pmf_meta_view(meta);
+  float2 dt = make_float2(1.f, 0.f);
+  if (v >= 0) dt = pmf_batch_dt(a.views[v], a.btab, j, pmf_row_batch(a.bor, a.M, v, i));
+  float z = fmaf(acc * cp.x, dt.x, cp.y + dt.y);
   if (a.synth) {
     const uint64_t ctr = (uint64_t)(j * a.M + i);
     const uint64_t r1 = splitmix64(a.seed ^ (ctr * 2ull));
@@ -662,7 +560,7 @@ __global__ __launch_bounds__(256) void k_forward(const ForwardArgs a) {
     const float u1 = ((r1 >> 40) + 1.0f) * (1.0f / 16777217.0f);
     const float u2 = (r1 & 0xFFFFFFull) * (1.0f / 16777216.0f);
     const float nrm = sqrtf(-2.f * logf(u1)) * cosf(6.28318530718f * u2);
-    const int kind = meta & 3;
+    const int kind = pmf_meta_kind(meta);
     if (kind == PMF_NOISE_NORMAL) z += a.noise * nrm;
     else if (kind == PMF_NOISE_BERNOULLI) z = (z + a.noise * nrm) > 0.f ? 1.f : 0.f;
     else z = floorf(__expf(fminf(z, 10.f)));
@@ -677,6 +575,23 @@ __global__ __launch_bounds__(256) void k_forward(const ForwardArgs a) {
 // host side helpers
 // ------------------------------------------------------------------------------------------------
 static inline int nblocks(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
+
+// the by-value copy of the batch views (and of their offsets into logdelta / theta) a kernel's argument struct carries
+static void fill_views(const pmf_ctx *c, ViewDesc *views, int64_t *val_off = nullptr) {
+  for (int v = 0; v < c->n_bv; ++v) {
+    views[v] = c->views[v];
+    if (val_off) val_off[v] = c->val_off[v];
+  }
+}
+// room for the n loss partials of the pass about to be launched, which k_loss_reduce will then sum
+static int ensure_loss_partials(pmf_ctx *c, int64_t n) {
+  if (n > c->loss_cap) {
+    PMFCHK(dev_alloc(&c->loss_partial, (size_t)n));
+    c->loss_cap = n;
+  }
+  c->n_macro = n;
+  return 0;
+}
 
 static int upload_padded(pmf_ctx *c, float *dst, const float *src, int64_t n, float padval) {
   // src: host K x n ; dst: device Kp x n
@@ -1332,7 +1247,7 @@ static int prepare(pmf_ctx *c) {
       DenseBtabArgs da;
       memset(&da, 0, sizeof(da));
       da.colmeta = c->colmeta; da.btab = c->btab; da.btd = c->btd; da.colview = c->colview; da.N = c->N; da.Npad = Npad; da.nbs_shift = shift;
-      for (int v = 0; v < c->n_bv; ++v) da.views[v] = c->views[v];
+      fill_views(c, da.views);
       k_dense_btab<<<nblocks(Npad * c->nbs, 256), 256, 0, c->stream>>>(da);
       HIPCHK(hipGetLastError());
       c->btd_ok = true;
@@ -1794,11 +1709,7 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     grid_sum += grid;
   }
   serial_sum = c->split_serial * PMF_MAX_CHUNKS + g.S;   // (split_serial is bumped by every recomputed split)
-  if (grid_sum > c->loss_cap) {
-    PMFCHK(dev_alloc(&c->loss_partial, (size_t)grid_sum));
-    c->loss_cap = grid_sum;
-  }
-  c->n_macro = grid_sum;                 // loss partials: one per workgroup and chunk
+  PMFCHK(ensure_loss_partials(c, grid_sum));   // one per workgroup and chunk
   const int64_t slab_stride = (int64_t)c->Kp * c->N;
   // never read before written, EXCEPT by pmf_fused_sb8_kernel, which loads the old values of a ragged last tile's absent
   // columns without clamping (they are accumulated and never stored): one tile of padding at THIS Kp keeps those loads in
@@ -1991,46 +1902,56 @@ static int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy) {
   return 0;
 }
 
-// k_layer_grad / k_stats keep [2][max_nb][64] batch sums in dynamic LDS, on top of the kernel's static LDS (k_layer_grad:
+// ---- host side of the column walk (k_layer_grad / k_stats)
+// The shared arguments and the grid: gx blocks of 64 columns x gy block rows of a.rows_per_block rows.
+static void col_walk_fill(pmf_ctx *c, ColWalkArgs &a, int &gx, int64_t &gy) {
+  a.D = c->D; a.d_bf16 = c->store == PMF_STORE_BF16; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab;
+  a.M = c->M; a.N = c->N; a.nRB = c->nRB; a.Kp = c->Kp; a.K = c->K;
+  fill_views(c, a.views, a.val_off);
+  a.max_nb = 1;
+  for (int v = 0; v < c->n_bv; ++v) a.max_nb = std::max(a.max_nb, c->views[v].nb);
+  gx = nblocks(c->N, 64);
+  // ~32 single-wave workgroups per CU hide the FMA / LDS latencies; at least 256 rows per workgroup keep the final
+  // partial stores (64 * (2 + 2 nb) per workgroup, added by k_sum_parts) negligible
+  gy = std::max<int64_t>(1, std::min<int64_t>((32ll * c->n_cu + gx - 1) / gx, (c->M + 255) / 256));
+  a.rows_per_block = (int)((c->M + gy - 1) / gy);
+  gy = (c->M + a.rows_per_block - 1) / a.rows_per_block;
+}
+// Launches kerns[KB - 1].  The [2][max_nb][64] batch sums are dynamic LDS on top of the kernel's static LDS (k_layer_grad:
 // block_reduce_sum's slots): past 160 KiB together the launch is refused here, naming the batch count.
-static int check_lds_fits(const void *kern, size_t lds, int max_nb, const char *what) {
+template <typename Args>
+static int col_walk_launch(pmf_ctx *c, void (*const (&kerns)[4])(const Args), const Args &a, int gx, int64_t gy, const char *what) {
+  if (c->KB < 1 || c->KB > 4) return pmf_fail("unsupported KB=%d", c->KB);
+  const void *kern = (const void *)kerns[c->KB - 1];
+  const size_t lds = col_walk_lds(c->Kp, a.max_nb);
   hipFuncAttributes fa;
   HIPCHK(hipFuncGetAttributes(&fa, kern));
   if (lds + fa.sharedSizeBytes > 160 * 1024)
-    return pmf_fail("too many row batches per view (%d) for the %s kernel", max_nb, what);
+    return pmf_fail("too many row batches per view (%d) for the %s kernel", a.max_nb, what);
+  PMFCHK(ensure_dyn_lds(c, kern, lds));
+  hipLaunchKernelGGL(kerns[c->KB - 1], dim3(gx, (unsigned)gy), dim3(64), lds, c->stream, a);
+  HIPCHK(hipGetLastError());
   return 0;
+}
+
+// where the layer gradients go: null for a frozen layer (bits of frozen_layers: 1 logsigma, 2 logdelta, 4 mu, 8 theta) and
+// for the batch layers of a model without batch views
+static void layer_grad_targets(pmf_ctx *c, const pmf_fit_opts *o, float *&g_logsigma, float *&g_logdelta, float *&g_mu, float *&g_theta) {
+  const int fl = o->frozen_layers;
+  g_logsigma = (fl & 1) ? nullptr : c->P[2].g;
+  g_logdelta = ((fl & 2) || c->n_bv == 0) ? nullptr : c->P[4].g;
+  g_mu = (fl & 4) ? nullptr : c->P[3].g;
+  g_theta = ((fl & 8) || c->n_bv == 0) ? nullptr : c->P[5].g;
 }
 
 static int launch_layer_grad(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) {
   LayerGradArgs a;
   memset(&a, 0, sizeof(a));
-  a.D = c->D; a.d_bf16 = c->store == PMF_STORE_BF16; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab;
-  const int fl = o->frozen_layers;
-  a.g_logsigma = (fl & 1) ? nullptr : c->P[2].g;
-  a.g_logdelta = ((fl & 2) || c->n_bv == 0) ? nullptr : c->P[4].g;
-  a.g_mu = (fl & 4) ? nullptr : c->P[3].g;
-  a.g_theta = ((fl & 8) || c->n_bv == 0) ? nullptr : c->P[5].g;
-  a.M = c->M; a.N = c->N; a.nRB = c->nRB; a.Kp = c->Kp; a.K = c->K;
-  int max_nb = 1;
-  for (int v = 0; v < c->n_bv; ++v) {
-    a.views[v] = c->views[v];
-    a.val_off[v] = c->val_off[v];
-    max_nb = std::max(max_nb, c->views[v].nb);
-  }
-  a.max_nb = max_nb;
-  const int gx = nblocks(c->N, 64);
-  // ~32 single-wave workgroups per CU hide the FMA / LDS latencies; at least 256 rows per workgroup keep the final
-  // partial stores (64 * (2 + 2 nb) per workgroup, added by k_sum_parts) negligible
-  int64_t gy = std::max<int64_t>(1, std::min<int64_t>((32ll * c->n_cu + gx - 1) / gx, (c->M + 255) / 256));
-  a.rows_per_block = (int)((c->M + gy - 1) / gy);
-  gy = (c->M + a.rows_per_block - 1) / a.rows_per_block;
-  const int64_t nslots = (int64_t)gx * gy;
+  int gx; int64_t gy;
+  col_walk_fill(c, a, gx, gy);
+  layer_grad_targets(c, o, a.g_logsigma, a.g_logdelta, a.g_mu, a.g_theta);
   if (with_loss) {
-    if (nslots > c->loss_cap) {
-      PMFCHK(dev_alloc(&c->loss_partial, (size_t)nslots));
-      c->loss_cap = nslots;
-    }
-    c->n_macro = nslots;
+    PMFCHK(ensure_loss_partials(c, (int64_t)gx * gy));
     a.loss_partial = c->loss_partial;
   }
   // private partials per block row, summed in fixed order afterwards (every entry of a vector is written by its block)
@@ -2042,19 +1963,7 @@ static int launch_layer_grad(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
     c->lgrad_part_cap = (size_t)(a.part_stride * gy);
   }
   a.part = c->lgrad_part;
-  void (*kern)(const LayerGradArgs) = nullptr;
-  switch (c->KB) {
-    case 1: kern = k_layer_grad<1>; break;
-    case 2: kern = k_layer_grad<2>; break;
-    case 3: kern = k_layer_grad<3>; break;
-    case 4: kern = k_layer_grad<4>; break;
-    default: return pmf_fail("unsupported KB=%d", c->KB);
-  }
-  const size_t lds = sizeof(float) * (size_t)(4 * c->Kp + 2 * max_nb * 64);
-  PMFCHK(check_lds_fits((const void *)kern, lds, max_nb, "layer-gradient"));
-  PMFCHK(ensure_dyn_lds(c, (const void *)kern, lds));
-  hipLaunchKernelGGL(kern, dim3(gx, (unsigned)gy), dim3(64), lds, c->stream, a);
-  HIPCHK(hipGetLastError());
+  PMFCHK(col_walk_launch(c, {k_layer_grad<1>, k_layer_grad<2>, k_layer_grad<3>, k_layer_grad<4>}, a, gx, gy, "layer-gradient"));
   PMFCHK(sum_parts(c, a.part, a.part_stride, (int)gy, a.g_mu, c->N));
   PMFCHK(sum_parts(c, a.part + c->N, a.part_stride, (int)gy, a.g_logsigma, c->N));
   PMFCHK(sum_parts(c, a.part + 2 * c->N, a.part_stride, (int)gy, a.g_theta, nbt));
@@ -2095,13 +2004,7 @@ static int launch_layer_pass(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
     c->LG_cap = lg_stride * n_parts;
   }
   HIPCHK(hipMemsetAsync(c->LG, 0, sizeof(float2) * (size_t)(lg_stride * n_parts), c->stream));
-  if (with_loss) {
-    if (grid > c->loss_cap) {
-      PMFCHK(dev_alloc(&c->loss_partial, (size_t)grid));
-      c->loss_cap = grid;
-    }
-    c->n_macro = grid;
-  }
+  if (with_loss) PMFCHK(ensure_loss_partials(c, grid));
   LayerPassArgs a;
   memset(&a, 0, sizeof(a));
   a.D = c->D; a.d_bf16 = c->store == PMF_STORE_BF16; a.nRB = c->nRB; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor;
@@ -2111,13 +2014,9 @@ static int launch_layer_pass(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
   PMFCHK(pmf_launch_layer_pass(&c->dyn_lds, c->stream, c->KB, lnw, c->mixed, grid, a));
   LayerMapArgs m;
   memset(&m, 0, sizeof(m));
-  const int fl = o->frozen_layers;
   m.LG = c->LG; m.lg_stride = lg_stride; m.n_parts = (int32_t)n_parts; m.btd = a.btd; m.colp = c->colp; m.N = c->N; m.n_bv = c->n_bv; m.nbs_shift = nbs_shift;
-  m.g_logsigma = (fl & 1) ? nullptr : c->P[2].g;
-  m.g_logdelta = ((fl & 2) || c->n_bv == 0) ? nullptr : c->P[4].g;
-  m.g_mu = (fl & 4) ? nullptr : c->P[3].g;
-  m.g_theta = ((fl & 8) || c->n_bv == 0) ? nullptr : c->P[5].g;
-  for (int v = 0; v < c->n_bv; ++v) { m.views[v] = c->views[v]; m.val_off[v] = c->val_off[v]; }
+  layer_grad_targets(c, o, m.g_logsigma, m.g_logdelta, m.g_mu, m.g_theta);
+  fill_views(c, m.views, m.val_off);
   return pmf_launch_layer_map(c->stream, m);
 }
 
@@ -2137,16 +2036,15 @@ int step_param_range(pmf_ctx *c, int which, int64_t e0, int64_t n, bool do_step,
                             int *reg_count, int max_blocks, bool advance) {
   ParamBuf &b = c->P[which];
   if (b.n == 0 || n == 0) return 0;
-  StepArgs s;
+  StepArgsGraph s;   // (the plain instance takes its StepArgs part)
   memset(&s, 0, sizeof(s));
   s.p = b.p + e0; s.g = b.g + e0; s.acc = b.acc + e0; s.mom = b.mom + e0;
   s.wq = b.wq ? b.wq + e0 : nullptr; s.cq = b.cq ? b.cq + e0 : nullptr;
   s.Kp = which <= 1 ? c->Kp : 1;
   s.K = which <= 1 ? c->K : 1;
   if (which == 1 && c->has_ard) { s.ard_alpha = c->ard_alpha + e0 / s.Kp; s.ard_beta = c->ard_beta + e0; s.ard_scale = c->ard_scale; }
-  StepArgsGraph sg;
-  sg.gpre = which <= 1 && c->net[which] ? c->net[which]->grad + e0 : nullptr;
-  sg.wl1 = b.wl1 ? b.wl1 + e0 : nullptr;
+  s.gpre = which <= 1 && c->net[which] ? c->net[which]->grad + e0 : nullptr;
+  s.wl1 = b.wl1 ? b.wl1 + e0 : nullptr;
   s.n = n;
   s.opt_kind = c->opt_kind; s.lr = c->lr; s.eps = c->eps; s.b1 = c->b1; s.b2 = c->b2;
   s.c1 = 1.f - b.bp1; s.c2 = 1.f - b.bp2;
@@ -2154,9 +2052,8 @@ int step_param_range(pmf_ctx *c, int which, int64_t e0, int64_t n, bool do_step,
   const int grid = (int)std::min<int64_t>(max_blocks, nblocks(n, 256));
   s.reg_partial = c->reg_partial + (int64_t)reg_slot * REG_SLOTS + *reg_count;
   if (*reg_count + grid > REG_SLOTS) return pmf_fail("internal: regularizer partial slab overflow");
-  sg.a = s;
-  if (use_reg && (sg.gpre || sg.wl1)) k_reg_step_graph<<<grid, 256, 0, c->stream>>>(sg);
-  else k_reg_step<<<grid, 256, 0, c->stream>>>(s);
+  if (use_reg && (s.gpre || s.wl1)) k_reg_step<true><<<grid, 256, 0, c->stream>>>(s);
+  else k_reg_step<false><<<grid, 256, 0, c->stream>>>(s);
   HIPCHK(hipGetLastError());
   *reg_count += grid;
   if (advance && do_step && c->opt_kind == PMF_OPT_ADAM) { b.bp1 *= c->b1; b.bp2 *= c->b2; }
@@ -2318,7 +2215,7 @@ static int run_forward(pmf_ctx *c, float *Zdev, int synth, uint64_t seed, float 
   a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.Z = Zdev;
   a.z_bf16 = nRB > 0 && c->store == PMF_STORE_BF16;
   a.M = c->M; a.N = c->N; a.nRB = nRB; a.Kp = c->Kp; a.K = c->K; a.synth = synth; a.seed = seed; a.noise = noise; a.frac_nan = frac_nan;
-  for (int v = 0; v < c->n_bv; ++v) a.views[v] = c->views[v];
+  fill_views(c, a.views);
   if ((c->M + 255) / 256 > 65535) return pmf_fail("M too large for the forward kernel grid");
   hipLaunchKernelGGL(k_forward, dim3((unsigned)c->N, (unsigned)((c->M + 255) / 256)), dim3(256), 0, c->stream, a);
   HIPCHK(hipGetLastError());
@@ -2486,19 +2383,9 @@ extern "C" int pmf_stats(pmf_ctx *c, int use_factors, float *col_n, float *col_s
   const size_t nfl = (size_t)(5 * c->N + 2 * nbt);
   StatsArgs a;
   memset(&a, 0, sizeof(a));
-  a.D = c->D; a.d_bf16 = c->store == PMF_STORE_BF16; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab;
-  a.M = c->M; a.N = c->N; a.nRB = c->nRB; a.Kp = c->Kp; a.K = c->K; a.use_factors = use_factors;
-  int max_nb = 1;
-  for (int v = 0; v < c->n_bv; ++v) {
-    a.views[v] = c->views[v];
-    a.val_off[v] = c->val_off[v];
-    max_nb = std::max(max_nb, c->views[v].nb);
-  }
-  a.max_nb = max_nb;
-  const int gx = nblocks(c->N, 64);
-  int64_t gy = std::max<int64_t>(1, std::min<int64_t>((32ll * c->n_cu + gx - 1) / gx, (c->M + 255) / 256));
-  a.rows_per_block = (int)((c->M + gy - 1) / gy);
-  gy = (c->M + a.rows_per_block - 1) / a.rows_per_block;
+  int gx; int64_t gy;
+  col_walk_fill(c, a, gx, gy);
+  a.use_factors = use_factors;
   // scratch: [results nfl][gy private partial vectors of nfl]; every entry of a partial vector is written by its block row,
   // the block rows are then added in fixed order (k_sum_parts): no float atomics, bitwise reproducible statistics
   PMFCHK(ensure_scratch(c, sizeof(float) * std::max<size_t>(nfl * (size_t)(gy + 1), 1)));
@@ -2507,19 +2394,7 @@ extern "C" int pmf_stats(pmf_ctx *c, int use_factors, float *col_n, float *col_s
   a.col_n = part; a.col_sum = part + c->N; a.col_sumsq = part + 2 * c->N; a.col_sqerr = part + 3 * c->N; a.col_ssqg = part + 4 * c->N;
   a.b_n = nbt ? part + 5 * c->N : nullptr;
   a.b_sqerr = nbt ? part + 5 * c->N + nbt : nullptr;
-  void (*kst)(const StatsArgs) = nullptr;
-  switch (c->KB) {
-    case 1: kst = k_stats<1>; break;
-    case 2: kst = k_stats<2>; break;
-    case 3: kst = k_stats<3>; break;
-    case 4: kst = k_stats<4>; break;
-    default: return pmf_fail("unsupported KB=%d", c->KB);
-  }
-  const size_t lds = sizeof(float) * (size_t)(4 * c->Kp + 2 * max_nb * 64);
-  PMFCHK(check_lds_fits((const void *)kst, lds, max_nb, "statistics"));
-  PMFCHK(ensure_dyn_lds(c, (const void *)kst, lds));
-  hipLaunchKernelGGL(kst, dim3(gx, (unsigned)gy), dim3(64), lds, c->stream, a);
-  HIPCHK(hipGetLastError());
+  PMFCHK(col_walk_launch(c, {k_stats<1>, k_stats<2>, k_stats<3>, k_stats<4>}, a, gx, gy, "statistics"));
   PMFCHK(sum_parts(c, part, (int64_t)nfl, (int)gy, buf, (int64_t)nfl));
   HIPCHK(hipStreamSynchronize(c->stream));
   float *outs[5] = {col_n, col_sum, col_sumsq, col_sqerr, col_ssq_grad};

@@ -88,19 +88,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(co
       const int meta = __float_as_int(cp.w);
       Cmu[c] = cp.y;
       Cmt[c] = meta;
-      int64_t base = 0;
-      if (batch && (meta >> 2) > 0) {
-        const ViewDesc vd = a.views[(meta >> 2) - 1];
-        base = vd.tab_off + (jc - vd.c0) * vd.nb;
-      }
-      Cbase[c] = base;
+      Cbase[c] = batch && pmf_meta_view(meta) >= 0 ? pmf_btab_index(a.views[pmf_meta_view(meta)], jc, 0) : 0;
     }
     __syncthreads();
     // one noise kind in the whole tile (the usual case: columns are sorted by distribution): a wave-uniform branch
     int tk[LS];
 #pragma unroll
     for (int t = 0; t < LS; ++t) {
-      const int kd = link || t >= nt ? PMF_NOISE_NORMAL : (Cmt[t * 32 + l31] & 3);
+      const int kd = link || t >= nt ? PMF_NOISE_NORMAL : pmf_meta_kind(Cmt[t * 32 + l31]);
       const int k0 = __builtin_amdgcn_readfirstlane(kd);
       tk[t] = __all(kd == k0) ? k0 : 3;
     }
@@ -174,7 +169,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(co
               const int r = 4 * c4 + u;
               const int meta = u == 0 ? mt4.x : (u == 1 ? mt4.y : (u == 2 ? mt4.z : mt4.w));
               const float muj = u == 0 ? mu4.x : (u == 1 ? mu4.y : (u == 2 ? mu4.z : mu4.w));
-              const int v = (meta >> 2) - 1;
+              const int v = pmf_meta_view(meta);
               float2 dt = make_float2(1.f, 0.f);
               if (v >= 0) {
                 const int b = Bw[v * 32 + l31];
@@ -197,7 +192,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(co
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
               const int meta = u == 0 ? mt4.x : (u == 1 ? mt4.y : (u == 2 ? mt4.z : mt4.w));
-              acc[4 * c4 + u] = pmf_impute_invlink(meta & 3, acc[4 * c4 + u]);
+              acc[4 * c4 + u] = pmf_impute_invlink(pmf_meta_kind(meta), acc[4 * c4 + u]);
             }
           }
         }
@@ -234,15 +229,11 @@ __global__ __launch_bounds__(256) void k_impute_entries(const ImputeEntriesArgs 
   float z = acc * cp.x;
   if ((a.flags & PMF_IMPUTE_BATCH) != 0) {
     float2 dt = make_float2(1.f, 0.f);
-    const int v = (meta >> 2) - 1;
-    if (v >= 0) {
-      const ViewDesc vd = a.views[v];
-      const int b = a.bor[(int64_t)v * a.M + i];
-      if (b >= 0) dt = a.btab[vd.tab_off + (j - vd.c0) * vd.nb + b];
-    }
+    const int v = pmf_meta_view(meta);
+    if (v >= 0) dt = pmf_batch_dt(a.views[v], a.btab, j, pmf_row_batch(a.bor, a.M, v, i));
     z = pmf_impute_batch(z, cp.y, dt);
   } else {
     z += cp.y;
   }
-  a.out[e] = pmf_impute_invlink((a.flags & PMF_IMPUTE_LINK) != 0 ? PMF_NOISE_NORMAL : (meta & 3), z);
+  a.out[e] = pmf_impute_invlink((a.flags & PMF_IMPUTE_LINK) != 0 ? PMF_NOISE_NORMAL : pmf_meta_kind(meta), z);
 }

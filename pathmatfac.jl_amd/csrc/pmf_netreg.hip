@@ -19,7 +19,7 @@
 //                        rounded once (a hub row has hundreds of terms).
 //                        Writes u_k, the iteration count and t'u + 0.5 u'BB u (f64).
 //   k_netreg_grad      : (row block, factor): p * (AA_k p_k + AB_k u_k) per row into a buffer in P's own layout that
-//                        k_reg_step_graph adds to the gradient, and p * 0.5 p'AA p summed in f64 into one loss partial per
+//                        k_reg_step<true> adds to the gradient, and p * 0.5 p'AA p summed in f64 into one loss partial per
 //                        workgroup (the factor's first workgroup adds the solve's p * (t'u + 0.5 u'BB u)).
 // The stopping rule is the library's own (Krylov.jl's is not reproduced): stop at |r| <= 1e-6 |t_k| or after 2 v_k
 // iterations, t_k = 0 gives u_k = 0; the warm start is the previous u_k.

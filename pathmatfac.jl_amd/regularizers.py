@@ -1,6 +1,6 @@
 """Regularizers (src/regularizers.jl, src/featureset_ard.jl): host-side descriptors.
 
-Their value and gradient are evaluated on the device by k_reg_step / k_reg_step_graph (csrc/pmf_hip.hip); the classes below hold the
+Their value and gradient are evaluated on the device by k_reg_step<false> / k_reg_step<true> (csrc/pmf_hip.hip); the classes below hold the
 parameters, mirror the reference's constructors and freeze bookkeeping, and know how to marshal themselves
 through the C ABI.  The pathway-graph family (NetworkRegularizer, SelectiveL1Reg, L1Regularizer) builds its sparse
 blocks on the host (scipy) exactly as the reference's constructors do; the per-epoch solve for the virtual nodes runs

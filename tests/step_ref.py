@@ -1,4 +1,4 @@
-"""Helpers of the regularizer + optimizer step tests (k_reg_step / k_reg_step_graph and the code around them): the dense
+"""Helpers of the regularizer + optimizer step tests (k_reg_step<false> / k_reg_step<true> and the code around them): the dense
 regularizer terms built in float64 straight from the C ABI's arguments (1-based inclusive ranges, as tests/problems.py
 carries them; none of the library's expanders is called), the closed formulas of the regularizer value / gradient and of
 the AdaGrad / Adam step in float64, a float32 twin of both (the same formulas, every operation in np.float32 and in the

@@ -1,4 +1,4 @@
-"""The pathway-graph regularizers on the DEVICE (csrc/pmf_netreg.hip, k_reg_step_graph): NetworkRegularizer, SelectiveL1Reg and
+"""The pathway-graph regularizers on the DEVICE (csrc/pmf_netreg.hip, k_reg_step<true>): NetworkRegularizer, SelectiveL1Reg and
 L1Regularizer marshalled through the C ABI and evaluated on the GPU, against the reference's literals
 (tests/golden/network_reg.json) and the exact fp64 restatement of tests/netreg_ref.py.  Value and gradient are read as
 tests/test_gpu_reg_literals.py does: data term off (every entry of D missing), one Adam step at lr -> 0, gradient = first

@@ -1,4 +1,4 @@
-"""The regularizer + optimizer step (k_reg_step / k_reg_step_graph, the range expanders, step_param_range, step_layers
+"""The regularizer + optimizer step (k_reg_step<false> / k_reg_step<true>, the range expanders, step_param_range, step_layers
 and the optimizer-state entry points) at size, range, chunk and state edges.
 
 The step is elementwise: given the device's own data gradient (pmf_get_grad after pmf_epoch_begin) and its own parameter
