@@ -210,6 +210,71 @@ int pmf_get_opt_state(pmf_ctx *ctx, int which, int view, float *acc, float *mom)
 /* MF.fit!(model.matfac, model.data; ...) as called from mf_fit! (src/fit.jl:24-36) */
 int pmf_fit(pmf_ctx *ctx, const pmf_fit_opts *opts, pmf_fit_result *result);
 
+/* full_loss(model, D) (src/fit_lbfgs.jl:3-8): data loss + X_reg(X) + Y_reg(Y) at the context's CURRENT parameters, the
+ * layer regularizers not included.  total = data + xreg + yreg (each output may be NULL).  The data term is always the
+ * exact-f32 pass, whatever pmf_set_precision says, summed in a fixed order: a value is bitwise the same run to run.
+ * Touches no parameter, gradient, optimizer state or communicator (it does overwrite the loss partials of the
+ * step-level API: do not call it between pmf_epoch_begin and pmf_epoch_loss).  Refused with a network term attached
+ * (evaluating it would move its warm-start state). */
+int pmf_loss(pmf_ctx *ctx, double *total, double *data, double *xreg, double *yreg);
+
+/* fit_lbfgs!(matfac, D; ...) (src/fit_lbfgs.jl:170-243): L-BFGS over X and Y together with the backtracking line search
+ * of backtrack! (:114-148) and the two-loop recursion of inner_loop! (:151-167); layers, noise weights and regularizer
+ * weights are constants.  The rules, the reference's quirks included, are restated in DESIGN.md section 2 ("Deviation 2 /
+ * L-BFGS").  Loss = pmf_loss; gradient = the fused data pass (in the context's precision mode) + the gradients of the
+ * attached quadratic (L2, group) and ARD-type terms.  Every inner product is a fixed-order f64 sum: a call repeats
+ * bit for bit.
+ *   m                   history length, 1..32 (the bound is the library's: scalars per pair live in fixed device slots);
+ *                       the call holds 2 m + 4 vectors of K_p (M + N) floats on the device, kept until (K, M, N, m) change
+ *   max_iter            fit_lbfgs!'s max_iter (0: only the start loss is evaluated)
+ *   backtrack_max_iter  backtrack!'s max_iter (reference: 100), >= 1
+ *   rel_tol, abs_tol    :230-236; backtrack_shrinkage in (0, 1); c1 = 1e-4 (sufficient_decrease :111); sy_min = 1e-4 (:216)
+ *   verbosity, print_iter  "(iter) L-BFGS; Loss=..." every print_iter iterations (:195-197)
+ * Result: term_code PMF_TERM_ABS_TOL / REL_TOL / NONFINITE (a non-finite loss after a backtrack; the reference would go
+ * on) / MAX_EPOCHS (max_iter reached); iters = line searches run; final_loss = the loss at the parameters the call
+ * leaves (bitwise pmf_loss there); loss_evals / grad_evals = data passes of either kind; resets = history resets.
+ * Traces (caller-owned, trace_cap entries each, any may be NULL; filled when keep_trace): per iteration the loss after
+ * the backtrack, its trial count, and flags: bit 0 reset (<s,y> <= sy_min), bit 1 the direction was no descent direction
+ * and -g was taken, bit 2 the backtrack ran out of trials.
+ * A start with a zero direction (e.g. X = Y = 0) returns PMF_TERM_ABS_TOL at once, parameters untouched.
+ * Refused: no data / factors; a network or L1 / SelectiveL1 term on X or Y; a communicator of more than one rank; m,
+ * backtrack_shrinkage, max_iter or backtrack_max_iter out of range.  Leaves the optimizer state, Adam's powers and the
+ * learning rate alone. */
+typedef struct pmf_lbfgs_opts {
+  int32_t m;
+  int32_t max_iter;
+  int32_t backtrack_max_iter;
+  int32_t keep_trace;
+  int32_t verbosity;
+  int32_t print_iter;
+  double rel_tol;
+  double abs_tol;
+  double backtrack_shrinkage;
+  double c1;
+  double sy_min;
+} pmf_lbfgs_opts;
+typedef struct pmf_lbfgs_result {
+  int32_t term_code;
+  int32_t iters;
+  int32_t loss_evals;
+  int32_t grad_evals;
+  int32_t resets;
+  int32_t n_trace;     /* entries written to the traces */
+  int32_t trace_cap;   /* in: capacity of each trace */
+  int32_t reserved;
+  double final_loss;
+  double seconds;
+  double *loss_trace;   /* in: host buffers (may be NULL) */
+  int32_t *trial_trace;
+  int32_t *flag_trace;
+} pmf_lbfgs_result;
+int pmf_fit_lbfgs(pmf_ctx *ctx, const pmf_lbfgs_opts *opts, pmf_lbfgs_result *result);
+/* The recursion kernels of pmf_fit_lbfgs on a handed-in history (tests): n_pairs (0..32) pairs (s, y) stacked NEWEST
+ * FIRST, each in the reference's shapes (sX, yX: n_pairs x K x M; sY, yY: n_pairs x K x N), the gradient g, and the
+ * direction p = -H g out.  No reset test.  Needs data and factors set (they fix K, M, N). */
+int pmf_debug_lbfgs_direction(pmf_ctx *ctx, int n_pairs, const float *sX, const float *sY, const float *yX,
+                              const float *yY, const float *gX, const float *gY, float *pX, float *pY);
+
 /* Step-level API (what pmf_fit is made of), exposed so that a multi-GPU host can place the cross-GPU
  * reduction of grad(Y) and of the loss between the two halves of an epoch (DESIGN.md "multi-GPU"):
  *   pmf_epoch_begin     : fused data pass -> local data loss partials + data gradients (async on the stream)

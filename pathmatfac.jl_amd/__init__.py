@@ -13,6 +13,8 @@ from .fit import (mf_fit_, mf_fit_adapt_lr_, init_theta_, init_factors_, constru
                   reweight_col_losses_, construct_minimal_regularizer, init_batch_effects_, theta_delta_em, whiten_,
                   rotate_by_svd_, reorder_by_importance_, reweight_eb_, basic_fit_, fit_ard_, fit_non_ard_,
                   fit_feature_set_ard_, fit_)
+from . import fit_lbfgs as _fit_lbfgs  # noqa: F401
+from .fit_lbfgs import fit_lbfgs_  # noqa: F401
 from . import featureset_ard  # noqa: F401
 from .featureset_ard import update_A_, update_lambda_  # noqa: F401
 from .transform import transform  # noqa: F401

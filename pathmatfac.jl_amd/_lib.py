@@ -39,6 +39,19 @@ class FitResult(C.Structure):
                 ("seconds", C.c_double)]
 
 
+class LbfgsOpts(C.Structure):
+    _fields_ = [("m", C.c_int32), ("max_iter", C.c_int32), ("backtrack_max_iter", C.c_int32), ("keep_trace", C.c_int32),
+                ("verbosity", C.c_int32), ("print_iter", C.c_int32), ("rel_tol", C.c_double), ("abs_tol", C.c_double),
+                ("backtrack_shrinkage", C.c_double), ("c1", C.c_double), ("sy_min", C.c_double)]
+
+
+class LbfgsResult(C.Structure):
+    _fields_ = [("term_code", C.c_int32), ("iters", C.c_int32), ("loss_evals", C.c_int32), ("grad_evals", C.c_int32),
+                ("resets", C.c_int32), ("n_trace", C.c_int32), ("trace_cap", C.c_int32), ("reserved", C.c_int32),
+                ("final_loss", C.c_double), ("seconds", C.c_double), ("loss_trace", C.POINTER(C.c_double)),
+                ("trial_trace", C.POINTER(C.c_int32)), ("flag_trace", C.POINTER(C.c_int32))]
+
+
 class Csr(C.Structure):
     """pmf_csr: one sparse block in 0-based CSR with sorted rows."""
     _fields_ = [("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rowptr", C.POINTER(C.c_int64)),
@@ -70,6 +83,7 @@ EXPORTS = [
     "pmf_comm_info", "pmf_comm_allreduce", "pmf_get_opt_state", "pmf_fsard_update_A", "pmf_debug_last_path", "pmf_debug_last_kernel",
     "pmf_add_xreg_network", "pmf_add_yreg_network", "pmf_get_reg_network_state", "pmf_add_xreg_l1", "pmf_add_yreg_l1",
     "pmf_impute", "pmf_impute_device", "pmf_impute_entries", "pmf_debug_impute_offset",
+    "pmf_loss", "pmf_fit_lbfgs", "pmf_debug_lbfgs_direction",
 ]
 
 COMM_ID_BYTES = 128
@@ -400,6 +414,46 @@ class Context:
         self._chk(self.lib.pmf_fit(self._h, C.byref(o), C.byref(r)))
         return {"term_code": TERM[r.term_code], "epochs": r.epochs, "loss": trace[:r.n_trace].copy(),
                 "final_loss": r.final_loss, "seconds": r.seconds}
+
+    def loss(self):
+        """pmf_loss: dict(total, data, xreg, yreg) at the current parameters (full_loss, src/fit_lbfgs.jl:3-8)."""
+        v = [C.c_double(0) for _ in range(4)]
+        self._chk(self.lib.pmf_loss(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("total", "data", "xreg", "yreg"), (x.value for x in v)))
+
+    def fit_lbfgs(self, m=10, max_iter=1000, backtrack_max_iter=100, rel_tol=1e-9, abs_tol=1e-6, backtrack_shrinkage=0.8,
+                  c1=1e-4, sy_min=1e-4, keep_trace=True, verbosity=0, print_iter=10):
+        """pmf_fit_lbfgs (fit_lbfgs!, src/fit_lbfgs.jl:170-243).  Returns the result fields and the three traces."""
+        o = LbfgsOpts(int(m), int(max_iter), int(backtrack_max_iter), int(keep_trace), int(verbosity), int(print_iter),
+                      float(rel_tol), float(abs_tol), float(backtrack_shrinkage), float(c1), float(sy_min))
+        cap = max(int(max_iter), 1)
+        loss, trials, flags = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        r = LbfgsResult()
+        r.trace_cap = cap
+        r.loss_trace = loss.ctypes.data_as(C.POINTER(C.c_double))
+        r.trial_trace = trials.ctypes.data_as(C.POINTER(C.c_int32))
+        r.flag_trace = flags.ctypes.data_as(C.POINTER(C.c_int32))
+        self._chk(self.lib.pmf_fit_lbfgs(self._h, C.byref(o), C.byref(r)))
+        n = r.n_trace
+        return {"term_code": TERM[r.term_code], "iters": r.iters, "loss": loss[:n].copy(), "trials": trials[:n].copy(),
+                "flags": flags[:n].copy(), "final_loss": r.final_loss, "loss_evals": r.loss_evals,
+                "grad_evals": r.grad_evals, "resets": r.resets, "seconds": r.seconds}
+
+    def debug_lbfgs_direction(self, s_pairs, y_pairs, g):
+        """pmf_debug_lbfgs_direction: s_pairs / y_pairs are lists (newest first) of (X-part K x M, Y-part K x N); g likewise
+        one such pair.  Returns p = (K x M, K x N)."""
+        n = len(s_pairs)
+        def stack(pairs, i, cols):
+            if not pairs:
+                return None
+            return np.ascontiguousarray(np.stack([np.asfortranarray(q[i], dtype=np.float32).ravel(order="F") for q in pairs]))
+        sX, sY, yX, yY = stack(s_pairs, 0, self.M), stack(s_pairs, 1, self.N), stack(y_pairs, 0, self.M), stack(y_pairs, 1, self.N)
+        gX, gY = _f32(g[0]), _f32(g[1])
+        pX = np.zeros((self.K, self.M), np.float32, order="F")
+        pY = np.zeros((self.K, self.N), np.float32, order="F")
+        self._chk(self.lib.pmf_debug_lbfgs_direction(self._h, n, _fp(sX), _fp(sY), _fp(yX), _fp(yY), _fp(gX), _fp(gY),
+                                                     _fp(pX), _fp(pY)))
+        return pX, pY
 
     def epoch_begin(self, o):
         self._chk(self.lib.pmf_epoch_begin(self._h, C.byref(o)))

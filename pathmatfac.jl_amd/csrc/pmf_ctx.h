@@ -4,6 +4,7 @@
 //   pmf_comm_fit.hip  cross-rank exchange (RCCL via dlopen / host-staged transport) and the epoch loop pmf_fit
 //   pmf_fsard.hip     the FeatureSetARD update_A! solver (ISTA on the device)
 //   pmf_netreg.hip    NetworkRegularizer (per-factor CG solve + sparse gradient) and the L1 / SelectiveL1 weights
+//   pmf_lbfgs.hip     L-BFGS over (X, Y): total gradient, history, two-loop recursion, backtracking (pmf_fit_lbfgs)
 #ifndef PMF_CTX_H
 #define PMF_CTX_H
 #include <hip/hip_runtime.h>
@@ -203,6 +204,7 @@ struct pmf_ctx {
   // largest dynamic-LDS size set so far per kernel ON THIS CONTEXT'S DEVICE (hipFuncSetAttribute is per device: a
   // process-wide cache would leave a second GPU's kernels without the attribute)
   PmfDynLds dyn_lds;
+  struct LbfgsState *lbfgs = nullptr;   // vectors and scalars of pmf_fit_lbfgs (pmf_lbfgs.hip), allocated on its first call
 };
 
 #define REG_SLOTS 1024
@@ -253,6 +255,35 @@ __device__ __forceinline__ double block_reduce_sum(double v, double *sh) {
   return s;  // valid on thread 0
 }
 
+// ---- the regularizer + optimizer step kernel's arguments (k_reg_step, pmf_hip.hip) and the per-entry value and gradient
+// of the smooth element-wise terms, shared with the total-gradient kernel of pmf_lbfgs.hip
+struct StepArgs {
+  float *p, *g, *acc, *mom;
+  const float *wq, *cq;          // quadratic regularizer (may be null)
+  const float *ard_alpha, *ard_beta;  // ARD-type regularizer (Y only; may be null)
+  float ard_scale;
+  int64_t n;   // elements
+  int Kp, K;   // leading dimension and number of live rows (Kp == K == 1 for vectors)
+  int opt_kind;
+  float lr, eps, b1, b2, c1, c2;  // c1 = 1 - beta1^t, c2 = 1 - beta2^t
+  int do_step;   // 0: only evaluate the regularizer loss (parameter frozen for stepping)
+  int use_reg;
+  double *reg_partial;  // [REG_SLOTS]
+};
+// quadratic : 0.5 w (p - c)^2, gradient w (p - c)
+__device__ __forceinline__ void pmf_reg_quad(float p, float w, float cq, float &g, double &lacc) {
+  const float d = p - cq;
+  const float gr = w * d;
+  lacc += 0.5 * (double)(gr * d);
+  g += gr;
+}
+// ARD-type  : scale (0.5 + alpha) log(1 + (0.5 / beta) p^2), gradient scale (alpha + 0.5) p / (b beta)
+__device__ __forceinline__ void pmf_reg_ard(float p, float be, float al, float scale, float &g, double &lacc) {
+  const float b = 1.f + (0.5f / be) * (p * p);
+  lacc += (double)(scale * (0.5f + al) * logf(b));
+  g += scale * ((al + 0.5f) * p / (b * be));
+}
+
 // ---- defined in pmf_hip.hip
 int ctx_bind(pmf_ctx *c);
 int ensure_dyn_lds(pmf_ctx *c, const void *kern, size_t lds);
@@ -270,6 +301,15 @@ int step_layers(pmf_ctx *c, const pmf_fit_opts *o, int *reg_count);
 // fixed-order reduction of the loss partial slabs into d_loss[which] for every bit `which` of mask (0 data term, 1 X reg,
 // 2 Y reg, 3 layer regs, 4 spare)
 int launch_loss_reduce(pmf_ctx *c, const RegCounts &rc, int mask);
+// the k_reg_step arguments of X (0) / Y (1) over the whole tensor, without optimizer or loss slab: its element-wise terms
+void step_args_xy(pmf_ctx *c, int which, StepArgs *s);
+// data loss + X regularizer + Y regularizer at the current parameters: out = {total, data, xreg, yreg}.  Always the exact
+// f32 data pass; writes no parameter, gradient or optimizer state (pmf_loss).
+int eval_full_loss(pmf_ctx *c, double out[4]);
+// the fused data pass with both gradients in the context's precision mode: grad(X), grad(Y) of the data term, on the stream
+int eval_data_grads(pmf_ctx *c);
+// ---- defined in pmf_lbfgs.hip
+void lbfgs_free(pmf_ctx *c);
 // ---- defined in pmf_netreg.hip
 void netreg_free(pmf_ctx *c, int which);   // drops the network term of X (0) / Y (1) and its state
 // evaluates the network term from the current parameter: u_k, its gradient buffer and its loss partials (appended to

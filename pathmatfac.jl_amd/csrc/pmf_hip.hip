@@ -189,19 +189,6 @@ __device__ __forceinline__ float pmf_d_get(const void *D, int64_t i, int64_t j, 
 }
 
 
-struct StepArgs {
-  float *p, *g, *acc, *mom;
-  const float *wq, *cq;          // quadratic regularizer (may be null)
-  const float *ard_alpha, *ard_beta;  // ARD-type regularizer (Y only; may be null)
-  float ard_scale;
-  int64_t n;   // elements
-  int Kp, K;   // leading dimension and number of live rows (Kp == K == 1 for vectors)
-  int opt_kind;
-  float lr, eps, b1, b2, c1, c2;  // c1 = 1 - beta1^t, c2 = 1 - beta2^t
-  int do_step;   // 0: only evaluate the regularizer loss (parameter frozen for stepping)
-  int use_reg;
-  double *reg_partial;  // [REG_SLOTS]
-};
 struct StepArgsGraph : StepArgs {   // k_reg_step<true>: the same, plus the pathway-graph terms (at least one of them set)
   const float *gpre;             // gradient of a term evaluated beforehand (NetworkRegularizer, pmf_netreg.hip; may be null)
   const float *wl1;              // dense L1 weights (L1Regularizer / SelectiveL1Reg; may be null)
@@ -229,19 +216,8 @@ __global__ __launch_bounds__(256) void k_reg_step(const std::conditional_t<GRAPH
     float p = a.p[e];
     float g = a.g[e];
     if (a.use_reg) {
-      if (a.wq) {
-        const float d = p - (a.cq ? a.cq[e] : 0.f);
-        const float gr = a.wq[e] * d;
-        lacc += 0.5 * (double)(gr * d);
-        g += gr;
-      }
-      if (a.ard_beta) {
-        const int64_t j = e / a.Kp;
-        const float be = a.ard_beta[e], al = a.ard_alpha[j];
-        const float b = 1.f + (0.5f / be) * (p * p);
-        lacc += (double)(a.ard_scale * (0.5f + al) * logf(b));
-        g += a.ard_scale * ((al + 0.5f) * p / (b * be));
-      }
+      if (a.wq) pmf_reg_quad(p, a.wq[e], a.cq ? a.cq[e] : 0.f, g, lacc);
+      if (a.ard_beta) pmf_reg_ard(p, a.ard_beta[e], a.ard_alpha[e / a.Kp], a.ard_scale, g, lacc);
       if constexpr (GRAPH) {
         if (a.gpre) g += a.gpre[e];
         if (a.wl1) {
@@ -682,6 +658,7 @@ extern "C" int pmf_destroy(pmf_ctx *c) {
   for (auto &b : c->P) param_free(b);
   netreg_free(c, 0);
   netreg_free(c, 1);
+  lbfgs_free(c);
   if (c->D) (void)hipFree(c->D);
   c->D = nullptr;
   dev_free(&c->tflags);
@@ -2064,6 +2041,14 @@ int step_param(pmf_ctx *c, int which, bool do_step, bool use_reg, int reg_slot, 
   // what a network term evaluated before the step has left of theirs
   return step_param_range(c, which, 0, c->P[which].n, do_step, use_reg, reg_slot, reg_count, reg_slot == 2 ? REG_SLOTS / 4 : REG_SLOTS - *reg_count, true);
 }
+void step_args_xy(pmf_ctx *c, int which, StepArgs *s) {
+  ParamBuf &b = c->P[which];
+  memset(s, 0, sizeof(*s));
+  s->p = b.p; s->g = b.g; s->wq = b.wq; s->cq = b.cq;
+  s->Kp = c->Kp; s->K = c->K; s->n = b.n;
+  if (which == 1 && c->has_ard) { s->ard_alpha = c->ard_alpha; s->ard_beta = c->ard_beta; s->ard_scale = c->ard_scale; }
+  s->use_reg = 1;
+}
 // layer l <-> param: 1 logsigma(2), 2 logdelta(4), 3 mu(3), 4 theta(5)
 int step_layers(pmf_ctx *c, const pmf_fit_opts *o, int *reg_count) {
   const int fl = o->frozen_layers, fr = o->frozen_regs;
@@ -2156,6 +2141,39 @@ extern "C" int pmf_epoch_loss(pmf_ctx *c, double *local_loss, double *shared_ter
   return 0;
 }
 
+
+// ---- full loss / data gradients at the current parameters (pmf_loss, pmf_fit_lbfgs)
+int eval_full_loss(pmf_ctx *c, double out[4]) {
+  if (c->net[0] || c->net[1])
+    return pmf_fail("pmf_loss: a network term is attached; evaluating it would move its warm-start state");
+  if (!c->prepared) PMFCHK(prepare(c));
+  PMFCHK(launch_fused(c, false, false));
+  RegCounts rc = {{0, 0, 0, 0}};
+  PMFCHK(step_param(c, 0, false, true, 0, &rc.c[0]));
+  PMFCHK(step_param(c, 1, false, true, 1, &rc.c[1]));
+  PMFCHK(launch_loss_reduce(c, rc, 0x7));
+  HIPCHK(hipMemcpyAsync(c->h_loss, c->d_loss, sizeof(double) * 3, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  harvest_events(c);
+  out[1] = c->h_loss[0]; out[2] = c->h_loss[1]; out[3] = c->h_loss[2];
+  out[0] = out[1] + out[2] + out[3];
+  return 0;
+}
+int eval_data_grads(pmf_ctx *c) {
+  if (!c->prepared) PMFCHK(prepare(c));
+  return launch_fused(c, true, true);
+}
+extern "C" int pmf_loss(pmf_ctx *c, double *total, double *data, double *xreg, double *yreg) {
+  PMFCHK(ctx_bind(c));
+  PMFCHK(check_ready(c));
+  double v[4];
+  PMFCHK(eval_full_loss(c, v));
+  if (total) *total = v[0];
+  if (data) *data = v[1];
+  if (xreg) *xreg = v[2];
+  if (yreg) *yreg = v[3];
+  return 0;
+}
 
 extern "C" int pmf_grad_device_ptr(pmf_ctx *c, int which, void **ptr, int64_t *n) {
   PMFCHK(ctx_bind(c));

@@ -78,12 +78,29 @@ def init_theta_(model, capacity=int(10e8), max_epochs=500, lr_theta=1.0, verbosi
 
 
 def init_factors_(model, verbosity=1, print_prefix="", history=None, lr=1.0, capacity=10 ** 8, max_epochs=1000,
-                  init_factors_method="adagrad", rel_tol=1e-5, abs_tol=1e-5, **kwargs):
-    """init_factors! (src/fit.jl:249-288), AdaGrad branch (the L-BFGS branch is out of scope).
-    `rel_tol` / `abs_tol` are captured here as in the reference (:256-257) and belong to the L-BFGS branch only: the
-    AdaGrad branch (:280-284) does not pass them on, so that stage stops on MF.fit!'s own default tolerances."""
+                  init_factors_method="adagrad", rel_tol=1e-5, abs_tol=1e-5, backtrack_shrinkage=0.8, device=0, **kwargs):
+    """init_factors! (src/fit.jl:249-288).  `rel_tol` / `abs_tol` / `backtrack_shrinkage` are captured here as in the
+    reference (:256-258) and belong to the L-BFGS branch only: the AdaGrad branch (:280-284) does not pass them on, so that
+    stage stops on MF.fit!'s own default tolerances.  The L-BFGS branch (:261-276) fits X and Y under 0.05 * sum(x .* x) in
+    place of X_reg / Y_reg -- the library's L2 term 0.5 * w * sum(x^2) with w = 0.1 in every row -- and takes neither `lr`
+    nor `capacity`."""
+    if init_factors_method == "lbfgs":
+        from .fit_lbfgs import fit_lbfgs_
+        if verbosity > 0:
+            print(f"{print_prefix}Initializing linear factors X,Y via L-BFGS...")
+        mf = model.matfac
+        orig_X_reg, orig_Y_reg = mf.X_reg, mf.Y_reg
+        mf.X_reg = L2Regularizer(np.full(mf.K, 0.1, np.float32))
+        mf.Y_reg = L2Regularizer(np.full(mf.K, 0.1, np.float32))
+        try:
+            fit_lbfgs_(mf, model.device_context(device), verbosity=verbosity, print_prefix=print_prefix + "    ",
+                       max_iter=max_epochs, rel_tol=rel_tol, abs_tol=abs_tol, backtrack_shrinkage=backtrack_shrinkage)
+        finally:
+            mf.X_reg, mf.Y_reg = orig_X_reg, orig_Y_reg
+        history_(history, name="init_factors_lbfgs")
+        return
     if init_factors_method != "adagrad":
-        raise NotImplementedError("init_factors_method='lbfgs' is out of scope (src/fit_lbfgs.jl)")
+        raise ValueError(f"init_factors_method={init_factors_method!r}: 'adagrad' or 'lbfgs' (src/fit.jl:261-286)")
     mf_fit_adapt_lr_(model, capacity=capacity, update_X=True, update_Y=True, lr=lr, min_lr=0.05,
                      max_epochs=max_epochs, verbosity=verbosity, print_prefix=print_prefix + "    ",
                      history=history, **kwargs)

@@ -34,6 +34,17 @@ mutable struct FitResult  # pmf_fit_result
     final_loss::Cdouble; loss_trace::Ptr{Cdouble}; seconds::Cdouble
 end
 
+struct LbfgsOpts          # pmf_lbfgs_opts
+    m::Cint; max_iter::Cint; backtrack_max_iter::Cint; keep_trace::Cint; verbosity::Cint; print_iter::Cint
+    rel_tol::Cdouble; abs_tol::Cdouble; backtrack_shrinkage::Cdouble; c1::Cdouble; sy_min::Cdouble
+end
+
+mutable struct LbfgsResult  # pmf_lbfgs_result
+    term_code::Cint; iters::Cint; loss_evals::Cint; grad_evals::Cint; resets::Cint; n_trace::Cint; trace_cap::Cint
+    reserved::Cint; final_loss::Cdouble; seconds::Cdouble
+    loss_trace::Ptr{Cdouble}; trial_trace::Ptr{Cint}; flag_trace::Ptr{Cint}
+end
+
 lasterr() = unsafe_string(ccall((:pmf_last_error, LIB[]), Cstring, ()))
 chk(rc::Integer) = rc == 0 ? nothing : error("libpmf_hip: " * lasterr())
 f32(a) = convert(Array{Float32}, a)
@@ -263,6 +274,36 @@ function mf_fit!(model::PM.PathMatFacModel; update_X=false, update_Y=false, upda
     unmarshal!(ctx, mf, update_X, update_Y, update_col_layers)
     return Dict("term_code" => TERM_CODES[res.term_code + 1], "epochs" => Int(res.epochs),
                 "loss" => trace[1:res.n_trace], "total_loss" => res.final_loss)
+end
+
+"""Replacement for PathMatFac.fit_lbfgs! (src/fit_lbfgs.jl:170-243) on the model's device context: L-BFGS over X and Y
+(pmf_fit_lbfgs; DESIGN.md section 2, "Deviation 2 / L-BFGS").  X_reg / Y_reg are marshalled as in mf_fit!, where a plain
+function counts as `x -> 0`: the closures init_factors! swaps in (src/fit.jl:266-267, 0.05 * sum(x .* x)) cannot be read
+from outside, so its L-BFGS branch passes `factor_l2 = 0.1f0` instead, the weight of the library's L2 term
+0.5 * w * sum(x .* x) that equals them.  Returns a Dict like mf_fit!'s."""
+function fit_lbfgs!(model::PM.PathMatFacModel; m=10, max_iter=1000, rel_tol=1e-9, abs_tol=1e-6, backtrack_shrinkage=0.8,
+                    print_prefix="", print_iter=10, verbosity=1, factor_l2=nothing, kwargs...)
+    ctx = context!(model)
+    mf = model.matfac
+    marshal!(ctx, mf)
+    if factor_l2 !== nothing
+        w = fill(Float32(factor_l2), size(mf.X, 1))
+        chk(ccall((:pmf_clear_xreg, LIB[]), Cint, (Ptr{Cvoid},), ctx))
+        chk(ccall((:pmf_clear_yreg, LIB[]), Cint, (Ptr{Cvoid},), ctx))
+        GC.@preserve w begin
+            chk(ccall((:pmf_add_xreg_l2, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Cfloat), ctx, w, 1f0))
+            chk(ccall((:pmf_add_yreg_l2, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Cfloat), ctx, w, 1f0))
+        end
+    end
+    opts = LbfgsOpts(m, max_iter, 100, 1, verbosity, print_iter, rel_tol, abs_tol, backtrack_shrinkage, 1e-4, 1e-4)
+    cap = max(max_iter, 1)
+    loss, trials, flags = zeros(Cdouble, cap), zeros(Cint, cap), zeros(Cint, cap)
+    res = LbfgsResult(0, 0, 0, 0, 0, 0, cap, 0, 0.0, 0.0, pointer(loss), pointer(trials), pointer(flags))
+    GC.@preserve loss trials flags chk(ccall((:pmf_fit_lbfgs, LIB[]), Cint, (Ptr{Cvoid}, Ref{LbfgsOpts}, Ref{LbfgsResult}),
+                                             ctx, opts, res))
+    unmarshal!(ctx, mf, true, true, false)
+    return Dict("term_code" => TERM_CODES[res.term_code + 1], "iters" => Int(res.iters), "loss" => loss[1:res.n_trace],
+                "trials" => trials[1:res.n_trace], "flags" => flags[1:res.n_trace], "total_loss" => res.final_loss)
 end
 
 function unmarshal!(ctx, mf, update_X, update_Y, update_col_layers)
