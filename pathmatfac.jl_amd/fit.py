@@ -122,10 +122,28 @@ from .util import ids_to_ind_mat, ids_to_ranges  # noqa: E402
 import copy  # noqa: E402
 
 
+_STAT_KEYS = ("n", "sum", "sumsq", "sqerr", "ssq_grad")
+
+
 def _device_stats(model, use_factors, device=0):
+    """pmf_stats on the model's rows.  Row-sharded: every array is converted to float64, packed into one buffer and summed
+    over the ranks with ONE collective per call; the sums come back as float64, identical on every rank."""
     ctx = model.device_context(device)
     MF.marshal(model.matfac, ctx, with_xreg=False, with_yreg=False)
-    return ctx.stats(use_factors)
+    st = ctx.stats(use_factors)
+    if not model.sharded:
+        return st
+    parts = [st[k] for k in _STAT_KEYS] + list(st["batch_count"]) + list(st["batch_sqerr"])
+    buf = np.concatenate([np.asarray(a, dtype=np.float64).ravel() for a in parts])
+    model.allreduce(buf)
+    out, off = [], 0
+    for a in parts:
+        out.append(buf[off:off + a.size].reshape(a.shape).copy())
+        off += a.size
+    nv = len(st["batch_count"])
+    red = dict(zip(_STAT_KEYS, out))
+    red["batch_count"], red["batch_sqerr"] = out[len(_STAT_KEYS):len(_STAT_KEYS) + nv], out[len(_STAT_KEYS) + nv:]
+    return red
 
 
 def init_mu_(model, capacity=int(10e8), lr_mu=0.1, max_epochs=500, verbosity=1, print_prefix="", history=None,
@@ -171,7 +189,7 @@ def init_logsigma_(model, capacity=int(10e8), history=None):
 
 def reweight_col_losses_(model, capacity=int(10e8), history=None):
     """reweight_col_losses! (src/fit.jl:151-187): weights <- 1 / (rms column gradient * sigma), non-finite -> 1."""
-    M, N = model.data.shape
+    M, N = model.M_total, model.data.shape[1]                                 # (row-sharded: all samples, not the local ones)
     nm = model.matfac.noise_model
     nm.set_weight_(np.ones(N, np.float32))                                    # :157
     st = _device_stats(model, use_factors=False)                              # X, Y zeroed (:160-163)
@@ -188,7 +206,7 @@ def construct_minimal_regularizer(model, capacity=10 ** 8):
     """src/regularizers.jl:750-774: GroupRegularizer over the noise-model column ranges, weight
     K*mean(sigma^2) / (sum(nanvar .* nonnan) / M) per group (nanvar floored at 1/M)."""
     mf = model.matfac
-    K, M = mf.X.shape
+    K, M = mf.X.shape[0], model.M_total
     st = _device_stats(model, use_factors=False)
     n = st["n"].astype(np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -265,6 +283,17 @@ def theta_delta_em(model, delta2, sigma2, update_priors=True, batch_em_max_iter=
     return [v.copy() for v in theta.values], delta2
 
 
+def _condition_ind_mat(model):
+    """ids_to_ind_mat of the sample conditions (:397).  Row-sharded: the rows are the local samples, the columns every
+    GLOBAL condition in global order -- the regression's Y (one row per condition) is replicated."""
+    if not model.sharded:
+        return ids_to_ind_mat(model.sample_conditions)
+    col = {c: j for j, c in enumerate(model.conditions)}
+    mat = np.zeros((len(model.sample_conditions), len(col)), dtype=bool)
+    mat[np.arange(mat.shape[0]), [col[c] for c in model.sample_conditions]] = True
+    return mat
+
+
 def init_batch_effects_(model, capacity=10 ** 8, max_epochs=5000, lr_regress=0.25, lr_mu=0.1, lr_theta=1.0,
                         batch_method="EM", batch_em_rtol=1e-8, batch_em_max_iter=100, verbosity=1, print_prefix="",
                         history=None, **kwargs):
@@ -274,7 +303,7 @@ def init_batch_effects_(model, capacity=10 ** 8, max_epochs=5000, lr_regress=0.2
     work = copy.deepcopy(orig)                                                           # :393
     model.matfac = work
     try:
-        cond = ids_to_ind_mat(model.sample_conditions)                                   # :397
+        cond = _condition_ind_mat(model)                                                 # :397
         M, Kc = cond.shape
         N = work.Y.shape[1]
         work.X = np.asfortranarray(cond.T.astype(np.float32))                            # :400-401
@@ -320,9 +349,16 @@ def rms(X, axis):
 
 
 def whiten_(model):
-    """whiten! (src/fit.jl:504-527)."""
+    """whiten! (src/fit.jl:504-527).  Row-sharded: the K row sums of squares of X are summed over the ranks and divided by
+    M_total; everything after that works on replicated arrays."""
     mf = model.matfac
-    X_rms = rms(mf.X.astype(np.float64), 1)
+    if model.sharded:
+        X64 = mf.X.astype(np.float64)
+        ssq = np.ascontiguousarray(np.sum(X64 * X64, axis=1))
+        model.allreduce(ssq)
+        X_rms = np.sqrt(ssq / model.M_total)[:, None]
+    else:
+        X_rms = rms(mf.X.astype(np.float64), 1)
     mf.X[...] = mf.X / X_rms
     mf.Y[...] = mf.Y * X_rms
     ls = mf.col_transform.unwrapped(1).logsigma
@@ -338,10 +374,23 @@ def whiten_(model):
 
 
 def rotate_by_svd_(model):
-    """rotate_by_svd! (src/fit.jl:530-543): Y <- S*Vt, X' <- X' * U."""
+    """rotate_by_svd! (src/fit.jl:530-543): Y <- S*Vt, X' <- X' * U.  Row-sharded: Y is replicated, so every rank could
+    factor it, but two LAPACK builds or thread counts need not return the same bits: U and S*Vt are the root's, handed to
+    every rank in one collective of K * (K + N) doubles; X_local <- U' X_local."""
     mf = model.matfac
-    U, s, Vt = np.linalg.svd(mf.Y.astype(np.float64), full_matrices=False)
-    mf.Y[...] = s[:, None] * Vt
+    K, N = mf.Y.shape
+    if model.sharded:
+        buf = np.zeros(K * K + K * N)
+        if model.is_root:
+            U, s, Vt = np.linalg.svd(mf.Y.astype(np.float64), full_matrices=False)
+            buf[:K * K] = U.ravel()
+            buf[K * K:] = (s[:, None] * Vt).ravel()
+        model.bcast_root_(buf)
+        U = buf[:K * K].reshape(K, K)
+        mf.Y[...] = buf[K * K:].reshape(K, N)
+    else:
+        U, s, Vt = np.linalg.svd(mf.Y.astype(np.float64), full_matrices=False)
+        mf.Y[...] = s[:, None] * Vt
     mf.X[...] = (mf.X.astype(np.float64).T @ U).T
 
 
@@ -380,9 +429,45 @@ def _reorder_reg(reg, p):  # reorder_reg! (regularizers.jl:5, 53-55, 449-452; fe
             _reorder_reg(r, p)
 
 
-def reweight_eb_(reg, P, mixture_p=1.0):
+def _lambda_max_sharded(model, grams):
+    """Largest eigenvalue of each of the K x K Gram matrices in `grams` (G x K x K, this rank's part) summed over the
+    ranks: one collective for the Grams; the eigenvalues are the root's (a second, G doubles long)."""
+    grams = np.ascontiguousarray(grams, dtype=np.float64)
+    model.allreduce(grams)
+    lam = np.zeros(grams.shape[0])
+    if model.is_root:
+        lam[...] = [np.linalg.eigvalsh(G)[-1] for G in grams]
+    return model.bcast_root_(lam)
+
+
+def _reweight_eb_sharded_(model, reg, X, mixture_p):
+    """reweight_eb! on the X regularizer of a row-sharded model: the largest squared singular value of a block of X is
+    the largest eigenvalue of its Gram matrix X_g X_g', which sums over the row shards."""
+    X64 = np.asarray(X, dtype=np.float64)
+    K = X64.shape[0]
+    if isinstance(reg, L2Regularizer):
+        lam = _lambda_max_sharded(model, (X64 @ X64.T)[None])
+        reg.weights[...] = mixture_p / lam[0]
+    elif isinstance(reg, GroupRegularizer):
+        grams = np.zeros((len(reg.group_idx), K, K))
+        for i, a, b in reg.local_groups():                      # a group without local rows contributes zeros
+            grams[i] = X64[:, a - 1:b] @ X64[:, a - 1:b].T
+        lam = _lambda_max_sharded(model, grams)
+        reg.group_weights = tuple(np.full(K, mixture_p / l, dtype=np.float32) for l in lam)
+    elif isinstance(reg, _R.CompositeRegularizer):
+        for r, p in zip(reg.regularizers, reg.mixture_p):
+            _reweight_eb_sharded_(model, r, X, p * mixture_p)
+    elif not isinstance(reg, ZeroReg):
+        raise NotImplementedError(f"reweight_eb_ of {type(reg).__name__} on X: rows are sharded and only L2Regularizer, "
+                                  "GroupRegularizer and their composites have a sharded update")
+
+
+def reweight_eb_(reg, P, mixture_p=1.0, model=None):
     """reweight_eb! for the regularizers in scope (regularizers.jl:39-47, 406-420, 588-609, 634-638): weights
-    <- mixture_p / (largest squared singular value) of the (group's) parameter block."""
+    <- mixture_p / (largest squared singular value) of the (group's) parameter block.  `model`: the model whose X
+    regularizer `reg` is, P being its (local) X; only a row-sharded model changes the path (_reweight_eb_sharded_)."""
+    if model is not None and model.sharded:
+        return _reweight_eb_sharded_(model, reg, P, mixture_p)
     if isinstance(reg, L2Regularizer):
         s = np.linalg.svd(P.astype(np.float64), compute_uv=False)
         reg.weights[...] = mixture_p / s[0] ** 2
@@ -503,7 +588,7 @@ def fit_ard_(model, max_epochs=1000, capacity=10 ** 8, verbosity=1, print_prefix
                print_prefix=n_pref, batch_method=batch_method, max_epochs=max_epochs, capacity=capacity,
                history=history, lr=lr, **kwargs)                              # :773-787
     mf.X_reg = orig_X_reg
-    reweight_eb_(mf.X_reg, mf.X)                                              # :791-792
+    reweight_eb_(mf.X_reg, mf.X, model=model)                                 # :791-792
     mf.Y_reg = orig_ard
     reweight_eb_(mf.Y_reg, mf.Y)                                              # :793-794
     reweight_col_losses_(model, capacity=capacity)                            # :797
@@ -542,7 +627,7 @@ def basic_fit_reg_weight_eb_(model, capacity=int(10e8), lr=1.0, max_epochs=1000,
     mf.X_reg, mf.Y_reg = orig_X_reg, orig_Y_reg
     if isinstance(sr, SequenceReg):
         reweight_eb_(sr, mf.col_transform)                                     # :712
-    reweight_eb_(mf.X_reg, mf.X)                                               # :713
+    reweight_eb_(mf.X_reg, mf.X, model=model)                                  # :713
     reweight_eb_(mf.Y_reg, mf.Y)                                               # :714
     history_(history, name="reweight_eb")
     basic_fit_(model, reweight_losses=True, fit_factors=True, verbosity=verbosity, print_prefix=n_pref,

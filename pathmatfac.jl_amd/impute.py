@@ -22,7 +22,8 @@ def impute(model, include_batch_effects=False, link=False, keep_observed=False, 
 
     link=True returns Z itself; keep_observed=True returns the observed entries of model.data and fills only the missing
     ones.  rows: a range or (start, stop) pair of 0-based rows, stop exclusive (default: all M); the result is
-    len(rows) x N float32.  The device computes blocks of capacity // N rows, so a caller bounds host memory with `rows`."""
+    len(rows) x N float32.  The device computes blocks of capacity // N rows, so a caller bounds host memory with `rows`.
+    On a row-sharded model this is per rank: the rows are the local ones and nothing is exchanged."""
     ctx = _context(model, device)
     M, N = ctx.M, ctx.N
     if rows is None:
@@ -45,7 +46,7 @@ def impute(model, include_batch_effects=False, link=False, keep_observed=False, 
 
 def impute_entries(model, rows, cols, include_batch_effects=False, link=False, device=0):
     """The predictions at the listed entries (0-based numpy indices; duplicates are legal): held-out scoring without an
-    M x N temporary."""
+    M x N temporary.  On a row-sharded model `rows` index the local rows of the calling rank."""
     ctx = _context(model, device)
     r = np.asarray(rows, dtype=np.int64).ravel() + 1
     c = np.asarray(cols, dtype=np.int64).ravel() + 1

@@ -36,13 +36,16 @@ class CompositeNoise:
 
 class MatFacModel:
     """MatFacModel(M, N, K, feature_distributions; col_transform, X_reg, Y_reg, col_transform_reg) (src/model.jl:69-72).
-    X is K x M, Y is K x N (column-major semantics; stored as Fortran-ordered float32)."""
+    X is K x M, Y is K x N (column-major semantics; stored as Fortran-ordered float32).
+    `row_shard` = (lo, hi, M_total) with M = hi - lo: X is drawn for all M_total samples and columns lo:hi are kept, so
+    that the shards of one seed concatenate to the unsharded X and the draw of Y that follows is the same on every rank."""
 
     def __init__(self, M, N, K, feature_distributions, col_transform=None, X_reg=None, Y_reg=None,
-                 col_transform_reg=None, rng=None):
+                 col_transform_reg=None, rng=None, row_shard=None):
         rng = rng or np.random.default_rng()
+        lo, hi, M_total = (0, M, M) if row_shard is None else row_shard
         # MatFac's own initialisation is not visible (un-vendored); self-specified: N(0,1)/sqrt(K)
-        self.X = np.asfortranarray((rng.standard_normal((K, M)) / np.sqrt(K)).astype(np.float32))
+        self.X = np.asfortranarray((rng.standard_normal((K, M_total)) / np.sqrt(K)).astype(np.float32)[:, lo:hi])
         self.Y = np.asfortranarray((rng.standard_normal((K, N)) / np.sqrt(K)).astype(np.float32))
         self.col_transform = col_transform
         self.noise_model = CompositeNoise(feature_distributions)

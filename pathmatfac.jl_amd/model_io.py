@@ -25,14 +25,21 @@ def _strs(v):
 
 
 def model_to_dict(model):
-    """The datasets of bson_to_hdf.jl's write_model_to_hdf, keyed by their HDF5 paths."""
+    """The datasets of bson_to_hdf.jl's write_model_to_hdf, keyed by their HDF5 paths.
+    Row-sharded model: "X", "sample_ids" and "sample_conditions" are those of ALL samples -- X is gathered
+    (parallel.gather_factors), which is a collective: every rank must make this call, whatever it does with the result."""
+    from .parallel import gather_factors
     mf = model.matfac
     ct = mf.col_transform
+    sharded = getattr(model, "sharded", False)
+    sample_ids = model.sample_ids_total if sharded else model.sample_ids
+    sample_conditions = model.sample_conditions_total if sharded else model.sample_conditions
     d = {
         "feature_ids": _strs(model.feature_ids), "feature_views": _strs(model.feature_views),          # :28-29
-        "sample_ids": _strs(model.sample_ids), "sample_conditions": _strs(model.sample_conditions),    # :30-31
+        "sample_ids": _strs(sample_ids), "sample_conditions": _strs(sample_conditions),                # :30-31
         "data_idx": np.asarray(model.data_idx, dtype=np.int64),                                        # :32
-        "X": np.asarray(mf.X, np.float32), "Y": np.asarray(mf.Y, np.float32),                          # :36-37
+        "X": gather_factors(model) if sharded else np.asarray(mf.X, np.float32),                       # :36
+        "Y": np.asarray(mf.Y, np.float32),                                                             # :37
         "logsigma": np.asarray(ct.unwrapped(1).logsigma, np.float32),                                  # :38
         "mu": np.asarray(ct.unwrapped(3).mu, np.float32),                                              # :39
     }
@@ -55,6 +62,8 @@ def model_to_dict(model):
 
 
 def save_params_npz(model, path, layout="h5py"):
+    """Writes model_to_dict(model).  On a row-sharded model every rank must call this (the gather of X is a collective) and
+    every call writes the same complete file: give rank 0 the real path and the other ranks a scratch one or os.devnull."""
     if layout not in ("h5py", "julia"):
         raise ValueError("layout must be 'h5py' or 'julia'")
     d = model_to_dict(model)

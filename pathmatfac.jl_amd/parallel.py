@@ -28,6 +28,20 @@ def shard_rows(M, world_size, rank):
     return lo, hi
 
 
+def gather_factors(model):
+    """The full K x M_total X of a row-sharded model, on every rank: each rank writes its columns into zeros and one sum
+    over the ranks (model.allreduce, K * M_total doubles) combines them -- x + 0 is exact, so the columns arrive with
+    their bits.  Collective: every rank calls it.  A model that is not sharded returns a copy of its X."""
+    X = model.matfac.X
+    if not model.sharded:
+        return np.array(X, dtype=np.float32, order="F")
+    lo, hi, M_total = model.row_shard
+    full = np.zeros((M_total, X.shape[0]))           # sample-major, so that this rank's columns are one contiguous run
+    full[lo:hi] = X.T
+    model.allreduce(full)
+    return np.asfortranarray(full.T.astype(np.float32))
+
+
 class _DevPtr:
     """Zero-copy view of a device buffer owned by libpmf_hip.so as a torch tensor (CUDA array interface)."""
 

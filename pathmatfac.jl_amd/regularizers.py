@@ -118,6 +118,8 @@ class NetworkRegularizer:  # regularizers.jl:169-338
 
 
 class GroupRegularizer:  # regularizers.jl:345-359
+    row_shard = None    # (lo, hi), 0-based half-open: on X of a row-sharded model the groups stay global (model.py)
+
     def __init__(self, group_labels=None, weight=1.0, K=1, group_idx=None, group_weights=None, labels=None):
         if group_idx is not None:
             self.group_labels = list(labels) if labels is not None else list(range(len(group_idx)))
@@ -128,8 +130,18 @@ class GroupRegularizer:  # regularizers.jl:345-359
             self.group_idx = tuple(ids_to_ranges(group_labels))
             self.group_weights = tuple(np.full(K, weight, dtype=np.float32) for _ in self.group_labels)
 
+    def local_groups(self):
+        """[(group index, start1, stop1)] in LOCAL rows: the non-empty intersections of the groups with the shard (every
+        group, unchanged, without one).  A group that straddles a shard boundary is one group with a part on each side."""
+        if self.row_shard is None:
+            return [(i, g.start, g.stop) for i, g in enumerate(self.group_idx)]
+        lo, hi = self.row_shard
+        parts = [(i, max(g.start, lo + 1) - lo, min(g.stop, hi) - lo) for i, g in enumerate(self.group_idx)]
+        return [(i, a, b) for i, a, b in parts if b >= a]
+
     def add_to(self, ctx, which, p=1.0):
-        ctx.add_reg_group(which, [(g.start, g.stop) for g in self.group_idx], np.stack(self.group_weights), p)
+        loc = self.local_groups()
+        ctx.add_reg_group(which, [(a, b) for _, a, b in loc], np.stack([self.group_weights[i] for i, _, _ in loc]), p)
 
 
 class ARDRegularizer:  # regularizers.jl:526-543

@@ -13,7 +13,9 @@ from .util import keymatch
 def transform(model, D, use_gpu=True, feature_ids=None, sample_ids=None, verbosity=1, print_prefix="",
               max_epochs=1000, lr=1.0, capacity=10 ** 8, **fit_kwargs):
     """transform(model, D; ...) (transform.jl:6-106).  Returns a new PathMatFacModel whose matfac.X (K x M_new)
-    holds the embedding.  `use_gpu` is accepted for API compatibility: the fit always runs on the GPU."""
+    holds the embedding.  `use_gpu` is accepted for API compatibility: the fit always runs on the GPU.
+    Only Y and the column layers of `model` are read and they are replicated, so with a row-sharded model this stays per
+    rank: each rank embeds the samples it is given, on its own device, without any exchange."""
     K, N = model.matfac.Y.shape
     D = np.asarray(D, dtype=np.float32)
     M_new, N_new = D.shape
