@@ -341,6 +341,18 @@ int pmf_debug_last_path(pmf_ctx *ctx, int *bmode, int *layer_path, int *slots);
  * 4 pmf_fused_sb4_kernel, 8 pmf_fused_sb8_kernel (split modes; tests assert that the intended variant really ran) */
 int pmf_debug_last_kernel(pmf_ctx *ctx, int *kernel);
 
+/* Diagnostics: per grow-only device buffer of the fused data pass (gx_part, gy_slabs, xsb, ysb, btd, colview, tflags,
+ * loss_partial, pm, row_slot), the bytes the kernels of the pass pmf_epoch_begin would run with these gradient flags address
+ * ("need", from the kernels' index expressions) and the bytes allocated ("capacity"); 0 / 0 for a buffer the pass does not
+ * use.  The call chooses the kernel family and prepares the buffers exactly as the pass would and launches no data pass.
+ * Every data pass makes the same comparison before its first launch and refuses to run when a need exceeds its capacity.
+ * names / need / capacity: arrays of n_max entries (PMF_PASS_EXTENTS_MAX is enough; names point to static strings), *n the
+ * entries filled.  cap_override (tests of the refusal; normally NULL): n_max capacities that replace the recorded ones
+ * where >= 0; the call then ends with the pass's own comparison and fails, naming the buffer, if it would be refused. */
+#define PMF_PASS_EXTENTS_MAX 16
+int pmf_debug_pass_extents(pmf_ctx *ctx, int update_X, int update_Y, const int64_t *cap_override, int n_max,
+                           const char **names, int64_t *need, int64_t *capacity, int *n);
+
 /* raw device addresses of the gradient buffers (float32) and their element counts, for in-place collectives */
 int pmf_grad_device_ptr(pmf_ctx *ctx, int which, void **ptr, int64_t *n_elements);
 /* copy a gradient of the last pmf_epoch_begin to the host in the reference's shape (tests / diagnostics) */

@@ -81,6 +81,7 @@ EXPORTS = [
     "pmf_set_precision", "pmf_get_precision",
     "pmf_comm_get_unique_id", "pmf_comm_init", "pmf_comm_init_host", "pmf_comm_destroy", "pmf_comm_set_chunks",
     "pmf_comm_info", "pmf_comm_allreduce", "pmf_get_opt_state", "pmf_fsard_update_A", "pmf_debug_last_path", "pmf_debug_last_kernel",
+    "pmf_debug_pass_extents",
     "pmf_add_xreg_network", "pmf_add_yreg_network", "pmf_get_reg_network_state", "pmf_add_xreg_l1", "pmf_add_yreg_l1",
     "pmf_impute", "pmf_impute_device", "pmf_impute_entries", "pmf_debug_impute_offset",
     "pmf_loss", "pmf_fit_lbfgs", "pmf_debug_lbfgs_direction",
@@ -638,6 +639,26 @@ class Context:
         k = C.c_int(0)
         self._chk(self.lib.pmf_debug_last_kernel(self._h, C.byref(k)))
         return k.value
+
+    def pass_extents(self, update_X=False, update_Y=False, capacity_override=None):
+        """pmf_debug_pass_extents: {buffer: dict(need=bytes, capacity=bytes)} of the data pass epoch_begin would run with
+        these flags, prepared but not launched.  capacity_override ({buffer: bytes}, tests of the refusal) replaces recorded
+        capacities and makes the call end with the pass's own check: PMFError naming the buffer if it would be refused."""
+        n_max = 16
+        names, n = (C.c_char_p * n_max)(), C.c_int(0)
+        need, cap = (C.c_int64 * n_max)(), (C.c_int64 * n_max)()
+        ov = None
+        if capacity_override is not None:
+            plain = self.pass_extents(update_X, update_Y)
+            unknown = set(capacity_override) - set(plain)
+            if unknown:
+                raise PMFError(f"pass_extents: unknown buffers {sorted(unknown)}")
+            ov = (C.c_int64 * n_max)(*([-1] * n_max))
+            for i, k in enumerate(plain):
+                ov[i] = int(capacity_override.get(k, -1))
+        self._chk(self.lib.pmf_debug_pass_extents(self._h, int(update_X), int(update_Y), ov, n_max, names, need, cap,
+                                                  C.byref(n)))
+        return {names[i].decode(): dict(need=need[i], capacity=cap[i]) for i in range(n.value)}
 
     def set_precision(self, mode):
         """'f32' (exact f32 MFMA, default) or 'bf16x3' (split-bf16 products where a kernel variant exists)."""

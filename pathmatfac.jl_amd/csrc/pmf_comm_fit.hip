@@ -364,7 +364,10 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
 
   bool in_flight = false;   // a data pass whose epoch has not been finished is enqueued
   if (o->epoch <= o->max_epochs) {
-    if (fused) PMFCHK(prepare_fused_pass(c, g, ux, uy));
+    if (fused) {
+      PMFCHK(prepare_fused_pass(c, g, ux, uy));
+      PMFCHK(guard_fused_pass(c, g, ux, uy));
+    }
     for (int s = 0; s < S; ++s) PMFCHK(pass_chunk(s));
     in_flight = true;
   }

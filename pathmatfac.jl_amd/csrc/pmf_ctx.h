@@ -43,6 +43,7 @@ struct PanelSlots {
   int BM = 0;
   bool ok = false;
   uint8_t *pm = nullptr, *row_slot = nullptr;
+  int64_t pm_cap = 0, row_slot_cap = 0;   // bytes allocated (fused_pass_extents)
 };
 
 // Cached work split of one column chunk of the fused data pass (see compute_work_split).
@@ -294,6 +295,15 @@ int epoch_layer_pass(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss);
 FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chunks);
 int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);
 int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool want_gy);
+// What the kernels of a prepared data pass address in every grow-only buffer against what is allocated, in bytes
+// ("Extents").  fused_pass_extents fills out[PMF_PASS_EXTENTS] and returns the count;
+// check_pass_extents fails on the first need > cap, naming the buffer; guard_fused_pass is both, between
+// prepare_fused_pass and the first launch of the pass: a few integer compares, no device work.
+struct PassExtent { const char *name; int64_t need, cap; };
+constexpr int PMF_PASS_EXTENTS = 10;
+int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy, PassExtent *out);
+int check_pass_extents(const PassExtent *e, int n);
+int guard_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);
 int step_param_range(pmf_ctx *c, int which, int64_t e0, int64_t n, bool do_step, bool use_reg, int reg_slot, int *reg_count,
                      int max_blocks, bool advance);
 int step_param(pmf_ctx *c, int which, bool do_step, bool use_reg, int reg_slot, int *reg_count);

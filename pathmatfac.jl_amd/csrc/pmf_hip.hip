@@ -1512,8 +1512,11 @@ static int ensure_panel_slots(pmf_ctx *c, int BM, PanelSlots **out) {
   ps.BM = BM;
   ps.serial = c->views_serial;
   if (ok) {
+    ps.pm_cap = ps.row_slot_cap = 0;
     PMFCHK(dev_alloc(&ps.pm, pm.size(), false));
     PMFCHK(dev_alloc(&ps.row_slot, std::max<size_t>(rs.size(), 1), false));
+    ps.pm_cap = (int64_t)pm.size();
+    ps.row_slot_cap = (int64_t)std::max<size_t>(rs.size(), 1);
     HIPCHK(hipMemcpy(ps.pm, pm.data(), pm.size(), hipMemcpyHostToDevice));
     if (!rs.empty()) HIPCHK(hipMemcpy(ps.row_slot, rs.data(), rs.size(), hipMemcpyHostToDevice));
   }
@@ -1722,13 +1725,21 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     PMFCHK(dev_alloc(&c->gx_idx, idx.size(), false));
     HIPCHK(hipMemcpy(c->gx_off, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->gx_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
-    const size_t need = (size_t)base * (size_t)f.BM() * (size_t)c->Kp;
+    c->gx_serial = serial_sum;
+  }
+  if (want_gx) {
+    // sized on EVERY pass, not with the slot map: a slot holds BM x Kp floats of the family that runs, and neither the family
+    // nor its panel height is in the work split's key (70 rows are one panel of 256 and of 512 rows alike: an exact f32 pass
+    // followed by an sb8 pass reuses the split and the slot map, and needs twice the bytes)
+    size_t pieces = 0;
+    for (int s = 0; s < g.S; ++s) pieces += c->splits[(size_t)s].piece_rp.size();
+    const size_t need = pieces * (size_t)f.BM() * (size_t)c->Kp;
     if (need > c->gx_part_cap) {
       dev_free(&c->gx_part);
+      c->gx_part_cap = 0;
       PMFCHK(dev_alloc(&c->gx_part, need, false));   // every slot is written whole by its piece before it is read
       c->gx_part_cap = need;
     }
-    c->gx_serial = serial_sum;
   }
   PMFCHK(ensure_tile_flags(c));
   if (f.img != IMG_NONE) {
@@ -1747,6 +1758,55 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     }
   }
   return 0;
+}
+
+// ---- extents: what a prepared pass addresses against what is allocated ("Extents")
+// Every need is taken from the index expressions of the kernels the pass launches (the fused kernel of g.fam, its operand
+// splits, k_gy_reduce, k_gx_reduce, k_loss_reduce) with the values launch_fused_chunk hands them, not from the sizing
+// formulas of prepare_fused_pass.  Bytes.
+int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy, PassExtent *out) {
+  const FusedFamily &f = *g.fam;
+  const int64_t Kp = c->Kp, Npad = g.n_ct_all * PMF_BN;
+  int64_t pieces = 0, grid_sum = 0, grid_top = 0;
+  for (int s = 0; s < g.S; ++s) {
+    const WorkSplit &ws = c->splits[(size_t)s];
+    pieces += (int64_t)ws.piece_rp.size();
+    grid_sum += ws.grid;
+    grid_top = std::max<int64_t>(grid_top, ws.grid);
+  }
+  const bool bt = g.bmode == 1;
+  int nbs_shift = 0;
+  while ((1 << nbs_shift) < c->nbs) ++nbs_shift;
+  const int64_t gx_slot_stride = (int64_t)f.BM() * Kp, slab_stride = Kp * c->N;
+  int n = 0;
+  // every piece stores its whole BM x Kp partial at slot * gx_slot_stride; the slots of all chunks are numbered through
+  out[n++] = {"gx_part", want_gx ? pieces * gx_slot_stride * 4 : 0, (int64_t)c->gx_part_cap * 4};
+  // workgroup wg < grid works in gy_slabs + wg * slab_stride: the live columns of its tiles, sb8 the whole last tile
+  out[n++] = {"gy_slabs", want_gy ? ((grid_top - 1) * slab_stride + (f.img == IMG_SB8 ? Npad * Kp : slab_stride)) * 4 : 0,
+              (int64_t)c->gy_slabs_cap * 4};
+  // row blocks < nRB (clamped); sb8 and its split whole panels of nblk blocks
+  out[n++] = {"xsb", f.img != IMG_NONE ? (c->nRB + f.nblk - 1) / f.nblk * f.nblk * f.xblk : 0, (int64_t)c->xsb_cap};
+  out[n++] = {"ysb", f.img != IMG_NONE ? g.n_ct_all * f.yblk : 0, (int64_t)c->ysb_cap};
+  // all 32 columns of every tile, the last slot of a column the identity
+  out[n++] = {"btd", bt ? (Npad << nbs_shift) * (int64_t)sizeof(float2) : 0, c->btd_cap * (int64_t)sizeof(float2)};
+  out[n++] = {"colview", bt ? Npad : 0, c->colview_cap};
+  out[n++] = {"tflags", g.n_ct_all * c->nRB * 4, c->tflags_cap * 4};
+  out[n++] = {"loss_partial", grid_sum * 8, c->loss_cap * 8};
+  out[n++] = {"pm", bt ? g.n_rp * c->n_bv * 16 : 0, bt ? g.ps->pm_cap : 0};
+  out[n++] = {"row_slot", bt ? (int64_t)c->n_bv * c->M : 0, bt ? g.ps->row_slot_cap : 0};
+  static_assert(PMF_PASS_EXTENTS == 10, "fused_pass_extents");
+  return n;
+}
+int check_pass_extents(const PassExtent *e, int n) {
+  for (int i = 0; i < n; ++i)
+    if (e[i].need > e[i].cap)
+      return pmf_fail("data pass refused: it addresses %lld bytes of %s, %lld are allocated", (long long)e[i].need, e[i].name,
+                      (long long)e[i].cap);
+  return 0;
+}
+int guard_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy) {
+  PassExtent e[PMF_PASS_EXTENTS];
+  return check_pass_extents(e, fused_pass_extents(c, g, want_gx, want_gy, e));
 }
 
 // split-bf16 operand images (k_sb_split): X once per pass, sigma*Y per chunk (its columns only: the Y step of a later
@@ -1875,6 +1935,7 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
 static int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy) {
   const FusedGeom g = fused_geometry(c, want_gx, want_gy, /*allow_chunks=*/c->n_chunks_req > 0);   // (chunks only on request)
   PMFCHK(prepare_fused_pass(c, g, want_gx, want_gy));
+  PMFCHK(guard_fused_pass(c, g, want_gx, want_gy));
   for (int s = 0; s < g.S; ++s) PMFCHK(launch_fused_chunk(c, g, s, want_gx, want_gy));
   return 0;
 }
@@ -2094,6 +2155,30 @@ extern "C" int pmf_debug_last_path(pmf_ctx *c, int *bmode, int *layer_path, int 
   if (layer_path) *layer_path = c->last_layer_path;
   if (slots) *slots = c->nbs;
   return 0;
+}
+
+// The extents of the data pass pmf_epoch_begin would run with these gradient flags (fused_pass_extents), after the same
+// geometry and preparation, without launching the pass.  cap_override (may be null; entries < 0 keep the recorded
+// capacity) replaces capacities in the report and makes the call end with the guard's own comparison on them.
+extern "C" int pmf_debug_pass_extents(pmf_ctx *c, int update_X, int update_Y, const int64_t *cap_override, int n_max,
+                                      const char **names, int64_t *need, int64_t *capacity, int *n_out) {
+  PMFCHK(ctx_bind(c));
+  PMFCHK(check_ready(c));
+  if (!c->prepared) PMFCHK(prepare(c));
+  const bool want_gx = update_X != 0, want_gy = update_Y != 0;
+  const FusedGeom g = fused_geometry(c, want_gx, want_gy, /*allow_chunks=*/c->n_chunks_req > 0);
+  PMFCHK(prepare_fused_pass(c, g, want_gx, want_gy));
+  PassExtent e[PMF_PASS_EXTENTS];
+  const int n = fused_pass_extents(c, g, want_gx, want_gy, e);
+  if (n_max < n) return pmf_fail("pmf_debug_pass_extents: room for %d entries, %d needed", n_max, n);
+  for (int i = 0; i < n; ++i) {
+    if (cap_override && cap_override[i] >= 0) e[i].cap = cap_override[i];
+    if (names) names[i] = e[i].name;
+    if (need) need[i] = e[i].need;
+    if (capacity) capacity[i] = e[i].cap;
+  }
+  if (n_out) *n_out = n;
+  return cap_override ? check_pass_extents(e, n) : 0;
 }
 
 extern "C" int pmf_epoch_begin(pmf_ctx *c, const pmf_fit_opts *o) {

@@ -85,6 +85,17 @@ function last_kernel(model)
     return Int(k[])
 end
 
+# bytes the data pass with these gradient flags addresses in each grow-only device buffer against the bytes allocated
+# (pmf_debug_pass_extents): Dict(name => (need = ..., capacity = ...)); the pass is prepared, not launched
+function pass_extents(model; update_X::Bool=false, update_Y::Bool=false)
+    nmax = 16
+    names = fill(Ptr{UInt8}(C_NULL), nmax); need = zeros(Int64, nmax); cap = zeros(Int64, nmax); n = Ref{Cint}(0)
+    chk(ccall((:pmf_debug_pass_extents, LIB[]), Cint,
+              (Ptr{Cvoid}, Cint, Cint, Ptr{Int64}, Cint, Ptr{Ptr{UInt8}}, Ptr{Int64}, Ptr{Int64}, Ref{Cint}),
+              context!(model), update_X, update_Y, C_NULL, nmax, names, need, cap, n))
+    return Dict(unsafe_string(names[i]) => (need = need[i], capacity = cap[i]) for i in 1:Int(n[]))
+end
+
 function comm_unique_id()
     id = zeros(UInt8, 128)
     GC.@preserve id chk(ccall((:pmf_comm_get_unique_id, LIB[]), Cint, (Ptr{UInt8},), id))
