@@ -407,6 +407,59 @@ int pmf_debug_impute_offset(int64_t row, int64_t col, int64_t ld, int64_t *offse
 int pmf_stats(pmf_ctx *ctx, int use_factors, float *col_n, float *col_sum, float *col_sumsq, float *col_sqerr,
               float *col_ssq_grad, float *batch_count, float *batch_sqerr);
 
+/* The closed-form stages between the gradient-descent stages, each as ONE call on the context's current parameters.  Every
+ * data pass is the column walk of pmf_stats; the statistics stay on the device, all arithmetic on them is float64 there, and a
+ * result is rounded to float32 where the parameter is float32.  Every sum has a fixed order: an output is bitwise the same run
+ * to run.  With a communicator of more than one rank (rows sharded) the statistics of a pass are widened to float64 and summed
+ * over the ranks in ONE collective per pass before any arithmetic, so every rank computes the same bits and takes the same
+ * stopping decision; a call that fails after its first launch drains both streams and marks the communicator unusable, as
+ * pmf_fit does.  No entry touches X, Y, a gradient, the optimizer state, Adam's powers or the learning rate.
+ *   pmf_stage_init_logsigma         : init_logsigma! (src/fit.jl:125-148).  Statistics with X'Y = 0;
+ *                                     logsigma[j] <- log(sqrt(sqerr[j] / n[j])), written into the context's logsigma (read it
+ *                                     with pmf_get_col_params).  IEEE results are kept: n = 0 gives NaN, a zero residual -inf.
+ *   pmf_stage_reweight_col_losses   : reweight_col_losses! (src/fit.jl:151-187).  The noise weights are set to 1 (:157), the
+ *                                     statistics taken with X'Y = 0 (:160-163), w[j] <- 1 / (sqrt(ssq_grad[j] / M_total) *
+ *                                     exp(logsigma[j])) (:170-176), non-finite -> 1 (:177), written into the context's noise
+ *                                     weights (:180).  M_total: all samples (the sum of the ranks' rows).
+ *   pmf_get_noise_weights           : the context's per-column noise weights (MF.set_weight!, src/fit.jl:157, 180), N floats.
+ *   pmf_stage_minimal_group_weights : construct_minimal_regularizer (src/regularizers.jl:750-774).  Per column range of the
+ *                                     noise model (pmf_set_noise), K * mean(sigma^2) / (sum_j var[j] n[j] / M_total) with var
+ *                                     the unbiased variance from sum / sumsq, non-finite -> 0, floored at 1 / M_total (:767).
+ *                                     Output only (one float per noise range): the host builds the regularizer.
+ *   pmf_stage_theta_delta_em        : theta_delta_em (src/fit.jl:326-375) with theta_mom / delta2_mom (:297-311).  theta is the
+ *                                     context's theta, updated in place (read it with pmf_get_batch_view); delta2 (in / out,
+ *                                     float64, flat over (view, column, batch) like theta) stays float64 on the device across
+ *                                     the iterations; sigma2 has N entries.  batch_count is taken once, before the loop (:332).
+ *                                     Per iteration: the theta update (:350, non-finite -> 0), one statistics pass with only the
+ *                                     batch outputs (:355), the delta2 update (:359; batch_sqerr non-finite -> 0, the result
+ *                                     non-finite -> 1), and ONE double read back, sum((theta - theta')^2) / sum(theta^2) (:363),
+ *                                     on which the host loop decides (diff < rtol, :367).  iters = iterations run; the diffs
+ *                                     go to a caller-owned buffer of diffs_cap entries (may be NULL), n_diffs written.
+ * Refused before anything is launched (the context stays usable): no data or factors; pmf_stage_theta_delta_em without batch
+ * views or with max_iter < 1; M_total below the context's row count; a NULL required pointer; more row batches per view than the
+ * statistics kernel's LDS holds (pmf_stats' own message). */
+typedef struct pmf_em_opts {
+  int32_t update_priors;   /* re-estimate the priors' moments every iteration ("EM") or only at the first ("EB"), src/fit.jl:343 */
+  int32_t max_iter;        /* batch_em_max_iter, >= 1 */
+  int32_t verbosity;       /* > 0: one line per iteration (:365) */
+  int32_t reserved;
+  double rtol;             /* batch_em_rtol */
+} pmf_em_opts;
+typedef struct pmf_em_result {
+  int32_t iters;
+  int32_t n_diffs;     /* entries written to diffs */
+  int32_t diffs_cap;   /* in: capacity of diffs */
+  int32_t reserved;
+  double *diffs;       /* in: host buffer (may be NULL) */
+  double seconds;
+} pmf_em_result;
+int pmf_stage_init_logsigma(pmf_ctx *ctx);
+int pmf_stage_reweight_col_losses(pmf_ctx *ctx, int64_t M_total);
+int pmf_get_noise_weights(pmf_ctx *ctx, float *w);
+int pmf_stage_minimal_group_weights(pmf_ctx *ctx, int64_t M_total, float *w_out);
+int pmf_stage_theta_delta_em(pmf_ctx *ctx, const pmf_em_opts *opts, const float *sigma2, double *delta2,
+                             pmf_em_result *result);
+
 /* FeatureSetARD outer loop, one view: update_A! / update_A_inner! (src/featureset_ard.jl:214-294) with ISTAOptimiser.update!
  * (src/optimizers.jl:26-62) and gamma_normal_loss + its pull-back (:154-186), run on the device against the context's
  * resident Y (columns col_start1:col_stop1 = the view's col_range).  A starts from 0 (:286); S is the view's L x N_v

@@ -52,6 +52,18 @@ class LbfgsResult(C.Structure):
                 ("trial_trace", C.POINTER(C.c_int32)), ("flag_trace", C.POINTER(C.c_int32))]
 
 
+class EmOpts(C.Structure):
+    """pmf_em_opts"""
+    _fields_ = [("update_priors", C.c_int32), ("max_iter", C.c_int32), ("verbosity", C.c_int32), ("reserved", C.c_int32),
+                ("rtol", C.c_double)]
+
+
+class EmResult(C.Structure):
+    """pmf_em_result"""
+    _fields_ = [("iters", C.c_int32), ("n_diffs", C.c_int32), ("diffs_cap", C.c_int32), ("reserved", C.c_int32),
+                ("diffs", C.POINTER(C.c_double)), ("seconds", C.c_double)]
+
+
 class Csr(C.Structure):
     """pmf_csr: one sparse block in 0-based CSR with sorted rows."""
     _fields_ = [("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rowptr", C.POINTER(C.c_int64)),
@@ -85,6 +97,8 @@ EXPORTS = [
     "pmf_add_xreg_network", "pmf_add_yreg_network", "pmf_get_reg_network_state", "pmf_add_xreg_l1", "pmf_add_yreg_l1",
     "pmf_impute", "pmf_impute_device", "pmf_impute_entries", "pmf_debug_impute_offset",
     "pmf_loss", "pmf_fit_lbfgs", "pmf_debug_lbfgs_direction",
+    "pmf_stage_init_logsigma", "pmf_stage_reweight_col_losses", "pmf_get_noise_weights", "pmf_stage_minimal_group_weights",
+    "pmf_stage_theta_delta_em",
 ]
 
 COMM_ID_BYTES = 128
@@ -175,6 +189,7 @@ class Context:
         self._chk(self.lib.pmf_create(int(device), C.byref(self._h)))
         self.M = self.N = self.K = 0
         self.view_shapes = []
+        self.n_noise_ranges = 0     # ranges of the last set_noise (the library forgets them with a new data shape: so does this)
 
     def _chk(self, rc):
         if rc != 0:
@@ -212,10 +227,14 @@ class Context:
     def set_data(self, D, store="f32"):
         """store = "bf16": the device copy of D is kept as bfloat16 (PMF_STORE_BF16; read by the split-bf16 data pass)."""
         D = _f32(D)
+        if D.shape != (self.M, self.N):
+            self.n_noise_ranges = 0
         self.M, self.N = D.shape
         self._chk(self.lib.pmf_set_data(self._h, _fp(D), C.c_int64(self.M), C.c_int64(self.N), STORE[store]))
 
     def set_data_device(self, ptr, M, N, store="f32"):
+        if (int(M), int(N)) != (self.M, self.N):
+            self.n_noise_ranges = 0
         self.M, self.N = int(M), int(N)
         self._chk(self.lib.pmf_set_data_device(self._h, C.c_void_p(ptr), C.c_int64(M), C.c_int64(N), STORE[store]))
 
@@ -285,6 +304,7 @@ class Context:
         w = None if weights is None else _f32(weights)
         self._chk(self.lib.pmf_set_noise(self._h, len(k), _i64p(s), _i64p(e), k.ctypes.data_as(C.POINTER(C.c_int32)),
                                          _fp(w)))
+        self.n_noise_ranges = len(k)
 
     # ---- regularizers
     def clear_xreg(self):
@@ -583,6 +603,52 @@ class Context:
             off += nb * nv
         out["batch_count"], out["batch_sqerr"] = cnt, sq
         return out
+
+    # ---- the closed-form stages in the library (pmf_stage_*): the statistics never leave the device
+    def stage_init_logsigma(self):
+        """pmf_stage_init_logsigma: logsigma <- log sqrt(sqerr / n) with X'Y = 0, on the device (get_col_params reads it)."""
+        self._chk(self.lib.pmf_stage_init_logsigma(self._h))
+
+    def stage_reweight_col_losses(self, M_total):
+        """pmf_stage_reweight_col_losses: the noise weights <- 1 / (rms column gradient * sigma) (get_noise_weights)."""
+        self._chk(self.lib.pmf_stage_reweight_col_losses(self._h, C.c_int64(int(M_total))))
+
+    def get_noise_weights(self):
+        w = np.zeros(self.N, np.float32)
+        self._chk(self.lib.pmf_get_noise_weights(self._h, _fp(w)))
+        return w
+
+    def stage_minimal_group_weights(self, M_total):
+        """pmf_stage_minimal_group_weights: one weight per column range of the noise model (as many as the last set_noise
+        on this data shape passed; without one the library refuses and writes nothing)."""
+        w = np.zeros(max(self.n_noise_ranges, 1), np.float32)
+        self._chk(self.lib.pmf_stage_minimal_group_weights(self._h, C.c_int64(int(M_total)), _fp(w)))
+        return w[:self.n_noise_ranges]
+
+    def stage_theta_delta_em(self, delta2, sigma2, update_priors=True, max_iter=100, rtol=1e-8, verbosity=0):
+        """pmf_stage_theta_delta_em on the context's theta.  delta2: per view an nb x N_v array (float64); sigma2: N values.
+        Returns dict(theta=[per view, float32], delta2=[per view, float64], diffs, iters, seconds)."""
+        if len(delta2) != len(self.view_shapes) or any(np.shape(d) != s for d, s in zip(delta2, self.view_shapes)):
+            raise PMFError(f"delta2 must hold one array per batch view, shaped {self.view_shapes}")
+        s2 = _f32(np.asarray(sigma2).ravel())
+        if s2.shape != (self.N,):
+            raise PMFError("sigma2 must have N entries")
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(d, np.float64).ravel(order="F") for d in delta2] or
+                                                   [np.zeros(1)]))
+        cap = max(int(max_iter), 1)
+        diffs = np.zeros(cap, np.float64)
+        o = EmOpts(int(bool(update_priors)), int(max_iter), int(verbosity), 0, float(rtol))
+        r = EmResult()
+        r.diffs_cap = cap
+        r.diffs = diffs.ctypes.data_as(C.POINTER(C.c_double))
+        self._chk(self.lib.pmf_stage_theta_delta_em(self._h, C.byref(o), _fp(s2), flat.ctypes.data_as(C.POINTER(C.c_double)),
+                                                    C.byref(r)))
+        out, off = [], 0
+        for nb, nv in self.view_shapes:
+            out.append(flat[off:off + nb * nv].reshape((nb, nv), order="F").copy())
+            off += nb * nv
+        theta = [self.get_batch_view(v)[1] for v in range(len(self.view_shapes))]
+        return dict(theta=theta, delta2=out, diffs=diffs[:r.n_diffs].copy(), iters=r.iters, seconds=r.seconds)
 
     # ---- multi-GPU
     def comm_init(self, rank, nranks, unique_id):

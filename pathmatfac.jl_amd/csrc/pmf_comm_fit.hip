@@ -184,7 +184,7 @@ extern "C" int pmf_comm_info(pmf_ctx *c, int *rank, int *nranks, int *transport,
 }
 
 // in-place sum over the ranks of `count` elements at device address p, ordered on the communication stream
-static int comm_allreduce(pmf_ctx *c, void *p, int64_t count, bool f64) {
+int comm_allreduce(pmf_ctx *c, void *p, int64_t count, bool f64) {
   Comm &m = c->comm;
   if (count <= 0) return 0;
   m.n_allreduce++;
@@ -287,7 +287,9 @@ extern "C" int pmf_fit(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
   // regularizers and refuses alike, before any collective of this fit is issued (the communicator stays usable).
   if (o->update_X && c->net[0] && comm_active(c) && c->comm.nranks > 1)
     return pmf_fail("a NetworkRegularizer on X is not supported with %d ranks: X is sharded by rows and the network couples rows across ranks (drop the term or fit on one rank)", c->comm.nranks);
-  const int rc = fit_loop(c, o, res);
+  return comm_error_exit(c, fit_loop(c, o, res));
+}
+int comm_error_exit(pmf_ctx *c, int rc) {
   if (rc < 0) {
     const std::string msg = pmf_last_error();
     (void)hipStreamSynchronize(c->stream);

@@ -5,6 +5,7 @@
 //   pmf_fsard.hip     the FeatureSetARD update_A! solver (ISTA on the device)
 //   pmf_netreg.hip    NetworkRegularizer (per-factor CG solve + sparse gradient) and the L1 / SelectiveL1 weights
 //   pmf_lbfgs.hip     L-BFGS over (X, Y): total gradient, history, two-loop recursion, backtracking (pmf_fit_lbfgs)
+//   pmf_stages.hip    the closed-form stages between the GD stages on the device statistics (pmf_stage_*)
 #ifndef PMF_CTX_H
 #define PMF_CTX_H
 #include <hip/hip_runtime.h>
@@ -164,6 +165,7 @@ struct pmf_ctx {
   // loss plumbing
   double *loss_partial = nullptr;
   std::vector<uint8_t> h_kind;    // host copy of the per-column noise kind (cost model of the work split)
+  std::vector<int64_t> noise_s1, noise_e1;   // the noise model's column ranges as pmf_set_noise got them (pmf_stage_minimal_group_weights)
   std::vector<WorkSplit> splits;  // cached work split of every column chunk of the fused pass (compute_work_split)
   int n_chunks_req = 0;           // column chunks per data pass: 0 = automatic (1 on one GPU; pmf_comm_set_chunks)
   float *gx_part = nullptr;       // [pieces][BM x Kp] per-piece partial sums of gX (fused kernel), summed by k_gx_reduce
@@ -318,6 +320,13 @@ void step_args_xy(pmf_ctx *c, int which, StepArgs *s);
 int eval_full_loss(pmf_ctx *c, double out[4]);
 // the fused data pass with both gradients in the context's precision mode: grad(X), grad(Y) of the data term, on the stream
 int eval_data_grads(pmf_ctx *c);
+// One k_stats pass over the local rows at the current parameters (prepare() + column walk + fixed-order sum of the block
+// rows), left ON THE DEVICE in the context's scratch buffer, valid until the next call that uses it: *cols = {n, sum, sumsq,
+// sqerr, ssq_grad}, N floats each (null unless want_cols), *batch = {count, sqerr}, flat like theta each (null unless
+// want_batch and the model has batch views).  No host synchronisation.  stats_pass_check: the pass's LDS refusal, and
+// nothing else, ahead of a caller that must not launch anything before it knows the pass will run.
+int stats_pass_check(pmf_ctx *c);
+int stats_pass(pmf_ctx *c, int use_factors, bool want_cols, bool want_batch, const float **cols, const float **batch);
 // ---- defined in pmf_lbfgs.hip
 void lbfgs_free(pmf_ctx *c);
 // ---- defined in pmf_netreg.hip
@@ -328,4 +337,9 @@ int netreg_eval(pmf_ctx *c, int which, int *reg_count);
 // ---- defined in pmf_comm_fit.hip
 int comm_release(pmf_ctx *c);
 bool comm_active(const pmf_ctx *c);
+// in-place sum over the ranks of `count` elements (f32 / f64) at device address p, ordered on the communication stream
+int comm_allreduce(pmf_ctx *c, void *p, int64_t count, bool f64);
+// the error exit of a call that may have left collectives unmatched: drains both streams, marks a communicator of more than
+// one rank unusable and appends that to the message; returns rc
+int comm_error_exit(pmf_ctx *c, int rc);
 #endif

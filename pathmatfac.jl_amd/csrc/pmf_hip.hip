@@ -740,6 +740,8 @@ static int data_shape_changed(pmf_ctx *c, int64_t M, int64_t N) {
   k_fill<<<nblocks(N, 256), 256, 0, c->stream>>>(c->colw, N, 1.f);
   HIPCHK(hipGetLastError());
   c->mixed = false;
+  c->noise_s1.clear();   // (the noise model is reset with the shape: its ranges indexed the old columns)
+  c->noise_e1.clear();
   c->prepared = false;
   c->state_init = false;
   return 0;
@@ -980,6 +982,8 @@ extern "C" int pmf_set_noise(pmf_ctx *c, int n_ranges, const int64_t *s1, const 
   HIPCHK(hipMemcpy(c->colmeta, meta.data(), sizeof(int32_t) * (size_t)c->N, hipMemcpyHostToDevice));
   if (weights) HIPCHK(hipMemcpy(c->colw, weights, sizeof(float) * (size_t)c->N, hipMemcpyHostToDevice));
   c->mixed = mixed;
+  c->noise_s1.assign(s1, s1 + n_ranges);
+  c->noise_e1.assign(e1, e1 + n_ranges);
   c->h_kind.assign(meta.begin(), meta.end());
   c->kind_version++;
   PMFCHK(rebuild_colmeta_views(c));
@@ -1956,17 +1960,23 @@ static void col_walk_fill(pmf_ctx *c, ColWalkArgs &a, int &gx, int64_t &gy) {
   gy = (c->M + a.rows_per_block - 1) / a.rows_per_block;
 }
 // Launches kerns[KB - 1].  The [2][max_nb][64] batch sums are dynamic LDS on top of the kernel's static LDS (k_layer_grad:
-// block_reduce_sum's slots): past 160 KiB together the launch is refused here, naming the batch count.
-template <typename Args>
-static int col_walk_launch(pmf_ctx *c, void (*const (&kerns)[4])(const Args), const Args &a, int gx, int64_t gy, const char *what) {
+// block_reduce_sum's slots): past 160 KiB together the launch is refused (col_walk_check), naming the batch count.
+static int col_walk_check(pmf_ctx *c, const void *const (&kerns)[4], int max_nb, const char *what, size_t *lds_out) {
   if (c->KB < 1 || c->KB > 4) return pmf_fail("unsupported KB=%d", c->KB);
-  const void *kern = (const void *)kerns[c->KB - 1];
-  const size_t lds = col_walk_lds(c->Kp, a.max_nb);
+  const void *kern = kerns[c->KB - 1];
+  const size_t lds = col_walk_lds(c->Kp, max_nb);
   hipFuncAttributes fa;
   HIPCHK(hipFuncGetAttributes(&fa, kern));
   if (lds + fa.sharedSizeBytes > 160 * 1024)
-    return pmf_fail("too many row batches per view (%d) for the %s kernel", a.max_nb, what);
-  PMFCHK(ensure_dyn_lds(c, kern, lds));
+    return pmf_fail("too many row batches per view (%d) for the %s kernel", max_nb, what);
+  if (lds_out) *lds_out = lds;
+  return 0;
+}
+template <typename Args>
+static int col_walk_launch(pmf_ctx *c, void (*const (&kerns)[4])(const Args), const Args &a, int gx, int64_t gy, const char *what) {
+  size_t lds = 0;
+  PMFCHK(col_walk_check(c, {(const void *)kerns[0], (const void *)kerns[1], (const void *)kerns[2], (const void *)kerns[3]}, a.max_nb, what, &lds));
+  PMFCHK(ensure_dyn_lds(c, (const void *)kerns[c->KB - 1], lds));
   hipLaunchKernelGGL(kerns[c->KB - 1], dim3(gx, (unsigned)gy), dim3(64), lds, c->stream, a);
   HIPCHK(hipGetLastError());
   return 0;
@@ -2477,13 +2487,18 @@ extern "C" int pmf_synth_data(pmf_ctx *c, uint64_t seed, float noise, float frac
   return 0;
 }
 
-extern "C" int pmf_stats(pmf_ctx *c, int use_factors, float *col_n, float *col_sum, float *col_sumsq, float *col_sqerr,
-                         float *col_ssq_grad, float *batch_count, float *batch_sqerr) {
-  PMFCHK(ctx_bind(c));
-  PMFCHK(check_ready(c));
+// ---- the statistics pass behind pmf_stats and the stage entries of pmf_stages.hip
+static void (*const k_stats_kb[4])(const StatsArgs) = {k_stats<1>, k_stats<2>, k_stats<3>, k_stats<4>};
+int stats_pass_check(pmf_ctx *c) {
+  int max_nb = 1;
+  for (int v = 0; v < c->n_bv; ++v) max_nb = std::max(max_nb, (int)c->views[v].nb);
+  return col_walk_check(c, {(const void *)k_stats_kb[0], (const void *)k_stats_kb[1], (const void *)k_stats_kb[2], (const void *)k_stats_kb[3]}, max_nb, "statistics", nullptr);
+}
+int stats_pass(pmf_ctx *c, int use_factors, bool want_cols, bool want_batch, const float **cols, const float **batch) {
   PMFCHK(prepare(c));
-  const int64_t nbt = c->n_bv > 0 ? c->val_off[c->n_bv] : 0;
-  const size_t nfl = (size_t)(5 * c->N + 2 * nbt);
+  const int64_t nbt = (want_batch && c->n_bv > 0) ? c->val_off[c->n_bv] : 0;
+  const int64_t ncol = want_cols ? 5 * c->N : 0;
+  const size_t nfl = (size_t)(ncol + 2 * nbt);
   StatsArgs a;
   memset(&a, 0, sizeof(a));
   int gx; int64_t gy;
@@ -2494,17 +2509,29 @@ extern "C" int pmf_stats(pmf_ctx *c, int use_factors, float *col_n, float *col_s
   PMFCHK(ensure_scratch(c, sizeof(float) * std::max<size_t>(nfl * (size_t)(gy + 1), 1)));
   float *buf = (float *)c->scratch, *part = buf + nfl;
   a.part_stride = (int64_t)nfl;
-  a.col_n = part; a.col_sum = part + c->N; a.col_sumsq = part + 2 * c->N; a.col_sqerr = part + 3 * c->N; a.col_ssqg = part + 4 * c->N;
-  a.b_n = nbt ? part + 5 * c->N : nullptr;
-  a.b_sqerr = nbt ? part + 5 * c->N + nbt : nullptr;
-  PMFCHK(col_walk_launch(c, {k_stats<1>, k_stats<2>, k_stats<3>, k_stats<4>}, a, gx, gy, "statistics"));
+  if (want_cols) { a.col_n = part; a.col_sum = part + c->N; a.col_sumsq = part + 2 * c->N; a.col_sqerr = part + 3 * c->N; a.col_ssqg = part + 4 * c->N; }
+  a.b_n = nbt ? part + ncol : nullptr;
+  a.b_sqerr = nbt ? part + ncol + nbt : nullptr;
+  PMFCHK(col_walk_launch(c, k_stats_kb, a, gx, gy, "statistics"));
   PMFCHK(sum_parts(c, part, (int64_t)nfl, (int)gy, buf, (int64_t)nfl));
+  if (cols) *cols = want_cols ? buf : nullptr;
+  if (batch) *batch = nbt ? buf + ncol : nullptr;
+  return 0;
+}
+
+extern "C" int pmf_stats(pmf_ctx *c, int use_factors, float *col_n, float *col_sum, float *col_sumsq, float *col_sqerr,
+                         float *col_ssq_grad, float *batch_count, float *batch_sqerr) {
+  PMFCHK(ctx_bind(c));
+  PMFCHK(check_ready(c));
+  const int64_t nbt = c->n_bv > 0 ? c->val_off[c->n_bv] : 0;
+  const float *buf = nullptr, *bbuf = nullptr;
+  PMFCHK(stats_pass(c, use_factors, true, true, &buf, &bbuf));
   HIPCHK(hipStreamSynchronize(c->stream));
   float *outs[5] = {col_n, col_sum, col_sumsq, col_sqerr, col_ssq_grad};
   for (int q = 0; q < 5; ++q)
     if (outs[q]) HIPCHK(hipMemcpy(outs[q], buf + (int64_t)q * c->N, sizeof(float) * (size_t)c->N, hipMemcpyDeviceToHost));
-  if (batch_count && nbt) HIPCHK(hipMemcpy(batch_count, buf + 5 * c->N, sizeof(float) * (size_t)nbt, hipMemcpyDeviceToHost));
-  if (batch_sqerr && nbt) HIPCHK(hipMemcpy(batch_sqerr, buf + 5 * c->N + nbt, sizeof(float) * (size_t)nbt, hipMemcpyDeviceToHost));
+  if (batch_count && nbt) HIPCHK(hipMemcpy(batch_count, bbuf, sizeof(float) * (size_t)nbt, hipMemcpyDeviceToHost));
+  if (batch_sqerr && nbt) HIPCHK(hipMemcpy(batch_sqerr, bbuf + nbt, sizeof(float) * (size_t)nbt, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -146,6 +146,22 @@ def _device_stats(model, use_factors, device=0):
     return red
 
 
+def _library_stage_context(model, stages, device=0):
+    """`stages` = "host" (None: the host arithmetic on downloaded statistics) or "library" (the model marshalled once, for
+    one pmf_stage_* call on its device context)."""
+    if stages == "host":
+        return None
+    if stages != "library":
+        raise ValueError(f"stages={stages!r}: 'host' or 'library'")
+    if model.sharded and model._allreduce_fn is not None:
+        raise ValueError("stages='library' on a row-sharded model whose reducer was replaced by model.set_allreduce: the "
+                         "library sums the statistics over the ranks through its own communicator and has none here "
+                         "(use stages='host', or attach_comm and set_allreduce(None))")
+    ctx = model.device_context(device)
+    MF.marshal(model.matfac, ctx, with_xreg=False, with_yreg=False)
+    return ctx
+
+
 def init_mu_(model, capacity=int(10e8), lr_mu=0.1, max_epochs=500, verbosity=1, print_prefix="", history=None,
              **kwargs):
     """init_mu! (src/fit.jl:82-103): mu <- per-column M-estimates argmin_m sum_i loss(m, D_ij), found by AdaGrad on mu
@@ -178,8 +194,14 @@ def init_mu_(model, capacity=int(10e8), lr_mu=0.1, max_epochs=500, verbosity=1, 
         history_(history, h, name="init_mu")
 
 
-def init_logsigma_(model, capacity=int(10e8), history=None):
+def init_logsigma_(model, capacity=int(10e8), history=None, stages="host"):
     """init_logsigma! (src/fit.jl:125-148): logsigma <- log sqrt( link_col_sqerr / column_nonnan ) with X'Y = 0."""
+    ctx = _library_stage_context(model, stages)
+    if ctx is not None:
+        ctx.stage_init_logsigma()
+        model.matfac.col_transform.unwrapped(1).logsigma[...] = ctx.get_col_params()[0]
+        history_(history, name="init_logsigma")
+        return
     st = _device_stats(model, use_factors=False)
     with np.errstate(divide="ignore", invalid="ignore"):
         col_vars = st["sqerr"].astype(np.float64) / st["n"].astype(np.float64)
@@ -187,10 +209,16 @@ def init_logsigma_(model, capacity=int(10e8), history=None):
     history_(history, name="init_logsigma")
 
 
-def reweight_col_losses_(model, capacity=int(10e8), history=None):
+def reweight_col_losses_(model, capacity=int(10e8), history=None, stages="host"):
     """reweight_col_losses! (src/fit.jl:151-187): weights <- 1 / (rms column gradient * sigma), non-finite -> 1."""
     M, N = model.M_total, model.data.shape[1]                                 # (row-sharded: all samples, not the local ones)
     nm = model.matfac.noise_model
+    ctx = _library_stage_context(model, stages)
+    if ctx is not None:
+        ctx.stage_reweight_col_losses(M)
+        nm.set_weight_(ctx.get_noise_weights())
+        history_(history, name="reweight_col_losses")
+        return
     nm.set_weight_(np.ones(N, np.float32))                                    # :157
     st = _device_stats(model, use_factors=False)                              # X, Y zeroed (:160-163)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -202,11 +230,17 @@ def reweight_col_losses_(model, capacity=int(10e8), history=None):
     history_(history, name="reweight_col_losses")
 
 
-def construct_minimal_regularizer(model, capacity=10 ** 8):
+def construct_minimal_regularizer(model, capacity=10 ** 8, stages="host"):
     """src/regularizers.jl:750-774: GroupRegularizer over the noise-model column ranges, weight
     K*mean(sigma^2) / (sum(nanvar .* nonnan) / M) per group (nanvar floored at 1/M)."""
     mf = model.matfac
     K, M = mf.X.shape[0], model.M_total
+    ctx = _library_stage_context(model, stages)
+    if ctx is not None:
+        nm = mf.noise_model
+        gws = ctx.stage_minimal_group_weights(M)
+        return GroupRegularizer(group_idx=[(g.start, g.stop) for g in nm.col_ranges],
+                                group_weights=[np.full(K, gw, dtype=np.float32) for gw in gws], labels=list(nm.noises))
     st = _device_stats(model, use_factors=False)
     n = st["n"].astype(np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -244,9 +278,22 @@ def _nans_to_val(arrs, val):  # :313-318
 
 
 def theta_delta_em(model, delta2, sigma2, update_priors=True, batch_em_max_iter=100, batch_em_rtol=1e-8,
-                   verbosity=1, print_prefix="", history=None):
+                   verbosity=1, print_prefix="", history=None, stages="host"):
     """theta_delta_em (src/fit.jl:326-375).  `model` is the working PathMatFacModel; the per-(batch, column) sums
     (ba_map) are computed on the device."""
+    ctx = _library_stage_context(model, stages)
+    if ctx is not None:
+        r = ctx.stage_theta_delta_em(delta2, sigma2, update_priors=update_priors, max_iter=batch_em_max_iter,
+                                     rtol=batch_em_rtol)
+        diffs = [float(d) for d in r["diffs"]]
+        if verbosity > 0:
+            for it, diff in enumerate(diffs, 1):
+                print(f"{print_prefix}({it}) ||theta - theta'||^2/||theta||^2 : {diff}")
+        theta = model.matfac.col_transform.unwrapped(4).theta
+        for dst, src in zip(theta.values, r["theta"]):          # only what changed comes back: theta of every view and delta2
+            dst[...] = src
+        history_(history, name="batch_effect_EM_procedure", diffs=diffs)
+        return [v.copy() for v in theta.values], r["delta2"]
     with np.errstate(divide="ignore", invalid="ignore"):
         theta = model.matfac.col_transform.unwrapped(4).theta
         theta_lsq = [v.copy() for v in theta.values]
@@ -296,8 +343,9 @@ def _condition_ind_mat(model):
 
 def init_batch_effects_(model, capacity=10 ** 8, max_epochs=5000, lr_regress=0.25, lr_mu=0.1, lr_theta=1.0,
                         batch_method="EM", batch_em_rtol=1e-8, batch_em_max_iter=100, verbosity=1, print_prefix="",
-                        history=None, **kwargs):
-    """init_batch_effects! (src/fit.jl:378-496)."""
+                        history=None, stages="host", **kwargs):
+    """init_batch_effects! (src/fit.jl:378-496).  `stages` reaches the EM; the one-off moments before it (:444-462) stay
+    on the downloaded statistics."""
     n_pref = print_prefix + "    "
     orig = model.matfac
     work = copy.deepcopy(orig)                                                           # :393
@@ -332,7 +380,8 @@ def init_batch_effects_(model, capacity=10 ** 8, max_epochs=5000, lr_regress=0.2
         if batch_method in ("EM", "EB"):                                                 # :466-481
             theta_values, delta2 = theta_delta_em(model, delta2, col_vars, update_priors=(batch_method == "EM"),
                                                   batch_em_max_iter=batch_em_max_iter, batch_em_rtol=batch_em_rtol,
-                                                  print_prefix=n_pref, verbosity=verbosity - 1, history=history)
+                                                  print_prefix=n_pref, verbosity=verbosity - 1, history=history,
+                                                  stages=stages)
     finally:
         model.matfac = orig                                                              # :487
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -541,8 +590,8 @@ def reweight_eb_(reg, P, mixture_p=1.0, model=None):
 def basic_fit_(model, fit_batch=False, batch_method="EM", fit_mu=False, fit_logsigma=False, reweight_losses=False,
                init_factors=False, init_factors_method="adagrad", fit_factors=False, init_ordinal=False,
                svd_rotate=False, whiten=False, capacity=int(10e8), lr=1.0, max_epochs=1000, verbosity=1,
-               print_prefix="", history=None, lr_regress=1.0, lr_mu=0.1, lr_theta=1.0, **kwargs):
-    """basic_fit! (src/fit.jl:564-671)."""
+               print_prefix="", history=None, lr_regress=1.0, lr_mu=0.1, lr_theta=1.0, stages="host", **kwargs):
+    """basic_fit! (src/fit.jl:564-671).  `stages`: where the closed-form stages run ("host" / "library")."""
     n_prefix = print_prefix + "    "
     ct = model.matfac.col_transform
     if init_ordinal:
@@ -552,15 +601,15 @@ def basic_fit_(model, fit_batch=False, batch_method="EM", fit_mu=False, fit_logs
             "Model must have batch parameters whenever `fit_batch` is true"
         init_batch_effects_(model, batch_method=batch_method, capacity=capacity, max_epochs=max_epochs,
                             verbosity=verbosity, print_prefix=n_prefix, history=history, lr_regress=lr_regress,
-                            lr_theta=lr_theta)
+                            lr_theta=lr_theta, stages=stages)
     else:
         if fit_mu:
             init_mu_(model, capacity=capacity, max_epochs=500, verbosity=verbosity, print_prefix=n_prefix,
                      history=history)
         if fit_logsigma:
-            init_logsigma_(model, capacity=capacity)
+            init_logsigma_(model, capacity=capacity, stages=stages)
     if reweight_losses:
-        reweight_col_losses_(model, capacity=capacity)
+        reweight_col_losses_(model, capacity=capacity, stages=stages)
     if init_factors:
         init_factors_(model, lr=lr, init_factors_method=init_factors_method, verbosity=verbosity,
                       print_prefix=print_prefix, history=history, capacity=capacity, max_epochs=max_epochs, **kwargs)
@@ -575,23 +624,23 @@ def basic_fit_(model, fit_batch=False, batch_method="EM", fit_mu=False, fit_logs
 
 
 def fit_ard_(model, max_epochs=1000, capacity=10 ** 8, verbosity=1, print_prefix="", history=None, lr=1.0,
-             lr_regress=1.0, lr_theta=1.0, svd_rotate=True, batch_method="EM", **kwargs):
+             lr_regress=1.0, lr_theta=1.0, svd_rotate=True, batch_method="EM", stages="host", **kwargs):
     """fit_ard! (src/fit.jl:751-808)."""
     n_pref = print_prefix + "    "
     mf = model.matfac
     orig_X_reg, orig_ard = mf.X_reg, mf.Y_reg
     mf.X_reg = ZeroReg()                                                     # :769
-    mf.Y_reg = construct_minimal_regularizer(model)                           # :770
+    mf.Y_reg = construct_minimal_regularizer(model, stages=stages)            # :770
     fit_batch = isinstance(mf.col_transform.unwrapped(2), BatchScale)
     basic_fit_(model, fit_batch=fit_batch, fit_mu=True, fit_logsigma=True, init_factors=True, reweight_losses=True,
                svd_rotate=svd_rotate, whiten=True, lr_regress=lr_regress, lr_theta=lr_theta, verbosity=verbosity,
                print_prefix=n_pref, batch_method=batch_method, max_epochs=max_epochs, capacity=capacity,
-               history=history, lr=lr, **kwargs)                              # :773-787
+               history=history, lr=lr, stages=stages, **kwargs)               # :773-787
     mf.X_reg = orig_X_reg
     reweight_eb_(mf.X_reg, mf.X, model=model)                                 # :791-792
     mf.Y_reg = orig_ard
     reweight_eb_(mf.Y_reg, mf.Y)                                              # :793-794
-    reweight_col_losses_(model, capacity=capacity)                            # :797
+    reweight_col_losses_(model, capacity=capacity, stages=stages)             # :797
     mf_fit_adapt_lr_(model, capacity=capacity, update_X=True, update_Y=True, lr=lr, min_lr=0.01,
                      max_epochs=max_epochs, verbosity=verbosity, print_prefix=n_pref, history=history, **kwargs)  # :800
 
@@ -608,7 +657,7 @@ def fit_non_ard_(model, fit_reg_weight="EB", **kwargs):
 
 
 def basic_fit_reg_weight_eb_(model, capacity=int(10e8), lr=1.0, max_epochs=1000, verbosity=1, print_prefix="",
-                             history=None, svd_rotate=True, **kwargs):
+                             history=None, svd_rotate=True, stages="host", **kwargs):
     """basic_fit_reg_weight_eb! (src/fit.jl:674-727)."""
     n_pref = print_prefix + "    "
     mf = model.matfac
@@ -617,11 +666,11 @@ def basic_fit_reg_weight_eb_(model, capacity=int(10e8), lr=1.0, max_epochs=1000,
         freeze_reg_(sr, [1, 2, 3, 4])                                          # :681
     orig_X_reg, orig_Y_reg = mf.X_reg, mf.Y_reg
     mf.X_reg = L2Regularizer(mf.X.shape[0], 1.0)                              # X -> 0.5*sum(X.*X)   (:686)
-    mf.Y_reg = construct_minimal_regularizer(model)                            # :687
+    mf.Y_reg = construct_minimal_regularizer(model, stages=stages)             # :687
     fit_batch = isinstance(mf.col_transform.unwrapped(2), BatchScale)
     basic_fit_(model, fit_mu=True, fit_logsigma=True, reweight_losses=True, fit_batch=fit_batch, init_factors=True,
                svd_rotate=svd_rotate, whiten=False, verbosity=verbosity, print_prefix=n_pref, capacity=capacity,
-               lr=lr, max_epochs=max_epochs, history=history, **kwargs)       # :694-704
+               lr=lr, max_epochs=max_epochs, history=history, stages=stages, **kwargs)   # :694-704
     if isinstance(sr, SequenceReg):
         unfreeze_reg_(sr, [1, 2, 3, 4])                                        # :709
     mf.X_reg, mf.Y_reg = orig_X_reg, orig_Y_reg
@@ -631,11 +680,12 @@ def basic_fit_reg_weight_eb_(model, capacity=int(10e8), lr=1.0, max_epochs=1000,
     reweight_eb_(mf.Y_reg, mf.Y)                                               # :714
     history_(history, name="reweight_eb")
     basic_fit_(model, reweight_losses=True, fit_factors=True, verbosity=verbosity, print_prefix=n_pref,
-               history=history, capacity=capacity, lr=lr, max_epochs=max_epochs, **kwargs)   # :720-725
+               history=history, capacity=capacity, lr=lr, max_epochs=max_epochs, stages=stages, **kwargs)   # :720-725
 
 
 def fit_feature_set_ard_(model, lr=1.0, capacity=10 ** 8, max_epochs=1000, fsard_max_iter=10, fsard_max_A_iter=1000,
-                         fsard_term_rtol=1e-5, verbosity=1, print_prefix="", svd_rotate=True, history=None, **kwargs):
+                         fsard_term_rtol=1e-5, verbosity=1, print_prefix="", svd_rotate=True, history=None, stages="host",
+                         **kwargs):
     """fit_feature_set_ard! (src/fit.jl:814-892)."""
     from .featureset_ard import update_A_
     n_pref = print_prefix + "    "
@@ -643,7 +693,7 @@ def fit_feature_set_ard_(model, lr=1.0, capacity=10 ** 8, max_epochs=1000, fsard
     orig_reg = mf.Y_reg
     mf.Y_reg = ARDRegularizer(model.feature_views)                            # :829
     fit_ard_(model, max_epochs=max_epochs, capacity=capacity, lr=lr, verbosity=verbosity, print_prefix=n_pref,
-             history=history, svd_rotate=svd_rotate, **kwargs)                 # :832
+             history=history, svd_rotate=svd_rotate, stages=stages, **kwargs)  # :832
     mf.Y_reg = orig_reg                                                        # :837
     beta_old = orig_reg.beta.copy()
     for it in range(1, fsard_max_iter + 1):
@@ -664,8 +714,10 @@ def fit_feature_set_ard_(model, lr=1.0, capacity=10 ** 8, max_epochs=1000, fsard
 
 def fit_(model, lr=1.0, fit_reg_weight="EB", n_lambda=8, lambda_max=None, lambda_min_frac=1e-3, keep_history=False,
          svd_rotate=True, fit_joint=False, fsard_max_iter=10, fsard_max_A_iter=1000, fsard_term_rtol=1e-5,
-         rel_tol=1e-5, abs_tol=1e-5, verbosity=1, print_prefix="", capacity=10 ** 8, **kwargs):
-    """fit! (src/fit.jl:923-1018), the master function.  Returns the history list (or None)."""
+         rel_tol=1e-5, abs_tol=1e-5, verbosity=1, print_prefix="", capacity=10 ** 8, stages="host", **kwargs):
+    """fit! (src/fit.jl:923-1018), the master function.  Returns the history list (or None).
+    `stages`: "host" (default) runs the closed-form stages between the GD stages on statistics downloaded from the device,
+    "library" runs each of them as one pmf_stage_* call."""
     global FIT_START_TIME
     FIT_START_TIME = time.time()
     hist = [] if keep_history else None
@@ -673,21 +725,21 @@ def fit_(model, lr=1.0, fit_reg_weight="EB", n_lambda=8, lambda_max=None, lambda
     mf = model.matfac
     if isinstance(mf.Y_reg, ARDRegularizer):
         fit_ard_(model, history=hist, verbosity=verbosity, print_prefix=print_prefix, rel_tol=rel_tol, abs_tol=abs_tol,
-                 capacity=capacity, svd_rotate=svd_rotate, lr=lr, **kwargs)
+                 capacity=capacity, svd_rotate=svd_rotate, lr=lr, stages=stages, **kwargs)
     elif isinstance(mf.Y_reg, FeatureSetARDReg):
         fit_feature_set_ard_(model, lr=lr, rel_tol=rel_tol, abs_tol=abs_tol, history=hist,
                              fsard_max_iter=fsard_max_iter, fsard_max_A_iter=fsard_max_A_iter,
                              fsard_term_rtol=fsard_term_rtol, svd_rotate=svd_rotate, verbosity=verbosity,
-                             print_prefix=print_prefix, capacity=capacity, **kwargs)
+                             print_prefix=print_prefix, capacity=capacity, stages=stages, **kwargs)
     else:
         fit_non_ard_(model, history=hist, rel_tol=rel_tol, abs_tol=abs_tol, fit_reg_weight=fit_reg_weight,
                      lambda_max=lambda_max, n_lambda=n_lambda, lambda_min_frac=lambda_min_frac, svd_rotate=svd_rotate,
-                     verbosity=verbosity, print_prefix=print_prefix, capacity=capacity, lr=lr, **kwargs)
+                     verbosity=verbosity, print_prefix=print_prefix, capacity=capacity, lr=lr, stages=stages, **kwargs)
     if fit_joint:
         # the reference's fit_joint branch references an undefined `max_epochs` (Q3, src/fit.jl:995): it cannot run there
         raise NotImplementedError("fit_joint=true is broken in the reference (src/fit.jl:995) and not reproduced")
     whiten_(model)                                                             # :1004
-    reweight_col_losses_(model, capacity=capacity, history=hist)               # :1008
+    reweight_col_losses_(model, capacity=capacity, history=hist, stages=stages)   # :1008
     reorder_by_importance_(model)                                              # :1011
     history_(hist, name="reorder_factors")
     history_(hist, name="finish")

@@ -4,12 +4,18 @@
 # Everything above `mf_fit!` in src/fit.jl (mf_fit_adapt_lr!, init_theta!, init_factors!, fit_ard!,
 # fit_feature_set_ard!, fit!, transform) runs unchanged: it only sees the history Dict this function returns
 # ("term_code", "epochs", src/fit.jl:63,69) and the mutated model parameters.
+# The closed-form stages between the gradient-descent stages (init_mu!, init_logsigma!, reweight_col_losses!,
+# construct_minimal_regularizer, theta_delta_em, update_A!) are re-pointed too: each marshals the model, makes ONE library
+# call (pmf_stage_* / pmf_fsard_update_A; init_mu! goes through this file's mf_fit!) and copies back what changed.  The
+# moments block inside init_batch_effects! (src/fit.jl:444-462) keeps MatFac's CPU helpers.
 #
 # Usage:   using PathMatFac; include("PathMatFacHIP.jl"); PathMatFacHIP.install!("/path/to/libpmf_hip.so")
 #          model = PathMatFacModel(D; ...);  fit!(model; ...)         # no gpu(model): the library owns the device copy
 #
 # NOTE: Julia is not installed in the build container, so this file has not been executed there; it is the
-# maintainer-side binding that INTEGRATION.md documents.  The Python ctypes binding (_lib.py) is its tested twin.
+# maintainer-side binding that INTEGRATION.md documents.  The Python ctypes binding (_lib.py) is its tested twin, and
+# tests/test_julia_shim_static.py checks every `ccall` here (name, return type, argument count and types) and every struct
+# against include/pmf_hip.h without running Julia.
 module PathMatFacHIP
 
 import PathMatFac
@@ -19,6 +25,7 @@ const LIB = Ref{String}("libpmf_hip.so")
 const CTX = IdDict{Any,Ptr{Cvoid}}()          # model => pmf_ctx*
 const DATA_KEY = IdDict{Any,UInt}()           # model => objectid(model.data) last uploaded
 const OPT_KEY = IdDict{Any,UInt}()            # model => objectid(opt) whose state lives on the device
+const FSARD_DATA = IdDict{Any,Matrix{Float32}}()   # FeatureSetARDReg => the all-missing 1 x N matrix of its own context (update_A!)
 
 const TERM_CODES = ("max_epochs", "loss_increase", "abs_tol", "rel_tol", "nonfinite")
 const NOISE_KIND = Dict("normal" => Cint(0), "bernoulli" => Cint(1), "poisson" => Cint(2))
@@ -45,6 +52,14 @@ mutable struct LbfgsResult  # pmf_lbfgs_result
     loss_trace::Ptr{Cdouble}; trial_trace::Ptr{Cint}; flag_trace::Ptr{Cint}
 end
 
+struct EmOpts             # pmf_em_opts
+    update_priors::Cint; max_iter::Cint; verbosity::Cint; reserved::Cint; rtol::Cdouble
+end
+
+mutable struct EmResult   # pmf_em_result
+    iters::Cint; n_diffs::Cint; diffs_cap::Cint; reserved::Cint; diffs::Ptr{Cdouble}; seconds::Cdouble
+end
+
 lasterr() = unsafe_string(ccall((:pmf_last_error, LIB[]), Cstring, ()))
 chk(rc::Integer) = rc == 0 ? nothing : error("libpmf_hip: " * lasterr())
 f32(a) = convert(Array{Float32}, a)
@@ -56,6 +71,12 @@ stops(rs) = Int64[r.stop for r in rs]
 function set_precision!(model, mode::Symbol)
     code = mode == :f32 ? 0 : mode == :bf16x3 ? 1 : error("precision must be :f32 or :bf16x3")
     chk(ccall((:pmf_set_precision, LIB[]), Cint, (Ptr{Cvoid}, Cint), context!(model), code))
+end
+# (mode, fused launches that took the split-bf16 kernel so far)
+function get_precision(model)
+    mode = Ref{Cint}(0); n = Ref{Int64}(0)
+    chk(ccall((:pmf_get_precision, LIB[]), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}), context!(model), mode, n))
+    return (mode[] == 0 ? :f32 : :bf16x3), Int(n[])
 end
 
 # Storage type of the device copy of D (include/pmf_hip.h): :f32 (default) or :bf16 (BASELINE configs[4], "D stored
@@ -114,6 +135,18 @@ function comm_allreduce!(model, a::Array{T}; op::Integer=0) where {T<:Union{Floa
     return a
 end
 
+# rank, size, transport (0 none, 1 RCCL, 2 host-staged), column chunks of the last fit, reserved CUs, collectives issued
+function comm_info(model)
+    r = Ref{Cint}(0); n = Ref{Cint}(0); t = Ref{Cint}(0); ch = Ref{Cint}(0); cu = Ref{Cint}(0); nc = Ref{Int64}(0)
+    chk(ccall((:pmf_comm_info, LIB[]), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Cint}, Ref{Cint}, Ref{Cint}, Ref{Int64}),
+              context!(model), r, n, t, ch, cu, nc))
+    return (rank = Int(r[]), nranks = Int(n[]), transport = Int(t[]), n_chunks = Int(ch[]), reserved_cus = Int(cu[]),
+            n_collectives = Int(nc[]))
+end
+
+# fresh optimizer state on the device (a new optimizer object does this by itself in mf_fit!)
+reset_optimizer_state!(model) = chk(ccall((:pmf_reset_optimizer_state, LIB[]), Cint, (Ptr{Cvoid},), context!(model)))
+
 # Adopt the host's HIP stream (AMDGPU.jl: AMDGPU.stream().stream); C_NULL = the library's own non-blocking stream.
 set_stream!(model, stream::Ptr{Cvoid}) = chk(ccall((:pmf_set_stream, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), context!(model), stream))
 
@@ -123,30 +156,34 @@ set_stream!(model, stream::Ptr{Cvoid}) = chk(ccall((:pmf_set_stream, LIB[]), Cin
 function fsard_update_A!(model, cr::UnitRange, S_t::Matrix{Float32}, alpha::Vector{Float32}, lambda::Vector{Float32},
                          A_t::Matrix{Float32}, ssq_t::Matrix{Float32}, beta::Matrix{Float32};
                          alpha0::Float32, v0::Float32, lr::Float32, max_epochs::Integer=1000, term_iter::Integer=50,
-                         atol::Float64=1e-5)
+                         atol::Float64=1e-5, ctx::Ptr{Cvoid}=context!(model))
     best = Ref{Cdouble}(0.0); ep = Ref{Cint}(0)
     L = size(S_t, 2)
     GC.@preserve S_t alpha lambda A_t ssq_t beta chk(ccall((:pmf_fsard_update_A, LIB[]), Cint,
         (Ptr{Cvoid}, Int64, Int64, Cint, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Cfloat, Cfloat, Cfloat, Ptr{Cfloat},
          Ptr{Cfloat}, Cint, Cint, Cdouble, Ref{Cdouble}, Ref{Cint}, Ptr{Cfloat}),
-        context!(model), cr.start, cr.stop, L, S_t, alpha, lambda, alpha0, v0, lr, ssq_t, A_t, max_epochs, term_iter, atol,
+        ctx, cr.start, cr.stop, L, S_t, alpha, lambda, alpha0, v0, lr, ssq_t, A_t, max_epochs, term_iter, atol,
         best, ep, beta))
     return best[], Int(ep[])
 end
 
-function context!(model; device::Integer=0)
-    ctx = get!(CTX, model) do
+context!(model; device::Integer=0) = data_context!(model, model.data; device=device)
+
+# The context of `owner` (a PathMatFacModel, or -- for the functions that get a bare MatFacModel and the data, as
+# theta_delta_em does -- the data array itself), with `data` resident on the device.
+function data_context!(owner, data; device::Integer=0)
+    ctx = get!(CTX, owner) do
         p = Ref{Ptr{Cvoid}}(C_NULL)
         chk(ccall((:pmf_create, LIB[]), Cint, (Cint, Ref{Ptr{Cvoid}}), device, p))
         p[]
     end
-    key = objectid(model.data)
-    if get(DATA_KEY, model, UInt(0)) != key            # gpu(model): upload the data matrix once
-        D = f32(model.data)
+    key = objectid(data)
+    if get(DATA_KEY, owner, UInt(0)) != key            # gpu(model): upload the data matrix once
+        D = f32(data)
         M, N = size(D)
         GC.@preserve D chk(ccall((:pmf_set_data, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Int64, Int64, Cint),
                                  ctx, D, M, N, STORE[]))
-        DATA_KEY[model] = key
+        DATA_KEY[owner] = key
     end
     return ctx
 end
@@ -170,18 +207,27 @@ function batch_of_row(rb)
     return out
 end
 
+# (`ccall` needs its function name as a literal: one call per branch, never a computed symbol)
 function add_reg!(ctx, which::Symbol, reg, p::Float32=1f0)
-    sym(s) = Symbol("pmf_add_", which == :X ? "xreg_" : "yreg_", s)
     if isa(reg, Function)                               # x -> 0
         return
     elseif isa(reg, PM.L2Regularizer)
         w = f32(reg.weights)
-        GC.@preserve w chk(ccall((sym("l2"), LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Cfloat), ctx, w, p))
+        if which == :X
+            GC.@preserve w chk(ccall((:pmf_add_xreg_l2, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Cfloat), ctx, w, p))
+        else
+            GC.@preserve w chk(ccall((:pmf_add_yreg_l2, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Cfloat), ctx, w, p))
+        end
     elseif isa(reg, PM.GroupRegularizer)
         s, e = starts(reg.group_idx), stops(reg.group_idx)
         w = f32(hcat(reg.group_weights...))             # K x n_groups column-major == n_groups x K with K contiguous
-        GC.@preserve s e w chk(ccall((sym("group"), LIB[]), Cint,
-            (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Cfloat}, Cfloat), ctx, length(s), s, e, w, p))
+        if which == :X
+            GC.@preserve s e w chk(ccall((:pmf_add_xreg_group, LIB[]), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Cfloat}, Cfloat), ctx, length(s), s, e, w, p))
+        else
+            GC.@preserve s e w chk(ccall((:pmf_add_yreg_group, LIB[]), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Cfloat}, Cfloat), ctx, length(s), s, e, w, p))
+        end
     elseif isa(reg, PM.ARDRegularizer) && which == :Y
         s, e = starts(reg.col_ranges), stops(reg.col_ranges)
         a, b = f32(collect(reg.alpha)), f32(collect(reg.beta))
@@ -200,7 +246,9 @@ function add_reg!(ctx, which::Symbol, reg, p::Float32=1f0)
     end
 end
 
-function marshal!(ctx, mf)
+# with_regs = false: parameters, batch views and noise model only, X_reg / Y_reg cleared -- what the statistics passes need
+# (init_batch_effects! keeps an X_reg of the wrong shape attached while it regresses Y, src/fit.jl:397-428)
+function marshal!(ctx, mf; with_regs::Bool=true)
     X, Y = f32(mf.X), f32(mf.Y)
     K = size(X, 1)
     GC.@preserve X Y chk(ccall((:pmf_set_factors, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Cint), ctx, X, Y, K))
@@ -227,9 +275,10 @@ function marshal!(ctx, mf)
     w = f32(noise_weights(nm))
     GC.@preserve s e kinds w chk(ccall((:pmf_set_noise, LIB[]), Cint,
         (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Cint}, Ptr{Cfloat}), ctx, length(s), s, e, kinds, w))
-    chk(ccall((:pmf_clear_xreg, LIB[]), Cint, (Ptr{Cvoid},), ctx)); add_reg!(ctx, :X, mf.X_reg)
-    chk(ccall((:pmf_clear_yreg, LIB[]), Cint, (Ptr{Cvoid},), ctx)); add_reg!(ctx, :Y, mf.Y_reg)
+    chk(ccall((:pmf_clear_xreg, LIB[]), Cint, (Ptr{Cvoid},), ctx)); with_regs && add_reg!(ctx, :X, mf.X_reg)
+    chk(ccall((:pmf_clear_yreg, LIB[]), Cint, (Ptr{Cvoid},), ctx)); with_regs && add_reg!(ctx, :Y, mf.Y_reg)
     marshal_layer_regs!(ctx, mf.col_transform_reg, nviews)
+    return nviews
 end
 
 function marshal_layer_regs!(ctx, sr, nviews)
@@ -268,9 +317,13 @@ function mf_fit!(model::PM.PathMatFacModel; update_X=false, update_Y=false, upda
     mf = model.matfac
     marshal!(ctx, mf)
     opt === nothing && (opt = PM.construct_optimizer(model, lr))
-    if get(OPT_KEY, model, UInt(0)) != objectid(opt)     # new optimizer object => fresh AdaGrad state (src/fit.jl:55)
+    if get(OPT_KEY, model, UInt(0)) != objectid(opt)     # new optimizer object => fresh state (src/fit.jl:55)
+        # Flux.Optimise.Adam(eta, beta::Tuple, epsilon) -> kind 1 with its own betas; anything else is the AdaGrad that
+        # construct_optimizer makes (src/fit.jl:41-43) -> kind 0, where the betas are not read
+        is_adam = isdefined(PM, :Flux) && opt isa PM.Flux.Optimise.Adam
+        b1, b2 = is_adam ? (Float32(opt.beta[1]), Float32(opt.beta[2])) : (0.9f0, 0.999f0)
         chk(ccall((:pmf_set_optimizer, LIB[]), Cint, (Ptr{Cvoid}, Cint, Cfloat, Cfloat, Cfloat, Cfloat),
-                  ctx, 0, opt.eta, opt.epsilon, 0.9f0, 0.999f0))
+                  ctx, is_adam ? 1 : 0, opt.eta, opt.epsilon, b1, b2))
         OPT_KEY[model] = objectid(opt)
     else                                                  # same optimizer, possibly halved eta (src/fit.jl:64)
         chk(ccall((:pmf_set_lr, LIB[]), Cint, (Ptr{Cvoid}, Cfloat), ctx, opt.eta))
@@ -343,6 +396,179 @@ function unmarshal!(ctx, mf, update_X, update_Y, update_col_layers)
     end
 end
 
+# ---- the closed-form stages, each ONE library call on the marshalled model (include/pmf_hip.h, pmf_stage_*) -------------
+# Masked column / batch statistics of the model's rows (pmf_stats); batch arrays flat over (view, column, batch).
+function stats(model::PM.PathMatFacModel; use_factors::Bool=false)
+    ctx = context!(model)
+    nviews = marshal!(ctx, model.matfac; with_regs=false)
+    N = size(model.data, 2)
+    nbt = nviews == 0 ? 0 : sum(length(v) for v in batch_array(model.matfac).values)
+    n, s1, s2, se, sg = zeros(Float32, N), zeros(Float32, N), zeros(Float32, N), zeros(Float32, N), zeros(Float32, N)
+    bc, bs = zeros(Float32, max(nbt, 1)), zeros(Float32, max(nbt, 1))
+    GC.@preserve n s1 s2 se sg bc bs chk(ccall((:pmf_stats, LIB[]), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}),
+        ctx, use_factors, n, s1, s2, se, sg, bc, bs))
+    return (n = n, sum = s1, sumsq = s2, sqerr = se, ssq_grad = sg, batch_count = bc[1:nbt], batch_sqerr = bs[1:nbt])
+end
+
+# the BatchArray that fixes the views (layers 2 and 4 share ranges and row batches), or nothing
+function batch_array(mf)
+    layers = map(unwrap, mf.col_transform.layers)
+    return isa(layers[2], PM.BatchScale) ? layers[2].logdelta : (isa(layers[4], PM.BatchShift) ? layers[4].theta : nothing)
+end
+
+function noise_weights_from_device(ctx, N)
+    w = zeros(Float32, N)
+    GC.@preserve w chk(ccall((:pmf_get_noise_weights, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}), ctx, w))
+    return w
+end
+
+"""Replacement for PathMatFac.init_logsigma! (src/fit.jl:125-148): pmf_stage_init_logsigma, logsigma copied back."""
+function init_logsigma!(model::PM.PathMatFacModel; capacity=Int(10e8), history=nothing)
+    ctx = context!(model)
+    marshal!(ctx, model.matfac; with_regs=false)
+    chk(ccall((:pmf_stage_init_logsigma, LIB[]), Cint, (Ptr{Cvoid},), ctx))
+    N = size(model.data, 2)
+    ls = zeros(Float32, N)
+    GC.@preserve ls chk(ccall((:pmf_get_col_params, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}), ctx, ls, C_NULL))
+    unwrap(model.matfac.col_transform.layers[1]).logsigma .= ls
+    PM.history!(history; name="init_logsigma")
+end
+
+"""Replacement for PathMatFac.reweight_col_losses! (src/fit.jl:151-187): pmf_stage_reweight_col_losses, the noise
+weights copied back through MF.set_weight!.  `M_total`: all samples when the rows are sharded over ranks."""
+function reweight_col_losses!(model::PM.PathMatFacModel; capacity=Int(10e8), history=nothing,
+                              M_total::Integer=size(model.data, 1))
+    ctx = context!(model)
+    marshal!(ctx, model.matfac; with_regs=false)
+    chk(ccall((:pmf_stage_reweight_col_losses, LIB[]), Cint, (Ptr{Cvoid}, Int64), ctx, M_total))
+    PM.MF.set_weight!(model.matfac.noise_model, noise_weights_from_device(ctx, size(model.data, 2)))
+    PM.history!(history; name="reweight_col_losses")
+end
+
+"""Replacement for PathMatFac.construct_minimal_regularizer (src/regularizers.jl:750-774): one weight per column range of
+the noise model from pmf_stage_minimal_group_weights, repeated over the K factors."""
+function construct_minimal_regularizer(model; capacity=10^8, M_total::Integer=size(model.data, 1))
+    ctx = context!(model)
+    mf = model.matfac
+    marshal!(ctx, mf; with_regs=false)
+    nm = mf.noise_model
+    K = size(mf.X, 1)
+    gw = zeros(Float32, length(nm.col_ranges))
+    GC.@preserve gw chk(ccall((:pmf_stage_minimal_group_weights, LIB[]), Cint, (Ptr{Cvoid}, Int64, Ptr{Cfloat}), ctx, M_total, gw))
+    # One group per noise range, labelled by the noise struct's type name: downstream code looks groups up by exactly
+    # these labels and ranges, so they have to be the ones the replaced function produces.
+    labels = String[string(typeof(noise)) for noise in nm.noises]
+    ranges = Tuple(first(r):last(r) for r in nm.col_ranges)
+    return PM.GroupRegularizer(labels, ranges, Tuple(fill(w, K) for w in gw))
+end
+
+"""Replacement for PathMatFac.theta_delta_em (src/fit.jl:326-375).  It gets a MatFacModel copy and the data, so the
+context is keyed by the data array: a SECOND context beside the model's own, with its own device copy of the data
+(8 GB at 100000 x 20000) for the duration of the call.  It is released before the function returns (`keep_context=true`
+keeps it for a host that calls the EM repeatedly on one matrix; release!(data) frees it then).  theta of every view and
+delta2 come back; nothing else is copied."""
+function theta_delta_em(matfac, delta2::Tuple, sigma2::AbstractVector, data::AbstractMatrix; update_priors=true,
+                        capacity=10^8, batch_em_max_iter=100, batch_em_rtol=1e-8, verbosity=1, print_prefix="",
+                        history=nothing, keep_context::Bool=false)
+    try
+        return theta_delta_em_on!(data_context!(data, data), matfac, delta2, sigma2; update_priors=update_priors,
+                                  batch_em_max_iter=batch_em_max_iter, batch_em_rtol=batch_em_rtol, verbosity=verbosity,
+                                  print_prefix=print_prefix, history=history)
+    finally
+        keep_context || release!(data)
+    end
+end
+
+function theta_delta_em_on!(ctx, matfac, delta2, sigma2; update_priors, batch_em_max_iter, batch_em_rtol, verbosity,
+                            print_prefix, history)
+    nviews = marshal!(ctx, matfac; with_regs=false)
+    theta = unwrap(matfac.col_transform.layers[4]).theta
+    d2 = Float64[]
+    for d in delta2
+        append!(d2, vec(convert(Array{Float64}, d)))     # nb x N_v column-major per view: flat like theta
+    end
+    s2 = f32(collect(sigma2))
+    diffs = zeros(Cdouble, max(batch_em_max_iter, 1))
+    opts = EmOpts(update_priors, batch_em_max_iter, 0, 0, batch_em_rtol)
+    res = EmResult(0, 0, length(diffs), 0, pointer(diffs), 0.0)
+    GC.@preserve d2 s2 diffs chk(ccall((:pmf_stage_theta_delta_em, LIB[]), Cint,
+        (Ptr{Cvoid}, Ref{EmOpts}, Ptr{Cfloat}, Ptr{Cdouble}, Ref{EmResult}), ctx, opts, s2, d2, res))
+    new_delta2 = Any[]
+    off = 0
+    for v in 1:nviews
+        th = zeros(Float32, size(theta.values[v]))
+        GC.@preserve th chk(ccall((:pmf_get_batch_view, LIB[]), Cint, (Ptr{Cvoid}, Cint, Ptr{Cfloat}, Ptr{Cfloat}),
+                                  ctx, v - 1, C_NULL, th))
+        theta.values[v] .= th
+        n = length(th)
+        push!(new_delta2, reshape(d2[off+1:off+n], size(th)))
+        off += n
+    end
+    trace = diffs[1:res.n_diffs]
+    if verbosity > 0
+        for (it, d) in enumerate(trace)
+            println(print_prefix, "(", it, ") ||theta - theta'||^2/||theta||^2 : ", d)
+        end
+    end
+    PM.history!(history; name="batch_effect_EM_procedure", diffs=trace)
+    return theta.values, Tuple(new_delta2)
+end
+
+"""Replacement for PathMatFac.init_mu! (src/fit.jl:82-103): the per-column M-estimates are the minimisers over mu alone
+with X'Y = 0, found by this file's mf_fit! on the ColShift layer with every other layer and every layer regularizer
+frozen (rel_tol 1e-5, abs_tol 1e-3), as pathmatfac.jl_amd/fit.py:init_mu_ does it."""
+function init_mu!(model::PM.PathMatFacModel; capacity=Int(10e8), lr_mu=0.1, max_epochs=500, verbosity=1,
+                  print_prefix="", history=nothing, kwargs...)
+    mf = model.matfac
+    ct = mf.col_transform
+    X0, Y0 = mf.X, mf.Y
+    mf.X, mf.Y = zero(X0), zero(Y0)
+    others = [l for l in (1, 2, 4) if !isa(ct.layers[l], PM.FrozenLayer)]
+    PM.freeze_layer!(ct, others)
+    sr = mf.col_transform_reg
+    regs = isa(sr, PM.SequenceReg) ? [l for l in 1:4 if !isa(sr.regs[l], PM.FrozenRegularizer)] : Int[]
+    isempty(regs) || PM.freeze_reg!(sr, regs)
+    h = nothing
+    try
+        h = mf_fit!(model; opt=PM.construct_optimizer(model, lr_mu), update_col_layers=true, max_epochs=max_epochs,
+                    rel_tol=1e-5, abs_tol=1e-3, verbosity=verbosity - 1, print_prefix=print_prefix, capacity=capacity)
+    finally
+        PM.unfreeze_layer!(ct, others)
+        isempty(regs) || PM.unfreeze_reg!(sr, regs)
+        mf.X, mf.Y = X0, Y0
+    end
+    history === nothing || PM.history!(history, h; name="init_mu")
+end
+
+"""Replacement for PathMatFac.update_A! (src/featureset_ard.jl:278-294): per view one pmf_fsard_update_A on a context of
+the regularizer's own that holds Y (an all-missing one-row data matrix fixes N; X is a zero column)."""
+function update_A!(reg::PM.FeatureSetARDReg, Y::AbstractMatrix; max_epochs=1000, term_iter=20, atol=1e-5, verbosity=1,
+                   print_prefix="", print_iter=100)
+    K, N = size(Y)
+    ctx = data_context!(reg, get!(() -> fill(NaN32, 1, N), FSARD_DATA, reg))
+    X0, Y32 = zeros(Float32, K, 1), f32(Y)
+    GC.@preserve X0 Y32 chk(ccall((:pmf_set_factors, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Cint), ctx, X0, Y32, K))
+    chk(ccall((:pmf_clear_yreg, LIB[]), Cint, (Ptr{Cvoid},), ctx))
+    add_reg!(ctx, :Y, reg)
+    beta_all = f32(reg.beta)
+    for (v, cr) in enumerate(reg.col_ranges)
+        opt = reg.A_opts[v]
+        S_t = f32(Matrix(transpose(reg.S[v])))             # N_v x L column-major = L x N_v row-major
+        A_t = zeros(Float32, K, size(reg.S[v], 1))          # update_A! starts every view from A = 0 (:286)
+        ssq_t = f32(Matrix(transpose(opt.ssq_grad)))
+        beta = zeros(Float32, K, length(cr))
+        best, _ = fsard_update_A!(reg, cr, S_t, f32(reg.alpha[cr]), f32(vec(opt.lambda)), A_t, ssq_t, beta;
+                                  alpha0=Float32(reg.alpha0), v0=Float32(reg.v0), lr=Float32(opt.lr),
+                                  max_epochs=max_epochs, term_iter=term_iter, atol=Float64(atol), ctx=ctx)
+        reg.A[v] .= transpose(A_t)
+        opt.ssq_grad .= transpose(ssq_t)
+        beta_all[:, cr] .= beta
+        verbosity > 1 && println(print_prefix, "    View ", v, ": final loss ", best)
+    end
+    reg.beta .= beta_all
+end
+
 """impute(model; include_batch_effects=false) (src/impute.jl:37-56) on the device: pmf_impute over the model's current
 parameters.  `link=true` returns Z itself, `keep_observed=true` returns the observed entries of model.data and predicts
 only the missing ones; `rows` (a UnitRange) bounds the host matrix.  Returns length(rows) x N Float32."""
@@ -361,12 +587,19 @@ end
 function install!(libpath::AbstractString="libpmf_hip.so")
     LIB[] = libpath
     @eval PathMatFac mf_fit!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.mf_fit!(model; kwargs...)
+    @eval PathMatFac init_mu!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.init_mu!(model; kwargs...)
+    @eval PathMatFac init_logsigma!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.init_logsigma!(model; kwargs...)
+    @eval PathMatFac reweight_col_losses!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.reweight_col_losses!(model; kwargs...)
+    @eval PathMatFac construct_minimal_regularizer(model; kwargs...) = Main.PathMatFacHIP.construct_minimal_regularizer(model; kwargs...)
+    @eval PathMatFac theta_delta_em(model::MF.MatFacModel, delta2::Tuple, sigma2::AbstractVector, data::AbstractMatrix; kwargs...) =
+        Main.PathMatFacHIP.theta_delta_em(model, delta2, sigma2, data; kwargs...)
+    @eval PathMatFac update_A!(reg::FeatureSetARDReg, Y::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.update_A!(reg, Y; kwargs...)
     return nothing
 end
 
 function release!(model)
     haskey(CTX, model) && (ccall((:pmf_destroy, LIB[]), Cint, (Ptr{Cvoid},), CTX[model]); delete!(CTX, model))
-    delete!(DATA_KEY, model); delete!(OPT_KEY, model)
+    delete!(DATA_KEY, model); delete!(OPT_KEY, model); delete!(FSARD_DATA, model)
     return nothing
 end
 
