@@ -10,6 +10,8 @@
 //   k_stage_group         per noise range K mean(sigma^2) / (sum_j var_j n_j / M)                 (construct_minimal_regularizer)
 //   k_em_moments          per (view, batch) row: mean / sample variance of theta, (alpha, beta) of delta^2 (theta_mom, delta2_mom)
 //   k_em_theta            the theta update, with the partial sums of the stopping rule            (theta_delta_em :350, :363)
+//                         (theta lives in f64 for the length of the EM, as in fit.py and like delta^2: the moments and the
+//                         stopping rule read that copy; the f32 parameter, which the statistics pass reads, is its rounding)
 //   k_em_diff             the two sums of the stopping rule, one workgroup, index order
 //   k_em_delta2           the delta^2 update                                                      (:359)
 // Sums: per thread over its strided elements, lanes by shuffles, the four waves in index order, workgroups through a slab
@@ -171,7 +173,7 @@ __device__ __forceinline__ void em_row_moments(const T *__restrict__ x, int64_t 
   var = st_block_sum(q, sh) / (double)(Nv - 1);   // N_v = 1: 0 / 0 = NaN, absorbed by the updates' NaN rules
 }
 // mom = [theta mean | theta var | alpha | beta], n_rows doubles each
-__global__ __launch_bounds__(256) void k_em_moments(const float *__restrict__ theta, const double *__restrict__ delta2,
+__global__ __launch_bounds__(256) void k_em_moments(const double *__restrict__ theta, const double *__restrict__ delta2,
                                                      const EmGeom g, int64_t n_rows, double *__restrict__ mom) {
   __shared__ double sh[4];
   const int64_t r = blockIdx.x;
@@ -190,7 +192,8 @@ __global__ __launch_bounds__(256) void k_em_moments(const float *__restrict__ th
   }
 }
 struct EmArgs {
-  float *theta, *theta_old;
+  float *theta;          // the parameter: the rounding of theta64, read by the statistics pass
+  double *theta64;       // theta for the length of the EM
   const float *theta_lsq, *sigma2;
   double *delta2;
   const double *bcount, *bsq, *mom;
@@ -214,9 +217,9 @@ __global__ __launch_bounds__(256) void k_em_theta(const EmArgs a) {
   for (int64_t q = blockIdx.x * 256ll + threadIdx.x; q < nq; q += (int64_t)gridDim.x * 256) {
     const int64_t e0 = 4 * q;
     const int cnt = (int)(a.nbt - e0 < 4 ? a.nbt - e0 : 4);
-    float to[4], lsq[4], tn[4];
-    double d2[4], bs[4];
-    st_ld4(a.theta, e0, cnt, true, to);
+    float lsq[4], tn[4];
+    double to[4], t64[4], d2[4], bs[4];
+    st_ld4(a.theta64, e0, cnt, true, to);
     st_ld4(a.theta_lsq, e0, cnt, true, lsq);
     st_ld4(a.delta2, e0, cnt, true, d2);
     st_ld4(a.bcount, e0, cnt, true, bs);
@@ -226,12 +229,13 @@ __global__ __launch_bounds__(256) void k_em_theta(const EmArgs a) {
       const double mean = a.mom[row], var = a.mom[a.n_rows + row], s2 = (double)a.sigma2[col];
       double t = (mean * d2[k] * s2 + (double)lsq[k] * bs[k] * var) / (s2 * d2[k] + bs[k] * var);
       if (!st_finite(t)) t = 0.0;
+      t64[k] = t;
       tn[k] = (float)t;
-      const double d = (double)tn[k] - (double)to[k];
+      const double d = t - to[k];
       num += d * d;
-      den += (double)tn[k] * (double)tn[k];
+      den += t * t;
     }
-    st_st4(a.theta_old, e0, cnt, true, to);
+    st_st4(a.theta64, e0, cnt, true, t64);
     st_st4(a.theta, e0, cnt, true, tn);
   }
   const double sn = st_block_sum(num, sh), sd = st_block_sum(den, sh);
@@ -373,13 +377,13 @@ extern "C" int pmf_stage_minimal_group_weights(pmf_ctx *c, int64_t M_total, floa
 }
 
 struct EmBufs {   // what one pmf_stage_theta_delta_em call owns
-  DevBuf<float> d_sigma2, theta_lsq, theta_old;
-  DevBuf<double> d_delta2, bcount, bsq, mom, part, d_diff;
+  DevBuf<float> d_sigma2, theta_lsq;
+  DevBuf<double> d_delta2, theta64, bcount, bsq, mom, part, d_diff;
   PinnedBuf<double> h_diff;
   int alloc(int64_t N, int64_t nbt, int64_t n_rows) {
     PMFCHK(d_sigma2.alloc((size_t)N));
     PMFCHK(theta_lsq.alloc((size_t)nbt));
-    PMFCHK(theta_old.alloc((size_t)nbt));
+    PMFCHK(theta64.alloc((size_t)nbt));
     PMFCHK(d_delta2.alloc((size_t)nbt));
     PMFCHK(bcount.alloc((size_t)nbt));
     PMFCHK(bsq.alloc((size_t)nbt));
@@ -393,20 +397,22 @@ struct EmBufs {   // what one pmf_stage_theta_delta_em call owns
 static int em_body(pmf_ctx *c, const pmf_em_opts *o, const float *sigma2, double *delta2, pmf_em_result *res, EmBufs &B) {
   const auto t0 = std::chrono::steady_clock::now();
   const int64_t nbt = c->val_off[c->n_bv], n_rows = c->bvb_off[c->n_bv];
-  DevBuf<float> &d_sigma2 = B.d_sigma2, &theta_lsq = B.theta_lsq, &theta_old = B.theta_old;
-  DevBuf<double> &d_delta2 = B.d_delta2, &bcount = B.bcount, &bsq = B.bsq, &mom = B.mom, &part = B.part, &d_diff = B.d_diff;
+  DevBuf<float> &d_sigma2 = B.d_sigma2, &theta_lsq = B.theta_lsq;
+  DevBuf<double> &theta64 = B.theta64, &d_delta2 = B.d_delta2, &bcount = B.bcount, &bsq = B.bsq, &mom = B.mom, &part = B.part, &d_diff = B.d_diff;
   PinnedBuf<double> &h_diff = B.h_diff;
   HIPCHK(hipMemcpyAsync(d_sigma2.p, sigma2, sizeof(float) * (size_t)c->N, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(d_delta2.p, delta2, sizeof(double) * (size_t)nbt, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(theta_lsq.p, c->P[5].p, sizeof(float) * (size_t)nbt, hipMemcpyDeviceToDevice, c->stream));
   EmArgs a;
   memset(&a, 0, sizeof(a));
-  a.theta = c->P[5].p; a.theta_old = theta_old.p; a.theta_lsq = theta_lsq.p; a.sigma2 = d_sigma2.p; a.delta2 = d_delta2.p;
+  a.theta = c->P[5].p; a.theta64 = theta64.p; a.theta_lsq = theta_lsq.p; a.sigma2 = d_sigma2.p; a.delta2 = d_delta2.p;
   a.bcount = bcount.p; a.bsq = bsq.p; a.mom = mom.p; a.val_view = c->d_val_view; a.part = part.p; a.nbt = nbt; a.n_rows = n_rows;
   a.g.n_bv = c->n_bv;
   for (int v = 0; v < c->n_bv; ++v) a.g.views[v] = c->views[v];
   for (int v = 0; v <= c->n_bv; ++v) { a.g.val_off[v] = c->val_off[v]; a.g.bvb_off[v] = c->bvb_off[v]; }
   const int nblk = (int)std::min<int64_t>(ST_MAXB, st_grid4(nbt));
+  k_st_widen<<<st_grid4(nbt), 256, 0, c->stream>>>(c->P[5].p, theta64.p, nbt, st_aligned16(c->P[5].p) ? 1 : 0);
+  HIPCHK(hipGetLastError());
   // the batch sizes, once, at the incoming parameters (:332)
   const float *bst = nullptr;
   PMFCHK(stats_pass(c, 1, false, true, nullptr, &bst));
@@ -415,7 +421,7 @@ static int em_body(pmf_ctx *c, const pmf_em_opts *o, const float *sigma2, double
   res->n_diffs = 0;
   for (int it = 1; it <= o->max_iter; ++it) {
     if (o->update_priors || it == 1) {
-      k_em_moments<<<(unsigned)n_rows, 256, 0, c->stream>>>(c->P[5].p, d_delta2.p, a.g, n_rows, mom.p);
+      k_em_moments<<<(unsigned)n_rows, 256, 0, c->stream>>>(theta64.p, d_delta2.p, a.g, n_rows, mom.p);
       HIPCHK(hipGetLastError());
     }
     k_em_theta<<<nblk, 256, 0, c->stream>>>(a);

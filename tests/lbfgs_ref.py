@@ -41,13 +41,43 @@ CASES = [
          problem=dict(M=37, N=29, K=33, seed=4, nan_frac=0.1, xreg="l2", yreg="group", random_init=True)),
 ]
 
-# (K, M, N) of the direction checks: one element; pad rows live; several workgroups and grid strides
+# (K, M, N) of the direction checks: one element; pad rows live; several workgroups (500 of the 1024 a grid holds: no
+# grid-stride trip -- EDGE_DIRECTIONS below has those)
 DIRECTION_SHAPES = [(1, 1, 1), (33, 7, 5), (64, 5000, 3000)]
 DIRECTION_PAIRS = [0, 1, 10]
 
+# (K, M, N, n_pairs) past one grid and at full history.  A vector has 32 ceil(K / 32) (M + N) floats; a grid of 1024
+# workgroups x 256 threads x 4 floats covers 1,048,576 of them, longer vectors take grid-stride trips.
+EDGE_DIRECTIONS = [
+    (32, 20000, 13000, 0), (32, 20000, 13000, 2),   # 1,056,000 floats: a second trip for the first workgroups only
+    (64, 20000, 13000, 1),                          # a third trip
+    (32, 1, 33000, 3), (32, 33000, 1, 3),           # the X / Y seam one column from either end
+    (1, 16400, 16400, 2),                           # K = 1: 31 pad rows per column
+    (33, 7, 5, 32), (64, 5000, 3000, 32),           # full history (LB_MAX_M pairs: 65 sweeps)
+    (32, 8193, 24600, 32),                          # ... beyond one grid
+]
+# 10 x the f32 twin's worst deviation over EDGE_DIRECTIONS, 4.62e-7 at the last row (tests/test_lbfgs_host.py)
+DIR_TOL_EDGE = 5e-6
+
+# trajectories (same record as CASES, MAX_ITER iterations) at the decisions CASES does not take: a vector beyond one grid
+# with a reset, a reset at every iteration, the non-descent fallback, a wrapping m = 2 queue.  sy_min absent: the default.
+EDGE_CASES = [
+    dict(name="wide_k32", m=3, backtrack_max_iter=100,
+         problem=dict(M=2, N=33000, K=32, seed=6, nan_frac=0.1, xreg="l2", yreg="group", random_init=True)),
+    dict(name="reset_every", m=10, backtrack_max_iter=100, sy_min=1e30,
+         problem=dict(M=40, N=33, K=2, seed=3, xreg="l2", yreg="l2", random_init=True)),
+    dict(name="non_descent", m=10, backtrack_max_iter=2, sy_min=-1e30,
+         problem=dict(M=40, N=33, K=2, seed=11, xreg="l2", yreg="l2", random_init=True)),
+    dict(name="m2_wrap", m=2, backtrack_max_iter=100,
+         problem=dict(M=48, N=36, K=3, seed=1, xreg="l2", yreg="l2", random_init=True)),
+]
+# 10 x the twin's worst relative loss deviation over the case's horizon (floor 2e-6), measured by tests/test_lbfgs_host.py:
+# 3.49e-5, 1.94e-5, 1.99e-5, 4.18e-5 in the order above
+LOSS_TOL_EDGE = {"wide_k32": 3.5e-4, "reset_every": 2e-4, "non_descent": 2e-4, "m2_wrap": 4.2e-4}
+
 
 def case_by_name(name):
-    return next(c for c in CASES if c["name"] == name)
+    return next(c for c in CASES + EDGE_CASES if c["name"] == name)
 
 
 def inner(a, b):
@@ -116,8 +146,9 @@ def fit_lbfgs(fun, X0, Y0, real=np.float64, m=10, max_iter=1000, backtrack_max_i
         else:
             p = (-g[0], -g[1])
             sq, yq = [], []
-            flags |= 1
-            out["resets"] += 1
+            if old_grad is not None:    # a reset forgets a history: on the first iteration there is none (sy_min >= 1)
+                flags |= 1
+                out["resets"] += 1
         qlen = len(sq)
         # backtrack!
         p_norm = np.sqrt(inner(p, p))
@@ -205,8 +236,9 @@ def case_run(name, precision):
         p = make_problem(**c["problem"])
         fun, _ = oracle_fun(p, precision)
         real = np.float64 if precision == 64 else np.float32
+        kw = dict(sy_min=c["sy_min"]) if "sy_min" in c else {}
         _RUNS[key] = (p, fit_lbfgs(fun, p["X"], p["Y"], real=real, m=c["m"], max_iter=MAX_ITER,
-                                   backtrack_max_iter=c["backtrack_max_iter"], rel_tol=0.0, abs_tol=0.0))
+                                   backtrack_max_iter=c["backtrack_max_iter"], rel_tol=0.0, abs_tol=0.0, **kw))
     return _RUNS[key]
 
 

@@ -130,6 +130,64 @@ def test_direction_tolerance_constant():
     assert R.DIR_TOL >= 2e-6 and worst <= R.DIR_TOL / 10
 
 
+# ---- the edge tables: what each case is there for, and the tolerance constants of tests/test_gpu_lbfgs_edges.py
+def test_first_iteration_is_no_reset():
+    # sy_min >= 1 fails the reset test on the first iteration too (sy = 1 without a pair): the direction is -g as ever, but
+    # with no history to forget neither the flag nor the count moves
+    rng = np.random.default_rng(0)
+    a = (1.0 + 9.0 * rng.random((2, 5)), 1.0 + 9.0 * rng.random((2, 4)))
+    X0, Y0 = rng.standard_normal((2, 5)), rng.standard_normal((2, 4))
+    r = R.fit_lbfgs(quad(a), X0, Y0, max_iter=4, sy_min=1e30, abs_tol=0, rel_tol=0)
+    assert r["flags"].tolist() == [0, 1, 1, 1] and r["resets"] == 3
+    assert [l["qlen"] for l in r["log"]] == [0, 0, 0, 0]
+    g = quad(a)(X0, Y0)[1]
+    assert np.array_equal(r["log"][0]["p_first"][0], -g[0]) and np.array_equal(r["log"][0]["p_first"][1], -g[1])
+    r1 = R.fit_lbfgs(quad(a), X0, Y0, max_iter=1, sy_min=1.0, abs_tol=0, rel_tol=0)      # sy = 1 > 1 fails as well
+    assert r1["flags"].tolist() == [0] and r1["resets"] == 0
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in R.EDGE_CASES])
+def test_edge_case_horizon_and_twin(name):
+    c = R.case_by_name(name)
+    assert c["problem"]["random_init"]
+    _, r64 = R.case_run(name, 64)
+    _, r32 = R.case_run(name, 32)
+    h = R.horizon(r64)
+    assert h >= R.MIN_HORIZON, (h, r64["margin"])
+    assert len(r32["loss"]) >= h
+    np.testing.assert_array_equal(r32["trials"][:h], r64["trials"][:h])
+    np.testing.assert_array_equal(r32["flags"][:h], r64["flags"][:h])
+    dev = float(np.max(np.abs(r32["loss"][:h] - r64["loss"][:h]) / np.abs(r64["loss"][:h])))
+    print(f"{name}: horizon {h}, flags {r64['flags'][:h].tolist()}, twin loss deviation {dev:.3g}, "
+          f"tolerance {R.LOSS_TOL_EDGE[name]:.3g}")
+    assert R.LOSS_TOL_EDGE[name] >= 2e-6 and dev <= R.LOSS_TOL_EDGE[name] / 10
+    fl, q = r64["flags"][:h], [l["qlen"] for l in r64["log"][:h]]
+    if name == "wide_k32":
+        p = c["problem"]
+        assert 32 * (p["M"] + p["N"]) > 1024 * 256 * 4             # beyond one grid of four-element threads
+        assert (fl[1:] & 1).any() and max(q) == c["m"]             # a reset and a full queue inside the horizon
+    if name == "reset_every":
+        assert fl[0] == 0 and (fl[1:] & 1).all() and max(q) == 0 and int((fl & 1).sum()) == h - 1
+    if name == "non_descent":
+        assert (fl & 2).any() and ((fl & 6) == 6).any()            # dd >= 0, once together with an exhausted backtrack
+    if name == "m2_wrap":
+        assert c["m"] == 2 and q[2:] == [2] * (h - 2) and h - 3 >= 6   # every push from the fourth iteration evicts a pair
+
+
+def test_edge_direction_tolerance_constant():
+    worst, shapes = 0.0, set()
+    for K, M, N, n in R.EDGE_DIRECTIONS:
+        g, s, y = R.random_history(K, M, N, n, seed=K + n)
+        p64, p32 = R.two_loop(g, s, y, np.float64), R.two_loop(g, s, y, np.float32)
+        num = max(float(np.max(np.abs(p32[i] - p64[i]))) for i in (0, 1))
+        den = max(float(np.max(np.abs(p64[i]))) for i in (0, 1))
+        worst = max(worst, num / den)
+        shapes.add((32 * -(-K // 32) * (M + N) > 1024 * 256 * 4, n == 32))
+    print(f"edge directions: twin deviation {worst:.3g}, tolerance {R.DIR_TOL_EDGE:.3g}")
+    assert R.DIR_TOL_EDGE >= 2e-6 and worst <= R.DIR_TOL_EDGE / 10
+    assert shapes == {(True, False), (False, True), (True, True)}  # beyond one grid, full history, and both at once
+
+
 # ---- ABI
 def test_lbfgs_struct_sizes(pkg):
     # pmf_lbfgs_opts: 6 int32 + 5 double ; pmf_lbfgs_result: 8 int32 + 2 double + 3 pointers
