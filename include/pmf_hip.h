@@ -460,6 +460,54 @@ int pmf_stage_minimal_group_weights(pmf_ctx *ctx, int64_t M_total, float *w_out)
 int pmf_stage_theta_delta_em(pmf_ctx *ctx, const pmf_em_opts *opts, const float *sigma2, double *delta2,
                              pmf_em_result *result);
 
+/* The factor post-processing stages that fit! runs between the gradient-descent stages, each as ONE call on the context's
+ * resident X (K x M, the local rows) and Y (K x N).  Every sum is float64 with a fixed order (no atomics): an output is bitwise
+ * the same run to run.  Every store of a float32 is ONE rounding of a float64 result (pmf_stage_whiten stores Y twice, where
+ * the host stores it: see below).  With a communicator of more than one rank the
+ * X-side sums are summed over the ranks in float64, in ONE collective per call, before any arithmetic; Y is replicated, so the
+ * Y-side calls issue no collective and every rank computes the same bits.  Column ranges are 1-based and inclusive, disjoint
+ * and ascending (gaps allowed).  The symmetric eigen-decomposition is the library's own cyclic Jacobi (no LAPACK): eigenvalues
+ * descending, ties by original index; each eigenvector signed so that its largest-magnitude component is positive, ties by
+ * lowest index; singular values sqrt(max(lambda, 0)).
+ *   pmf_gram                        : G_g = P[:, a_g..b_g] P[:, a_g..b_g]' of P = X (which = 0) or Y (1): n_groups x K x K doubles,
+ *                                     or with diag_only the n_groups x K diagonals (bitwise the diagonal of the full result).  A
+ *                                     group a..a-1 has no columns (a row-sharded group without local rows) and gives zeros.
+ *                                     X on more than one rank: the sums over all ranks (one collective).
+ *   pmf_stage_lambda_max            : the largest eigenvalue of each group's (reduced) Gram matrix = the largest squared singular
+ *                                     value of the block, by which reweight_eb! of L2Regularizer (one group, every column) and
+ *                                     GroupRegularizer divide mixture_p (src/regularizers.jl:39-47, 406-420).  One collective on X.
+ *   pmf_stage_whiten                : whiten! (src/fit.jl:504-527).  x_rms[k] = sqrt(sum_i X[k,i]^2 / M_total) (:505, one
+ *                                     collective); X[k,:] /= x_rms[k] (:506); Y[k,:] *= x_rms[k] (:507); per view range
+ *                                     c = max_k rms(Y[k, range]) of the rescaled Y (:513-517); c > 0: Y[:, range] /= c and
+ *                                     logsigma[range] += log c (:519-520), else Y[:, range] = 0 and logsigma[range] = -1e9
+ *                                     (:522-523).  Every step is float64 arithmetic that rounds once where it stores, in the
+ *                                     host's order (Y is stored after :507 and again after :519); c is taken from the float64
+ *                                     products Y * x_rms, so logsigma does not inherit Y's rounding.  IEEE results are kept: an
+ *                                     all-zero factor of X gives NaN in that row of X and leaves Y's row zero.  Outputs (either
+ *                                     may be NULL): x_rms[K], c[n_views].
+ *   pmf_stage_rotate_by_svd         : rotate_by_svd! (src/fit.jl:530-543) through the Gram matrix: Y Y' = U S^2 U', Y <- U'Y (= S Vt,
+ *                                     :538), X <- U'X (X' <- X'U, :541).  No collective.  Outputs (either may be NULL): the K
+ *                                     singular values; U, K x K row-major, U[k*K + r] = component k of singular vector r.
+ *   pmf_stage_reorder_by_importance : reorder_by_importance! (src/fit.jl:546-555): the rows of X and Y in the stable descending order
+ *                                     of sum_j Y[k,j]^2 (:549).  perm_out[r] (0-based, K entries) = the old row now at r: the host
+ *                                     permutes its regularizers with it (reorder_reg!, :552-553).  No collective.
+ * Each entry invalidates the prepared column parameters where it rewrote logsigma (the split-precision images of X and Y are
+ * rebuilt by every data pass).  None touches a gradient, the optimizer state, Adam's powers, the learning rate, the noise
+ * weights or a layer parameter other than logsigma.
+ * Refused before anything is launched (the context and the communicator stay usable): no data or factors; n_groups < 1; a range
+ * outside the matrix; overlapping or descending ranges; M_total below the context's row count; a NULL required pointer.  A call
+ * that fails after its first launch drains both streams and marks a communicator of more than one rank unusable. */
+int pmf_gram(pmf_ctx *ctx, int which, int n_groups, const int64_t *starts1, const int64_t *stops1, int diag_only, double *out);
+int pmf_stage_lambda_max(pmf_ctx *ctx, int which, int n_groups, const int64_t *starts1, const int64_t *stops1, double *lam_out);
+int pmf_stage_whiten(pmf_ctx *ctx, int64_t M_total, int n_views, const int64_t *starts1, const int64_t *stops1,
+                     double *x_rms_out, double *y_rms_max_out);
+int pmf_stage_rotate_by_svd(pmf_ctx *ctx, double *sing_out, double *U_out);
+int pmf_stage_reorder_by_importance(pmf_ctx *ctx, int32_t *perm_out);
+/* host-clock seconds of the phases of the last of the five calls above on this context, each phase closed by a stream
+ * synchronisation: the Gram / diagonal passes (with their collective and download), the eigen-solver, and the kernels that
+ * rewrite X, Y and logsigma.  Any pointer may be NULL.  (scripts/kbench_postprocess.py) */
+int pmf_debug_postprocess_times(pmf_ctx *ctx, double *gram_s, double *eig_s, double *apply_s);
+
 /* FeatureSetARD outer loop, one view: update_A! / update_A_inner! (src/featureset_ard.jl:214-294) with ISTAOptimiser.update!
  * (src/optimizers.jl:26-62) and gamma_normal_loss + its pull-back (:154-186), run on the device against the context's
  * resident Y (columns col_start1:col_stop1 = the view's col_range).  A starts from 0 (:286); S is the view's L x N_v

@@ -99,6 +99,8 @@ EXPORTS = [
     "pmf_loss", "pmf_fit_lbfgs", "pmf_debug_lbfgs_direction",
     "pmf_stage_init_logsigma", "pmf_stage_reweight_col_losses", "pmf_get_noise_weights", "pmf_stage_minimal_group_weights",
     "pmf_stage_theta_delta_em",
+    "pmf_gram", "pmf_stage_lambda_max", "pmf_stage_whiten", "pmf_stage_rotate_by_svd", "pmf_stage_reorder_by_importance",
+    "pmf_debug_postprocess_times",
 ]
 
 COMM_ID_BYTES = 128
@@ -649,6 +651,51 @@ class Context:
             off += nb * nv
         theta = [self.get_batch_view(v)[1] for v in range(len(self.view_shapes))]
         return dict(theta=theta, delta2=out, diffs=diffs[:r.n_diffs].copy(), iters=r.iters, seconds=r.seconds)
+
+    # ---- the factor post-processing stages in the library: X and Y never leave the device
+    @staticmethod
+    def _dp(a):
+        return a.ctypes.data_as(C.POINTER(C.c_double))
+
+    def gram(self, which, ranges, diag_only=False):
+        """pmf_gram of X (which = 0) or Y (1) over 1-based inclusive column ranges: (n_groups, K, K) float64, or with
+        diag_only (n_groups, K).  X on a communicator of more than one rank: summed over the ranks."""
+        s, e = _ranges(ranges)
+        out = np.zeros((len(s), self.K) if diag_only else (len(s), self.K, self.K), np.float64)
+        self._chk(self.lib.pmf_gram(self._h, int(which), len(s), _i64p(s), _i64p(e), int(bool(diag_only)), self._dp(out)))
+        return out
+
+    def stage_lambda_max(self, which, ranges):
+        """pmf_stage_lambda_max: the largest eigenvalue of each range's Gram matrix (float64)."""
+        s, e = _ranges(ranges)
+        lam = np.zeros(max(len(s), 1), np.float64)
+        self._chk(self.lib.pmf_stage_lambda_max(self._h, int(which), len(s), _i64p(s), _i64p(e), self._dp(lam)))
+        return lam[:len(s)]
+
+    def stage_whiten(self, M_total, view_ranges):
+        """pmf_stage_whiten on the context's X, Y and logsigma.  Returns (x_rms [K], y_rms_max [views])."""
+        s, e = _ranges(view_ranges)
+        xr, c = np.zeros(max(self.K, 1), np.float64), np.zeros(max(len(s), 1), np.float64)
+        self._chk(self.lib.pmf_stage_whiten(self._h, C.c_int64(int(M_total)), len(s), _i64p(s), _i64p(e), self._dp(xr), self._dp(c)))
+        return xr[:self.K], c[:len(s)]
+
+    def stage_rotate_by_svd(self):
+        """pmf_stage_rotate_by_svd on the context's X and Y.  Returns (singular values [K], U [K x K], U[:, r] the r-th vector)."""
+        sing, U = np.zeros(max(self.K, 1), np.float64), np.zeros((max(self.K, 1),) * 2, np.float64)
+        self._chk(self.lib.pmf_stage_rotate_by_svd(self._h, self._dp(sing), self._dp(U)))
+        return sing[:self.K], U[:self.K, :self.K]
+
+    def stage_reorder_by_importance(self):
+        """pmf_stage_reorder_by_importance on the context's X and Y.  Returns the 0-based permutation (new row r = old row p[r])."""
+        p = np.zeros(max(self.K, 1), np.int32)
+        self._chk(self.lib.pmf_stage_reorder_by_importance(self._h, p.ctypes.data_as(C.POINTER(C.c_int32))))
+        return p[:self.K].astype(np.int64)
+
+    def postprocess_times(self):
+        """pmf_debug_postprocess_times: dict(gram, eig, apply) seconds of the last post-processing call's phases."""
+        g, e, a = C.c_double(0), C.c_double(0), C.c_double(0)
+        self._chk(self.lib.pmf_debug_postprocess_times(self._h, C.byref(g), C.byref(e), C.byref(a)))
+        return dict(gram=g.value, eig=e.value, apply=a.value)
 
     # ---- multi-GPU
     def comm_init(self, rank, nranks, unique_id):

@@ -6,6 +6,7 @@
 //   pmf_netreg.hip    NetworkRegularizer (per-factor CG solve + sparse gradient) and the L1 / SelectiveL1 weights
 //   pmf_lbfgs.hip     L-BFGS over (X, Y): total gradient, history, two-loop recursion, backtracking (pmf_fit_lbfgs)
 //   pmf_stages.hip    the closed-form stages between the GD stages on the device statistics (pmf_stage_*)
+//   pmf_postprocess.hip  the factor post-processing stages (whiten, rotate_by_svd, reorder, lambda_max) on the resident X, Y
 #ifndef PMF_CTX_H
 #define PMF_CTX_H
 #include <hip/hip_runtime.h>
@@ -207,6 +208,7 @@ struct pmf_ctx {
   // largest dynamic-LDS size set so far per kernel ON THIS CONTEXT'S DEVICE (hipFuncSetAttribute is per device: a
   // process-wide cache would leave a second GPU's kernels without the attribute)
   PmfDynLds dyn_lds;
+  double pp_seconds[3] = {0.0, 0.0, 0.0};   // phases of the last post-processing call (pmf_postprocess.hip, PpClock)
   struct LbfgsState *lbfgs = nullptr;   // vectors and scalars of pmf_fit_lbfgs (pmf_lbfgs.hip), allocated on its first call
 };
 
@@ -245,6 +247,32 @@ static void dev_free(T **p) {
   if (*p) (void)hipFree(*p);
   *p = nullptr;
 }
+
+// device / pinned host memory owned for the duration of a call (pmf_stages.hip, pmf_postprocess.hip)
+template <typename T>
+struct DevBuf {
+  T *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  int alloc(size_t n) {
+    HIPCHK(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)));
+    return 0;
+  }
+};
+template <typename T>
+struct PinnedBuf {
+  T *p = nullptr;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf &) = delete;
+  PinnedBuf &operator=(const PinnedBuf &) = delete;
+  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+  int alloc(size_t n) {
+    HIPCHK(hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)));
+    return 0;
+  }
+};
 
 __device__ __forceinline__ double block_reduce_sum(double v, double *sh) {
 #pragma unroll

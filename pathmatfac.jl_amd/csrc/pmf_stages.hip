@@ -19,32 +19,6 @@
 // holding the same reduced statistics and the same replicated parameters -- rank to rank.
 #include "pmf_ctx.h"
 
-// device / pinned host memory owned for the duration of a call
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    HIPCHK(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)));
-    return 0;
-  }
-};
-template <typename T>
-struct PinnedBuf {
-  T *p = nullptr;
-  PinnedBuf() = default;
-  PinnedBuf(const PinnedBuf &) = delete;
-  PinnedBuf &operator=(const PinnedBuf &) = delete;
-  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-  int alloc(size_t n) {
-    HIPCHK(hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)));
-    return 0;
-  }
-};
-
 static inline unsigned st_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + 255) / 256); }
 #define ST_MAXB 1024   // workgroups of the theta update at most = partials per sum of the stopping rule
 

@@ -162,6 +162,22 @@ def _library_stage_context(model, stages, device=0):
     return ctx
 
 
+def _postprocess_context(model, postprocess, device=0):
+    """`postprocess` = "host" (None: numpy / LAPACK on the downloaded factors) or "library" (the model marshalled once, for
+    one post-processing call on its device context: pmf_stage_whiten, _rotate_by_svd, _reorder_by_importance, _lambda_max)."""
+    if postprocess == "host":
+        return None
+    if postprocess != "library":
+        raise ValueError(f"postprocess={postprocess!r}: 'host' or 'library'")
+    if model.sharded and model._allreduce_fn is not None:
+        raise ValueError("postprocess='library' on a row-sharded model whose reducer was replaced by model.set_allreduce: "
+                         "the library sums the X-side sums over the ranks through its own communicator and has none here "
+                         "(use postprocess='host', or attach_comm and set_allreduce(None))")
+    ctx = model.device_context(device)
+    MF.marshal(model.matfac, ctx, with_xreg=False, with_yreg=False)
+    return ctx
+
+
 def init_mu_(model, capacity=int(10e8), lr_mu=0.1, max_epochs=500, verbosity=1, print_prefix="", history=None,
              **kwargs):
     """init_mu! (src/fit.jl:82-103): mu <- per-column M-estimates argmin_m sum_i loss(m, D_ij), found by AdaGrad on mu
@@ -397,10 +413,21 @@ def rms(X, axis):
     return np.sqrt(np.mean(X * X, axis=axis, keepdims=True))
 
 
-def whiten_(model):
+def whiten_(model, postprocess="host"):
     """whiten! (src/fit.jl:504-527).  Row-sharded: the K row sums of squares of X are summed over the ranks and divided by
-    M_total; everything after that works on replicated arrays."""
+    M_total; everything after that works on replicated arrays.  `postprocess` = "library": one pmf_stage_whiten call on the
+    device copies; X, Y and logsigma come back."""
     mf = model.matfac
+    ctx = _postprocess_context(model, postprocess)
+    if ctx is not None:
+        ctx.stage_whiten(model.M_total, [(cr.start, cr.stop) for cr in ids_to_ranges(model.feature_views)])
+        X, Y = ctx.get_factors()
+        mf.X[...] = X
+        mf.Y[...] = Y
+        l1 = mf.col_transform.unwrapped(1)
+        if isinstance(l1, ColScale):
+            l1.logsigma[...] = ctx.get_col_params()[0]
+        return
     if model.sharded:
         X64 = mf.X.astype(np.float64)
         ssq = np.ascontiguousarray(np.sum(X64 * X64, axis=1))
@@ -422,11 +449,20 @@ def whiten_(model):
             ls[sl] = np.float32(-1e9)
 
 
-def rotate_by_svd_(model):
+def rotate_by_svd_(model, postprocess="host"):
     """rotate_by_svd! (src/fit.jl:530-543): Y <- S*Vt, X' <- X' * U.  Row-sharded: Y is replicated, so every rank could
     factor it, but two LAPACK builds or thread counts need not return the same bits: U and S*Vt are the root's, handed to
-    every rank in one collective of K * (K + N) doubles; X_local <- U' X_local."""
+    every rank in one collective of K * (K + N) doubles; X_local <- U' X_local.
+    `postprocess` = "library": one pmf_stage_rotate_by_svd call (the library's own eigen-decomposition of Y Y', identical on
+    every rank: no collective; its sign convention, not LAPACK's); X and Y come back."""
     mf = model.matfac
+    ctx = _postprocess_context(model, postprocess)
+    if ctx is not None:
+        ctx.stage_rotate_by_svd()
+        X, Y = ctx.get_factors()
+        mf.X[...] = X
+        mf.Y[...] = Y
+        return
     K, N = mf.Y.shape
     if model.sharded:
         buf = np.zeros(K * K + K * N)
@@ -443,12 +479,20 @@ def rotate_by_svd_(model):
     mf.X[...] = (mf.X.astype(np.float64).T @ U).T
 
 
-def reorder_by_importance_(model):
-    """reorder_by_importance! (src/fit.jl:546-555)."""
+def reorder_by_importance_(model, postprocess="host"):
+    """reorder_by_importance! (src/fit.jl:546-555).  `postprocess` = "library": one pmf_stage_reorder_by_importance call;
+    X, Y and the permutation come back, and the regularizers (host state) are permuted here with it."""
     mf = model.matfac
-    idx = np.argsort(-np.sum(mf.Y.astype(np.float64) ** 2, axis=1), kind="stable")
-    mf.X[...] = mf.X[idx, :]
-    mf.Y[...] = mf.Y[idx, :]
+    ctx = _postprocess_context(model, postprocess)
+    if ctx is not None:
+        idx = ctx.stage_reorder_by_importance()
+        X, Y = ctx.get_factors()
+        mf.X[...] = X
+        mf.Y[...] = Y
+    else:
+        idx = np.argsort(-np.sum(mf.Y.astype(np.float64) ** 2, axis=1), kind="stable")
+        mf.X[...] = mf.X[idx, :]
+        mf.Y[...] = mf.Y[idx, :]
     for reg in (mf.Y_reg, mf.X_reg):
         _reorder_reg(reg, idx)
 
@@ -511,10 +555,46 @@ def _reweight_eb_sharded_(model, reg, X, mixture_p):
                                   "GroupRegularizer and their composites have a sharded update")
 
 
-def reweight_eb_(reg, P, mixture_p=1.0, model=None):
+def _group_ranges_with_empties(reg):
+    """One 1-based inclusive LOCAL range per group of `reg`, in group order: a group without local rows becomes the empty
+    range a..a-1 right behind the range before it (pmf_stage_lambda_max: it contributes zeros to the sum over the ranks)."""
+    loc = {i: (a, b) for i, a, b in reg.local_groups()}
+    out, prev = [], 0
+    for i in range(len(reg.group_idx)):
+        a, b = loc.get(i, (prev + 1, prev))
+        out.append((a, b))
+        prev = max(prev, b)
+    return out
+
+
+def _reweight_eb_library_(model, ctx, which, reg, P, mixture_p):
+    """reweight_eb! with the largest eigenvalue of the block's Gram matrix from pmf_stage_lambda_max (X: summed over the row
+    shards in the library, one collective per call).  Only the lambda values come back.  Terms without a Gram matrix (ARD,
+    L1, SelectiveL1, Network) keep their host update."""
+    if isinstance(reg, L2Regularizer):
+        lam = ctx.stage_lambda_max(which, [(1, P.shape[1])])
+        reg.weights[...] = mixture_p / lam[0]
+    elif isinstance(reg, GroupRegularizer):
+        lam = ctx.stage_lambda_max(which, _group_ranges_with_empties(reg))
+        reg.group_weights = tuple(np.full(P.shape[0], mixture_p / l, dtype=np.float32) for l in lam)
+    elif isinstance(reg, _R.CompositeRegularizer):
+        for r, p in zip(reg.regularizers, reg.mixture_p):
+            _reweight_eb_library_(model, ctx, which, r, P, p * mixture_p)
+    else:
+        reweight_eb_(reg, P, mixture_p=mixture_p, model=model if which == 0 else None)
+
+
+def reweight_eb_(reg, P, mixture_p=1.0, model=None, postprocess="host"):
     """reweight_eb! for the regularizers in scope (regularizers.jl:39-47, 406-420, 588-609, 634-638): weights
     <- mixture_p / (largest squared singular value) of the (group's) parameter block.  `model`: the model whose X
-    regularizer `reg` is, P being its (local) X; only a row-sharded model changes the path (_reweight_eb_sharded_)."""
+    regularizer `reg` is, P being its (local) X; only a row-sharded model changes the path (_reweight_eb_sharded_).
+    `postprocess` = "library" (needs `model`; P is its X or its Y): the L2 / Group terms take their lambda from one
+    pmf_stage_lambda_max call each on the device copy of P."""
+    if postprocess != "host":
+        if model is None or not (P is model.matfac.X or P is model.matfac.Y):
+            raise ValueError("reweight_eb_(postprocess='library') needs model= and P = model.matfac.X or model.matfac.Y")
+        ctx = _postprocess_context(model, postprocess)
+        return _reweight_eb_library_(model, ctx, 0 if P is model.matfac.X else 1, reg, P, mixture_p)
     if model is not None and model.sharded:
         return _reweight_eb_sharded_(model, reg, P, mixture_p)
     if isinstance(reg, L2Regularizer):
@@ -590,8 +670,10 @@ def reweight_eb_(reg, P, mixture_p=1.0, model=None):
 def basic_fit_(model, fit_batch=False, batch_method="EM", fit_mu=False, fit_logsigma=False, reweight_losses=False,
                init_factors=False, init_factors_method="adagrad", fit_factors=False, init_ordinal=False,
                svd_rotate=False, whiten=False, capacity=int(10e8), lr=1.0, max_epochs=1000, verbosity=1,
-               print_prefix="", history=None, lr_regress=1.0, lr_mu=0.1, lr_theta=1.0, stages="host", **kwargs):
-    """basic_fit! (src/fit.jl:564-671).  `stages`: where the closed-form stages run ("host" / "library")."""
+               print_prefix="", history=None, lr_regress=1.0, lr_mu=0.1, lr_theta=1.0, stages="host", postprocess="host",
+               **kwargs):
+    """basic_fit! (src/fit.jl:564-671).  `stages`: where the closed-form stages run ("host" / "library"); `postprocess`:
+    where whiten! and rotate_by_svd! run (the same two values)."""
     n_prefix = print_prefix + "    "
     ct = model.matfac.col_transform
     if init_ordinal:
@@ -617,14 +699,14 @@ def basic_fit_(model, fit_batch=False, batch_method="EM", fit_mu=False, fit_logs
         mf_fit_adapt_lr_(model, capacity=capacity, update_X=True, update_Y=True, lr=lr, min_lr=0.05,
                          max_epochs=max_epochs, verbosity=verbosity, print_prefix=n_prefix, history=history, **kwargs)
     if whiten:
-        whiten_(model)
+        whiten_(model, postprocess=postprocess)
     if svd_rotate:
-        rotate_by_svd_(model)
+        rotate_by_svd_(model, postprocess=postprocess)
     unfreeze_layer_(ct, [1, 2, 3, 4])
 
 
 def fit_ard_(model, max_epochs=1000, capacity=10 ** 8, verbosity=1, print_prefix="", history=None, lr=1.0,
-             lr_regress=1.0, lr_theta=1.0, svd_rotate=True, batch_method="EM", stages="host", **kwargs):
+             lr_regress=1.0, lr_theta=1.0, svd_rotate=True, batch_method="EM", stages="host", postprocess="host", **kwargs):
     """fit_ard! (src/fit.jl:751-808)."""
     n_pref = print_prefix + "    "
     mf = model.matfac
@@ -635,11 +717,11 @@ def fit_ard_(model, max_epochs=1000, capacity=10 ** 8, verbosity=1, print_prefix
     basic_fit_(model, fit_batch=fit_batch, fit_mu=True, fit_logsigma=True, init_factors=True, reweight_losses=True,
                svd_rotate=svd_rotate, whiten=True, lr_regress=lr_regress, lr_theta=lr_theta, verbosity=verbosity,
                print_prefix=n_pref, batch_method=batch_method, max_epochs=max_epochs, capacity=capacity,
-               history=history, lr=lr, stages=stages, **kwargs)               # :773-787
+               history=history, lr=lr, stages=stages, postprocess=postprocess, **kwargs)   # :773-787
     mf.X_reg = orig_X_reg
-    reweight_eb_(mf.X_reg, mf.X, model=model)                                 # :791-792
+    reweight_eb_(mf.X_reg, mf.X, model=model, postprocess=postprocess)        # :791-792
     mf.Y_reg = orig_ard
-    reweight_eb_(mf.Y_reg, mf.Y)                                              # :793-794
+    reweight_eb_(mf.Y_reg, mf.Y, model=model if postprocess != "host" else None, postprocess=postprocess)   # :793-794
     reweight_col_losses_(model, capacity=capacity, stages=stages)             # :797
     mf_fit_adapt_lr_(model, capacity=capacity, update_X=True, update_Y=True, lr=lr, min_lr=0.01,
                      max_epochs=max_epochs, verbosity=verbosity, print_prefix=n_pref, history=history, **kwargs)  # :800
@@ -657,7 +739,7 @@ def fit_non_ard_(model, fit_reg_weight="EB", **kwargs):
 
 
 def basic_fit_reg_weight_eb_(model, capacity=int(10e8), lr=1.0, max_epochs=1000, verbosity=1, print_prefix="",
-                             history=None, svd_rotate=True, stages="host", **kwargs):
+                             history=None, svd_rotate=True, stages="host", postprocess="host", **kwargs):
     """basic_fit_reg_weight_eb! (src/fit.jl:674-727)."""
     n_pref = print_prefix + "    "
     mf = model.matfac
@@ -670,22 +752,23 @@ def basic_fit_reg_weight_eb_(model, capacity=int(10e8), lr=1.0, max_epochs=1000,
     fit_batch = isinstance(mf.col_transform.unwrapped(2), BatchScale)
     basic_fit_(model, fit_mu=True, fit_logsigma=True, reweight_losses=True, fit_batch=fit_batch, init_factors=True,
                svd_rotate=svd_rotate, whiten=False, verbosity=verbosity, print_prefix=n_pref, capacity=capacity,
-               lr=lr, max_epochs=max_epochs, history=history, stages=stages, **kwargs)   # :694-704
+               lr=lr, max_epochs=max_epochs, history=history, stages=stages, postprocess=postprocess, **kwargs)   # :694-704
     if isinstance(sr, SequenceReg):
         unfreeze_reg_(sr, [1, 2, 3, 4])                                        # :709
     mf.X_reg, mf.Y_reg = orig_X_reg, orig_Y_reg
     if isinstance(sr, SequenceReg):
         reweight_eb_(sr, mf.col_transform)                                     # :712
-    reweight_eb_(mf.X_reg, mf.X, model=model)                                  # :713
-    reweight_eb_(mf.Y_reg, mf.Y)                                               # :714
+    reweight_eb_(mf.X_reg, mf.X, model=model, postprocess=postprocess)         # :713
+    reweight_eb_(mf.Y_reg, mf.Y, model=model if postprocess != "host" else None, postprocess=postprocess)   # :714
     history_(history, name="reweight_eb")
     basic_fit_(model, reweight_losses=True, fit_factors=True, verbosity=verbosity, print_prefix=n_pref,
-               history=history, capacity=capacity, lr=lr, max_epochs=max_epochs, stages=stages, **kwargs)   # :720-725
+               history=history, capacity=capacity, lr=lr, max_epochs=max_epochs, stages=stages, postprocess=postprocess,
+               **kwargs)   # :720-725
 
 
 def fit_feature_set_ard_(model, lr=1.0, capacity=10 ** 8, max_epochs=1000, fsard_max_iter=10, fsard_max_A_iter=1000,
                          fsard_term_rtol=1e-5, verbosity=1, print_prefix="", svd_rotate=True, history=None, stages="host",
-                         **kwargs):
+                         postprocess="host", **kwargs):
     """fit_feature_set_ard! (src/fit.jl:814-892)."""
     from .featureset_ard import update_A_
     n_pref = print_prefix + "    "
@@ -693,7 +776,7 @@ def fit_feature_set_ard_(model, lr=1.0, capacity=10 ** 8, max_epochs=1000, fsard
     orig_reg = mf.Y_reg
     mf.Y_reg = ARDRegularizer(model.feature_views)                            # :829
     fit_ard_(model, max_epochs=max_epochs, capacity=capacity, lr=lr, verbosity=verbosity, print_prefix=n_pref,
-             history=history, svd_rotate=svd_rotate, stages=stages, **kwargs)  # :832
+             history=history, svd_rotate=svd_rotate, stages=stages, postprocess=postprocess, **kwargs)  # :832
     mf.Y_reg = orig_reg                                                        # :837
     beta_old = orig_reg.beta.copy()
     for it in range(1, fsard_max_iter + 1):
@@ -714,10 +797,14 @@ def fit_feature_set_ard_(model, lr=1.0, capacity=10 ** 8, max_epochs=1000, fsard
 
 def fit_(model, lr=1.0, fit_reg_weight="EB", n_lambda=8, lambda_max=None, lambda_min_frac=1e-3, keep_history=False,
          svd_rotate=True, fit_joint=False, fsard_max_iter=10, fsard_max_A_iter=1000, fsard_term_rtol=1e-5,
-         rel_tol=1e-5, abs_tol=1e-5, verbosity=1, print_prefix="", capacity=10 ** 8, stages="host", **kwargs):
+         rel_tol=1e-5, abs_tol=1e-5, verbosity=1, print_prefix="", capacity=10 ** 8, stages="host", postprocess="host",
+         **kwargs):
     """fit! (src/fit.jl:923-1018), the master function.  Returns the history list (or None).
     `stages`: "host" (default) runs the closed-form stages between the GD stages on statistics downloaded from the device,
-    "library" runs each of them as one pmf_stage_* call."""
+    "library" runs each of them as one pmf_stage_* call.
+    `postprocess`: "host" (default) runs whiten!, rotate_by_svd!, reorder_by_importance! and the L2 / Group reweight_eb! in
+    numpy on downloaded factors, "library" as one call each on the device copies (the singular
+    vectors then carry the library's sign convention, not LAPACK's).  The two keywords are independent."""
     global FIT_START_TIME
     FIT_START_TIME = time.time()
     hist = [] if keep_history else None
@@ -725,22 +812,24 @@ def fit_(model, lr=1.0, fit_reg_weight="EB", n_lambda=8, lambda_max=None, lambda
     mf = model.matfac
     if isinstance(mf.Y_reg, ARDRegularizer):
         fit_ard_(model, history=hist, verbosity=verbosity, print_prefix=print_prefix, rel_tol=rel_tol, abs_tol=abs_tol,
-                 capacity=capacity, svd_rotate=svd_rotate, lr=lr, stages=stages, **kwargs)
+                 capacity=capacity, svd_rotate=svd_rotate, lr=lr, stages=stages, postprocess=postprocess, **kwargs)
     elif isinstance(mf.Y_reg, FeatureSetARDReg):
         fit_feature_set_ard_(model, lr=lr, rel_tol=rel_tol, abs_tol=abs_tol, history=hist,
                              fsard_max_iter=fsard_max_iter, fsard_max_A_iter=fsard_max_A_iter,
                              fsard_term_rtol=fsard_term_rtol, svd_rotate=svd_rotate, verbosity=verbosity,
-                             print_prefix=print_prefix, capacity=capacity, stages=stages, **kwargs)
+                             print_prefix=print_prefix, capacity=capacity, stages=stages, postprocess=postprocess,
+                             **kwargs)
     else:
         fit_non_ard_(model, history=hist, rel_tol=rel_tol, abs_tol=abs_tol, fit_reg_weight=fit_reg_weight,
                      lambda_max=lambda_max, n_lambda=n_lambda, lambda_min_frac=lambda_min_frac, svd_rotate=svd_rotate,
-                     verbosity=verbosity, print_prefix=print_prefix, capacity=capacity, lr=lr, stages=stages, **kwargs)
+                     verbosity=verbosity, print_prefix=print_prefix, capacity=capacity, lr=lr, stages=stages,
+                     postprocess=postprocess, **kwargs)
     if fit_joint:
         # the reference's fit_joint branch references an undefined `max_epochs` (Q3, src/fit.jl:995): it cannot run there
         raise NotImplementedError("fit_joint=true is broken in the reference (src/fit.jl:995) and not reproduced")
-    whiten_(model)                                                             # :1004
+    whiten_(model, postprocess=postprocess)                                    # :1004
     reweight_col_losses_(model, capacity=capacity, history=hist, stages=stages)   # :1008
-    reorder_by_importance_(model)                                              # :1011
+    reorder_by_importance_(model, postprocess=postprocess)                     # :1011
     history_(hist, name="reorder_factors")
     history_(hist, name="finish")
     return hist

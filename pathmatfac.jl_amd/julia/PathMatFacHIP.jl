@@ -8,6 +8,8 @@
 # construct_minimal_regularizer, theta_delta_em, update_A!) are re-pointed too: each marshals the model, makes ONE library
 # call (pmf_stage_* / pmf_fsard_update_A; init_mu! goes through this file's mf_fit!) and copies back what changed.  The
 # moments block inside init_batch_effects! (src/fit.jl:444-462) keeps MatFac's CPU helpers.
+# So is the factor post-processing (whiten!, rotate_by_svd!, reorder_by_importance!, reweight_eb! of the L2 / Group terms):
+# one pmf_stage_whiten / _rotate_by_svd / _reorder_by_importance / _lambda_max call each.
 #
 # Usage:   using PathMatFac; include("PathMatFacHIP.jl"); PathMatFacHIP.install!("/path/to/libpmf_hip.so")
 #          model = PathMatFacModel(D; ...);  fit!(model; ...)         # no gpu(model): the library owns the device copy
@@ -569,6 +571,99 @@ function update_A!(reg::PM.FeatureSetARDReg, Y::AbstractMatrix; max_epochs=1000,
     reg.beta .= beta_all
 end
 
+# ---- factor post-processing, each ONE library call on the marshalled model (include/pmf_hip.h: pmf_stage_whiten, ----------
+# pmf_stage_rotate_by_svd, pmf_stage_reorder_by_importance, pmf_stage_lambda_max).  X and Y stay on the device for the
+# call; only what changed is copied back.  On a row-sharded model (comm_init!) the X-side sums are summed over the ranks
+# inside the library: whiten! takes M_total, the L2 / Group reweight_eb! of the X regularizer take `model`.
+const EB_DATA = IdDict{Any,Matrix{Float32}}()      # regularizer => the all-missing 1 x n matrix of its own context (reweight_eb!)
+
+function factors_from_device!(ctx, mf)
+    X, Y = similar(mf.X, Float32), similar(mf.Y, Float32)
+    GC.@preserve X Y chk(ccall((:pmf_get_factors, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}), ctx, X, Y))
+    mf.X .= X
+    mf.Y .= Y
+end
+
+"""Replacement for PathMatFac.whiten! (src/fit.jl:504-527): pmf_stage_whiten; X, Y and logsigma copied back.
+`M_total`: all samples when the rows are sharded over ranks."""
+function whiten!(model::PM.PathMatFacModel; M_total::Integer=size(model.data, 1))
+    ctx = context!(model)
+    mf = model.matfac
+    marshal!(ctx, mf; with_regs=false)
+    crs = PM.ids_to_ranges(model.feature_views)
+    s, e = starts(crs), stops(crs)
+    GC.@preserve s e chk(ccall((:pmf_stage_whiten, LIB[]), Cint,
+        (Ptr{Cvoid}, Int64, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ptr{Cdouble}), ctx, M_total, length(s), s, e, C_NULL, C_NULL))
+    factors_from_device!(ctx, mf)
+    l1 = unwrap(mf.col_transform.layers[1])
+    if isa(l1, PM.ColScale)
+        ls = zeros(Float32, size(mf.Y, 2))
+        GC.@preserve ls chk(ccall((:pmf_get_col_params, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}), ctx, ls, C_NULL))
+        l1.logsigma .= ls
+    end
+    return nothing
+end
+
+"""Replacement for PathMatFac.rotate_by_svd! (src/fit.jl:530-543): pmf_stage_rotate_by_svd (the library's own
+eigen-decomposition of Y Y'; each singular vector signed so that its largest component is positive); X and Y copied back."""
+function rotate_by_svd!(model::PM.PathMatFacModel)
+    ctx = context!(model)
+    marshal!(ctx, model.matfac; with_regs=false)
+    chk(ccall((:pmf_stage_rotate_by_svd, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), ctx, C_NULL, C_NULL))
+    factors_from_device!(ctx, model.matfac)
+    return nothing
+end
+
+"""Replacement for PathMatFac.reorder_by_importance! (src/fit.jl:546-555): pmf_stage_reorder_by_importance; X, Y and the
+permutation come back, the regularizers (host state) are permuted here (reorder_reg!, :553-554)."""
+function reorder_by_importance!(model::PM.PathMatFacModel)
+    ctx = context!(model)
+    mf = model.matfac
+    marshal!(ctx, mf; with_regs=false)
+    perm = zeros(Int32, size(mf.Y, 1))
+    GC.@preserve perm chk(ccall((:pmf_stage_reorder_by_importance, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Int32}), ctx, perm))
+    factors_from_device!(ctx, mf)
+    srt_idx = Int.(perm) .+ 1
+    PM.reorder_reg!(mf.Y_reg, srt_idx)
+    PM.reorder_reg!(mf.X_reg, srt_idx)
+    return nothing
+end
+
+# Largest eigenvalue of the Gram matrix of P[:, r] for every range r (= the largest squared singular value of the block).
+# With `model`, P must be its X or its Y: the model's context is used (X: summed over the row shards).  Without, P goes
+# to a context of the regularizer's own as the Y of an all-missing one-row data matrix, as update_A! does it.
+function lambda_max(reg, P::AbstractMatrix, ranges; model=nothing)
+    s, e = starts(ranges), stops(ranges)
+    lam = zeros(Cdouble, length(s))
+    if model !== nothing
+        which = P === model.matfac.X ? 0 : (P === model.matfac.Y ? 1 : error("lambda_max: P is neither model.matfac.X nor model.matfac.Y"))
+        ctx = context!(model)
+        marshal!(ctx, model.matfac; with_regs=false)
+    else
+        K, n = size(P)
+        ctx = data_context!(reg, get!(() -> fill(NaN32, 1, n), EB_DATA, reg))
+        X0, P32 = zeros(Float32, K, 1), f32(P)
+        GC.@preserve X0 P32 chk(ccall((:pmf_set_factors, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Cfloat}, Ptr{Cfloat}, Cint), ctx, X0, P32, K))
+        which = 1
+    end
+    GC.@preserve s e lam chk(ccall((:pmf_stage_lambda_max, LIB[]), Cint,
+        (Ptr{Cvoid}, Cint, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}), ctx, which, length(s), s, e, lam))
+    return lam
+end
+
+"""Replacement for PathMatFac.reweight_eb!(::L2Regularizer, ::AbstractMatrix) (src/regularizers.jl:39-47)."""
+function reweight_eb!(reg::PM.L2Regularizer, X::AbstractMatrix; mixture_p=Float32(1.0), model=nothing)
+    lam = lambda_max(reg, X, (1:size(X, 2),); model=model)
+    reg.weights .= mixture_p / lam[1]
+end
+
+"""Replacement for PathMatFac.reweight_eb!(::GroupRegularizer, ::AbstractMatrix) (src/regularizers.jl:406-420)."""
+function reweight_eb!(gr::PM.GroupRegularizer, X::AbstractMatrix; mixture_p=Float32(1.0), model=nothing)
+    K = size(X, 1)
+    lam = lambda_max(gr, X, gr.group_idx; model=model)
+    gr.group_weights = Tuple(fill!(similar(X, K), mixture_p / l) for l in lam)
+end
+
 """impute(model; include_batch_effects=false) (src/impute.jl:37-56) on the device: pmf_impute over the model's current
 parameters.  `link=true` returns Z itself, `keep_observed=true` returns the observed entries of model.data and predicts
 only the missing ones; `rows` (a UnitRange) bounds the host matrix.  Returns length(rows) x N Float32."""
@@ -594,12 +689,17 @@ function install!(libpath::AbstractString="libpmf_hip.so")
     @eval PathMatFac theta_delta_em(model::MF.MatFacModel, delta2::Tuple, sigma2::AbstractVector, data::AbstractMatrix; kwargs...) =
         Main.PathMatFacHIP.theta_delta_em(model, delta2, sigma2, data; kwargs...)
     @eval PathMatFac update_A!(reg::FeatureSetARDReg, Y::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.update_A!(reg, Y; kwargs...)
+    @eval PathMatFac whiten!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.whiten!(model; kwargs...)
+    @eval PathMatFac rotate_by_svd!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.rotate_by_svd!(model; kwargs...)
+    @eval PathMatFac reorder_by_importance!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.reorder_by_importance!(model; kwargs...)
+    @eval PathMatFac reweight_eb!(reg::L2Regularizer, X::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.reweight_eb!(reg, X; kwargs...)
+    @eval PathMatFac reweight_eb!(reg::GroupRegularizer, X::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.reweight_eb!(reg, X; kwargs...)
     return nothing
 end
 
 function release!(model)
     haskey(CTX, model) && (ccall((:pmf_destroy, LIB[]), Cint, (Ptr{Cvoid},), CTX[model]); delete!(CTX, model))
-    delete!(DATA_KEY, model); delete!(OPT_KEY, model); delete!(FSARD_DATA, model)
+    delete!(DATA_KEY, model); delete!(OPT_KEY, model); delete!(FSARD_DATA, model); delete!(EB_DATA, model)   # (the last two are keyed by a regularizer: release!(reg))
     return nothing
 end
 
