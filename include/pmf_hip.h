@@ -522,6 +522,20 @@ int pmf_debug_postprocess_times(pmf_ctx *ctx, double *gram_s, double *eig_s, dou
 int pmf_fsard_update_A(pmf_ctx *ctx, int64_t col_start1, int64_t col_stop1, int L, const float *S, const float *alpha,
                        const float *lambda, float alpha0, float v0, float lr, float *ssq_grad, float *A, int max_epochs,
                        int term_iter, double atol, double *best_loss, int *epochs_run, float *beta_out);
+/* The same call on a sparse S, without a bound on L * K other than device memory: the arguments, outputs and semantics of
+ * pmf_fsard_update_A, except that S comes as its 0-based CSR (rowptr[L + 1], col[nnz], val[nnz]; L rows = feature sets,
+ * N_v columns = the view's columns; columns strictly ascending within a row; stored zeros are legal), as the reference
+ * holds it (a SparseMatrixCSC, src/featureset_ard.jl:22).  A, the pull-back and the gradient live in device memory
+ * (csrc/pmf_fsard_csr.hip: four launches per iteration, no atomics, every sum in an order fixed by the shapes, the loss in
+ * f64); results agree with pmf_fsard_update_A to rounding, not bit for bit.
+ * Refused before anything is allocated or launched, the message naming the argument, no output touched and the context
+ * usable: an empty or out-of-range column range, L < 1, max_epochs < 0, term_iter < 1, a NULL rowptr / col / val / alpha /
+ * lambda / ssq_grad / A, rowptr[0] != 0, a decreasing rowptr, a column index outside 0 .. N_v - 1, unsorted or repeated
+ * columns in a row.  A failed allocation names its size. */
+int pmf_fsard_update_A_csr(pmf_ctx *ctx, int64_t col_start1, int64_t col_stop1, int L, const int64_t *rowptr,
+                           const int32_t *col, const float *val, const float *alpha, const float *lambda, float alpha0,
+                           float v0, float lr, float *ssq_grad, float *A, int max_epochs, int term_iter, double atol,
+                           double *best_loss, int *epochs_run, float *beta_out);
 
 /* Arithmetic of the three matrix products of the fused data pass (no reference counterpart: the reference computes
  * in Float32 on the GPU, src/fit.jl:24 via MatFac):

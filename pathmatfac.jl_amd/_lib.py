@@ -80,6 +80,23 @@ def csr_arrays(A):
             np.ascontiguousarray(A.data, dtype=np.float32))
 
 
+def dense_to_csr(S):
+    """A dense L x N_v array -> (rowptr int64 [L + 1], col int32, val float32): the 0-based CSR of its non-zero entries, by
+    a row-major scan, so the columns of a row come out ascending (pmf_fsard_update_A_csr).  No scipy."""
+    S = np.ascontiguousarray(S, dtype=np.float32)
+    if S.ndim != 2:
+        raise ValueError("dense_to_csr: S must be a matrix")
+    L, Nv = S.shape
+    flat = np.flatnonzero(S.ravel())                       # ascending = row by row, columns ascending within a row
+    rowptr = np.zeros(L + 1, np.int64)
+    if Nv:
+        np.cumsum(np.bincount(flat // Nv, minlength=L), out=rowptr[1:])
+        col = (flat % Nv).astype(np.int32)
+    else:
+        col = np.zeros(0, np.int32)
+    return rowptr, col, S.ravel()[flat].astype(np.float32)
+
+
 # every symbol include/pmf_hip.h declares (checked by tests/test_abi.py against the header and the .so)
 EXPORTS = [
     "pmf_last_error", "pmf_version", "pmf_device_count", "pmf_create", "pmf_destroy", "pmf_set_stream", "pmf_synchronize",
@@ -101,6 +118,7 @@ EXPORTS = [
     "pmf_stage_theta_delta_em",
     "pmf_gram", "pmf_stage_lambda_max", "pmf_stage_whiten", "pmf_stage_rotate_by_svd", "pmf_stage_reorder_by_importance",
     "pmf_debug_postprocess_times",
+    "pmf_fsard_update_A_csr",
 ]
 
 COMM_ID_BYTES = 128
@@ -542,6 +560,44 @@ class Context:
                                               C.c_float(alpha0), C.c_float(v0), C.c_float(lr), _fp(ssq_grad), _fp(A),
                                               int(max_epochs), int(term_iter), C.c_double(atol), C.byref(best), C.byref(ep),
                                               _fp(beta)))
+        return A, beta, best.value, ep.value
+
+    def fsard_update_A_csr(self, start1, stop1, S, alpha, lam, alpha0, v0, lr, ssq_grad, max_epochs=1000, term_iter=20,
+                           atol=1e-5):
+        """update_A! for one view on a sparse S, without the L x K bound of fsard_update_A (pmf_fsard_update_A_csr).
+        S: a dense L x Nv array, or the (rowptr, col, val) triple of its 0-based CSR (dense_to_csr); ssq_grad: L x K
+        (updated in place).  Returns (A [L x K], beta [K x Nv], best_loss, epochs_run)."""
+        Nv = stop1 - start1 + 1
+        if isinstance(S, (tuple, list)):
+            if len(S) != 3:
+                raise PMFError("S must be a dense L x Nv array or a (rowptr, col, val) triple")
+            rowptr, col, val = S
+        else:
+            S = np.asarray(S)
+            if S.ndim != 2 or S.shape[1] != Nv:
+                raise PMFError("S must have one column per column of the view")
+            rowptr, col, val = dense_to_csr(S)
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int64)
+        col = np.ascontiguousarray(col, dtype=np.int32)
+        val = np.ascontiguousarray(val, dtype=np.float32)
+        L = rowptr.size - 1
+        if L < 1 or col.shape != val.shape or col.ndim != 1 or rowptr[-1] != col.size:
+            raise PMFError("S: rowptr must have L + 1 >= 2 entries and end at the length of col and val")
+        if col.size == 0:                                  # (a pointer the library may look at, never through)
+            col, val = np.zeros(1, np.int32), np.zeros(1, np.float32)
+        al = np.ascontiguousarray(alpha, dtype=np.float32)
+        lm = np.ascontiguousarray(lam, dtype=np.float32)
+        if al.size != Nv or lm.size != self.K:
+            raise PMFError("alpha must have one entry per column of the view and lambda one per factor")
+        if ssq_grad.dtype != np.float32 or not ssq_grad.flags.c_contiguous or ssq_grad.shape != (L, self.K):
+            raise PMFError("ssq_grad must be a C-contiguous float32 L x K array")
+        A = np.zeros((L, self.K), np.float32)
+        beta = np.zeros((self.K, max(Nv, 0)), np.float32, order="F")
+        best, ep = C.c_double(0), C.c_int(0)
+        self._chk(self.lib.pmf_fsard_update_A_csr(
+            self._h, C.c_int64(start1), C.c_int64(stop1), int(L), _i64p(rowptr), col.ctypes.data_as(C.POINTER(C.c_int32)),
+            _fp(val), _fp(al), _fp(lm), C.c_float(alpha0), C.c_float(v0), C.c_float(lr), _fp(ssq_grad), _fp(A),
+            int(max_epochs), int(term_iter), C.c_double(atol), C.byref(best), C.byref(ep), _fp(beta)))
         return A, beta, best.value, ep.value
 
     def forward(self):

@@ -2,7 +2,8 @@
 // helpers its translation units share.
 //   pmf_hip.hip       C ABI (marshalling, step-level API, statistics), small kernels, work split, data-pass launches
 //   pmf_comm_fit.hip  cross-rank exchange (RCCL via dlopen / host-staged transport) and the epoch loop pmf_fit
-//   pmf_fsard.hip     the FeatureSetARD update_A! solver (ISTA on the device)
+//   pmf_fsard.hip     the FeatureSetARD update_A! solver (ISTA on the device; dense S, A in LDS, L x K <= 16384)
+//   pmf_fsard_csr.hip the same solver on a sparse S with A in device memory (no bound on L x K)
 //   pmf_netreg.hip    NetworkRegularizer (per-factor CG solve + sparse gradient) and the L1 / SelectiveL1 weights
 //   pmf_lbfgs.hip     L-BFGS over (X, Y): total gradient, history, two-loop recursion, backtracking (pmf_fit_lbfgs)
 //   pmf_stages.hip    the closed-form stages between the GD stages on the device statistics (pmf_stage_*)

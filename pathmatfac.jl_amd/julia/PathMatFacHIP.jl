@@ -6,7 +6,8 @@
 # ("term_code", "epochs", src/fit.jl:63,69) and the mutated model parameters.
 # The closed-form stages between the gradient-descent stages (init_mu!, init_logsigma!, reweight_col_losses!,
 # construct_minimal_regularizer, theta_delta_em, update_A!) are re-pointed too: each marshals the model, makes ONE library
-# call (pmf_stage_* / pmf_fsard_update_A; init_mu! goes through this file's mf_fit!) and copies back what changed.  The
+# call (pmf_stage_* / pmf_fsard_update_A, or pmf_fsard_update_A_csr on the sparse S where L * K exceeds the dense entry's
+# capacity; init_mu! goes through this file's mf_fit!) and copies back what changed.  The
 # moments block inside init_batch_effects! (src/fit.jl:444-462) keeps MatFac's CPU helpers.
 # So is the factor post-processing (whiten!, rotate_by_svd!, reorder_by_importance!, reweight_eb! of the L2 / Group terms):
 # one pmf_stage_whiten / _rotate_by_svd / _reorder_by_importance / _lambda_max call each.
@@ -21,6 +22,7 @@
 module PathMatFacHIP
 
 import PathMatFac
+import SparseArrays
 const PM = PathMatFac
 
 const LIB = Ref{String}("libpmf_hip.so")
@@ -28,6 +30,8 @@ const CTX = IdDict{Any,Ptr{Cvoid}}()          # model => pmf_ctx*
 const DATA_KEY = IdDict{Any,UInt}()           # model => objectid(model.data) last uploaded
 const OPT_KEY = IdDict{Any,UInt}()            # model => objectid(opt) whose state lives on the device
 const FSARD_DATA = IdDict{Any,Matrix{Float32}}()   # FeatureSetARDReg => the all-missing 1 x N matrix of its own context (update_A!)
+
+const FSARD_DENSE_CAPACITY = 16384            # L * K that pmf_fsard_update_A accepts (A in one workgroup's LDS)
 
 const TERM_CODES = ("max_epochs", "loss_increase", "abs_tol", "rel_tol", "nonfinite")
 const NOISE_KIND = Dict("normal" => Cint(0), "bernoulli" => Cint(1), "poisson" => Cint(2))
@@ -165,6 +169,29 @@ function fsard_update_A!(model, cr::UnitRange, S_t::Matrix{Float32}, alpha::Vect
         (Ptr{Cvoid}, Int64, Int64, Cint, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Cfloat, Cfloat, Cfloat, Ptr{Cfloat},
          Ptr{Cfloat}, Cint, Cint, Cdouble, Ref{Cdouble}, Ref{Cint}, Ptr{Cfloat}),
         ctx, cr.start, cr.stop, L, S_t, alpha, lambda, alpha0, v0, lr, ssq_t, A_t, max_epochs, term_iter, atol,
+        best, ep, beta))
+    return best[], Int(ep[])
+end
+
+# The same on a sparse S, without the L * K <= 16384 bound of the dense entry (pmf_fsard_update_A_csr): S_t is the view's
+# N_v x L transpose as a SparseMatrixCSC, whose colptr / rowval, shifted to 0-based, are the CSR of the L x N_v matrix
+# (row indices ascend within a column of a SparseMatrixCSC, as the library wants the columns of a row).
+function fsard_update_A_csr!(model, cr::UnitRange, S_t, alpha::Vector{Float32}, lambda::Vector{Float32},
+                             A_t::Matrix{Float32}, ssq_t::Matrix{Float32}, beta::Matrix{Float32};
+                             alpha0::Float32, v0::Float32, lr::Float32, max_epochs::Integer=1000, term_iter::Integer=50,
+                             atol::Float64=1e-5, ctx::Ptr{Cvoid}=context!(model))
+    best = Ref{Cdouble}(0.0); ep = Ref{Cint}(0)
+    L = size(S_t, 2)
+    rowptr = Vector{Int64}(S_t.colptr .- 1)
+    col = Vector{Int32}(S_t.rowval .- 1)
+    val = Vector{Float32}(S_t.nzval)
+    if isempty(col)                       # (a pointer the library may look at, never through)
+        col = Int32[0]; val = Float32[0]
+    end
+    GC.@preserve rowptr col val alpha lambda A_t ssq_t beta chk(ccall((:pmf_fsard_update_A_csr, LIB[]), Cint,
+        (Ptr{Cvoid}, Int64, Int64, Cint, Ptr{Int64}, Ptr{Int32}, Ptr{Cfloat}, Ptr{Cfloat}, Ptr{Cfloat}, Cfloat, Cfloat, Cfloat,
+         Ptr{Cfloat}, Ptr{Cfloat}, Cint, Cint, Cdouble, Ref{Cdouble}, Ref{Cint}, Ptr{Cfloat}),
+        ctx, cr.start, cr.stop, L, rowptr, col, val, alpha, lambda, alpha0, v0, lr, ssq_t, A_t, max_epochs, term_iter, atol,
         best, ep, beta))
     return best[], Int(ep[])
 end
@@ -543,10 +570,13 @@ function init_mu!(model::PM.PathMatFacModel; capacity=Int(10e8), lr_mu=0.1, max_
     history === nothing || PM.history!(history, h; name="init_mu")
 end
 
-"""Replacement for PathMatFac.update_A! (src/featureset_ard.jl:278-294): per view one pmf_fsard_update_A on a context of
-the regularizer's own that holds Y (an all-missing one-row data matrix fixes N; X is a zero column)."""
+"""Replacement for PathMatFac.update_A! (src/featureset_ard.jl:278-294): per view one pmf_fsard_update_A -- or, where
+L * K exceeds that entry's capacity, one pmf_fsard_update_A_csr on the sparse S -- on a context of the regularizer's own
+that holds Y (an all-missing one-row data matrix fixes N; X is a zero column).  `kernel`: :auto (the dense entry wherever it
+accepts the shape, as the Python twin update_A_ chooses), :dense or :sparse."""
 function update_A!(reg::PM.FeatureSetARDReg, Y::AbstractMatrix; max_epochs=1000, term_iter=20, atol=1e-5, verbosity=1,
-                   print_prefix="", print_iter=100)
+                   print_prefix="", print_iter=100, kernel::Symbol=:auto)
+    kernel in (:auto, :dense, :sparse) || throw(ArgumentError("update_A!: kernel must be :auto, :dense or :sparse"))
     K, N = size(Y)
     ctx = data_context!(reg, get!(() -> fill(NaN32, 1, N), FSARD_DATA, reg))
     X0, Y32 = zeros(Float32, K, 1), f32(Y)
@@ -556,13 +586,20 @@ function update_A!(reg::PM.FeatureSetARDReg, Y::AbstractMatrix; max_epochs=1000,
     beta_all = f32(reg.beta)
     for (v, cr) in enumerate(reg.col_ranges)
         opt = reg.A_opts[v]
-        S_t = f32(Matrix(transpose(reg.S[v])))             # N_v x L column-major = L x N_v row-major
-        A_t = zeros(Float32, K, size(reg.S[v], 1))          # update_A! starts every view from A = 0 (:286)
+        L = size(reg.S[v], 1)
+        sparse = kernel == :sparse || (kernel == :auto && L * K > FSARD_DENSE_CAPACITY)
+        A_t = zeros(Float32, K, L)                          # update_A! starts every view from A = 0 (:286)
         ssq_t = f32(Matrix(transpose(opt.ssq_grad)))
         beta = zeros(Float32, K, length(cr))
-        best, _ = fsard_update_A!(reg, cr, S_t, f32(reg.alpha[cr]), f32(vec(opt.lambda)), A_t, ssq_t, beta;
-                                  alpha0=Float32(reg.alpha0), v0=Float32(reg.v0), lr=Float32(opt.lr),
-                                  max_epochs=max_epochs, term_iter=term_iter, atol=Float64(atol), ctx=ctx)
+        kw = (alpha0=Float32(reg.alpha0), v0=Float32(reg.v0), lr=Float32(opt.lr), max_epochs=max_epochs,
+              term_iter=term_iter, atol=Float64(atol), ctx=ctx)
+        best, _ = if sparse
+            S_csc = SparseArrays.SparseMatrixCSC(transpose(reg.S[v]))     # N_v x L: its columns are the rows of S
+            fsard_update_A_csr!(reg, cr, S_csc, f32(reg.alpha[cr]), f32(vec(opt.lambda)), A_t, ssq_t, beta; kw...)
+        else
+            S_t = f32(Matrix(transpose(reg.S[v])))         # N_v x L column-major = L x N_v row-major
+            fsard_update_A!(reg, cr, S_t, f32(reg.alpha[cr]), f32(vec(opt.lambda)), A_t, ssq_t, beta; kw...)
+        end
         reg.A[v] .= transpose(A_t)
         opt.ssq_grad .= transpose(ssq_t)
         beta_all[:, cr] .= beta
