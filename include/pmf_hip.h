@@ -353,6 +353,12 @@ int pmf_debug_last_kernel(pmf_ctx *ctx, int *kernel);
 int pmf_debug_pass_extents(pmf_ctx *ctx, int update_X, int update_Y, const int64_t *cap_override, int n_max,
                            const char **names, int64_t *need, int64_t *capacity, int *n);
 
+/* Diagnostics: the bytes of device memory and of pinned host memory that the library holds at this moment, summed over every
+ * context of the PROCESS (its contexts' buffers and the temporaries of a running call).  Every allocation of the library is
+ * counted where it is made and where it is freed, so the figures are exact whatever else runs on the GPU: a context's
+ * pmf_destroy brings both back to what they were before its pmf_create.  Either pointer may be NULL. */
+int pmf_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes);
+
 /* raw device addresses of the gradient buffers (float32) and their element counts, for in-place collectives */
 int pmf_grad_device_ptr(pmf_ctx *ctx, int which, void **ptr, int64_t *n_elements);
 /* copy a gradient of the last pmf_epoch_begin to the host in the reference's shape (tests / diagnostics) */

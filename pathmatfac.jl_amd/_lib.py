@@ -110,7 +110,7 @@ EXPORTS = [
     "pmf_set_precision", "pmf_get_precision",
     "pmf_comm_get_unique_id", "pmf_comm_init", "pmf_comm_init_host", "pmf_comm_destroy", "pmf_comm_set_chunks",
     "pmf_comm_info", "pmf_comm_allreduce", "pmf_get_opt_state", "pmf_fsard_update_A", "pmf_debug_last_path", "pmf_debug_last_kernel",
-    "pmf_debug_pass_extents",
+    "pmf_debug_pass_extents", "pmf_debug_live_bytes",
     "pmf_add_xreg_network", "pmf_add_yreg_network", "pmf_get_reg_network_state", "pmf_add_xreg_l1", "pmf_add_yreg_l1",
     "pmf_impute", "pmf_impute_device", "pmf_impute_entries", "pmf_debug_impute_offset",
     "pmf_loss", "pmf_fit_lbfgs", "pmf_debug_lbfgs_direction",
@@ -133,6 +133,15 @@ def comm_unique_id(lib_path=None):
         raise PMFError(lib.pmf_last_error().decode())
     return buf.raw
 
+
+
+def live_bytes(lib_path=None):
+    """pmf_debug_live_bytes: (device, pinned) bytes the library holds in this process, over all of its contexts."""
+    lib = load_library(lib_path)
+    d, h = C.c_int64(0), C.c_int64(0)
+    if lib.pmf_debug_live_bytes(C.byref(d), C.byref(h)) != 0:
+        raise PMFError(lib.pmf_last_error().decode())
+    return d.value, h.value
 
 
 def device_count(lib_path=None):

@@ -85,21 +85,14 @@ int comm_release(pmf_ctx *c) {
   Comm &m = c->comm;
   if (m.stream) (void)hipStreamSynchronize(m.stream);
   if (m.nccl && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t)m.nccl);
-  m.nccl = nullptr;
-  m.host_fn = nullptr;
-  m.host_user = nullptr;
   for (auto e : m.ev_ready) (void)hipEventDestroy(e);
   for (auto e : m.ev_done) (void)hipEventDestroy(e);
-  m.ev_ready.clear(); m.ev_done.clear();
-  hipEvent_t *evs[4] = {&m.ev_loss_ready, &m.ev_loss_done, &m.ev_layer_ready, &m.ev_layer_done};
-  for (auto pe : evs) { if (*pe) (void)hipEventDestroy(*pe); *pe = nullptr; }
+  for (auto e : {m.ev_loss_ready, m.ev_loss_done, m.ev_layer_ready, m.ev_layer_done})
+    if (e) (void)hipEventDestroy(e);
   if (m.stream) (void)hipStreamDestroy(m.stream);
-  m.stream = nullptr;
-  if (m.stage) (void)hipHostFree(m.stage);
-  m.stage = nullptr; m.stage_bytes = 0;
-  if (m.dstage) (void)hipFree(m.dstage);
-  m.dstage = nullptr; m.dstage_bytes = 0;
-  m.rank = 0; m.nranks = 1; m.reserve_cus = 0; m.cta_cap = 0; m.broken = false; m.m_mean = 0;
+  const int64_t n_allreduce = m.n_allreduce;   // (a diagnostic of the context, not of the communicator)
+  m = Comm();                                  // one rank, no transport; the staging buffers go with the old value
+  m.n_allreduce = n_allreduce;
   return 0;
 }
 static int comm_common_init(pmf_ctx *c, int rank, int nranks) {
@@ -193,12 +186,7 @@ int comm_allreduce(pmf_ctx *c, void *p, int64_t count, bool f64) {
                     "ncclAllReduce", (ncclComm_t)m.nccl);
   // host-staged transport (tests): device -> pinned host -> callback (e.g. gloo) -> device, blocking
   const size_t bytes = (size_t)count * (f64 ? 8 : 4);
-  if (bytes > m.stage_bytes) {
-    if (m.stage) (void)hipHostFree(m.stage);
-    m.stage = nullptr; m.stage_bytes = 0;
-    HIPCHK(hipHostMalloc(&m.stage, bytes));
-    m.stage_bytes = bytes;
-  }
+  PMFCHK(m.stage.ensure(bytes, false));
   HIPCHK(hipMemcpyAsync(m.stage, p, bytes, hipMemcpyDeviceToHost, m.stream));
   HIPCHK(hipStreamSynchronize(m.stream));
   if (m.host_fn(m.host_user, m.stage, count, f64 ? 1 : 0) != 0) return pmf_fail("host all-reduce callback failed");
@@ -217,13 +205,7 @@ extern "C" int pmf_comm_allreduce(pmf_ctx *c, void *host_buf, int64_t count, int
   Comm &m = c->comm;
   const size_t bytes = (size_t)count * (dtype ? 8 : 4);
   if (m.nccl) {
-    if (bytes > m.dstage_bytes) {   // device staging buffer of the communicator, grown on demand (no allocation per call)
-      if (m.dstage) (void)hipFree(m.dstage);
-      m.dstage = nullptr; m.dstage_bytes = 0;
-      const size_t want = std::max<size_t>(bytes, 1 << 16);
-      HIPCHK(hipMalloc(&m.dstage, want));
-      m.dstage_bytes = want;
-    }
+    PMFCHK(m.dstage.ensure(std::max<size_t>(bytes, 1 << 16), false));   // (grown on demand: no allocation per call)
     void *d = m.dstage;
     hipError_t e = hipMemcpyAsync(d, host_buf, bytes, hipMemcpyHostToDevice, m.stream);
     int rc = 0;

@@ -1,5 +1,6 @@
 // pmf_ctx.h -- internal to libpmf_hip.so: the context behind the opaque `pmf_ctx` of include/pmf_hip.h and the host
-// helpers its translation units share.
+// helpers its translation units share; DevBuf / PinnedBuf, the one type that allocates and frees device and pinned memory
+// (every buffer below is a member of that type, or a local of one call: no capacity fields, no free lists).
 //   pmf_hip.hip       C ABI (marshalling, step-level API, statistics), small kernels, work split, data-pass launches
 //   pmf_comm_fit.hip  cross-rank exchange (RCCL via dlopen / host-staged transport) and the epoch loop pmf_fit
 //   pmf_fsard.hip     the FeatureSetARD update_A! solver (ISTA on the device; dense S, A in LDS, L x K <= 16384)
@@ -13,26 +14,89 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
 
 #include "pmf_common.h"
 
+// hipMemset on device memory is queued on the NULL stream and may return before it has run; the library's kernels and
+// copies run on a NON-BLOCKING stream, which the NULL stream does not order (memset_now, pmf_hip.hip).
+int memset_now(void *p, int v, size_t bytes);
+// The one owner of device and pinned host memory: every allocation of the library is a DevBuf (PinnedBuf: the same
+// type on hipHostMalloc), a member of the struct that uses it or a local of one call, and is freed by its destructor.
+// size() is what is allocated, in elements: the capacity that grow sites (ensure) and the extents guard (bytes()) read.
+// pmf_live_bytes counts what every DevBuf of the process holds: [0] device, [1] pinned (pmf_debug_live_bytes).
+inline std::atomic<int64_t> pmf_live_bytes[2];
+template <typename T, bool PINNED = false>
+struct DevBuf {
+  T *p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) { free(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+    return *this;
+  }
+  ~DevBuf() { free(); }
+  operator T *() const { return p; }
+  size_t size() const { return n; }
+  size_t bytes() const { return n * sizeof(T); }
+  void free() {
+    if (p) {
+      (void)(PINNED ? hipHostFree(p) : hipFree(p));
+      pmf_live_bytes[PINNED] -= (int64_t)bytes();
+    }
+    p = nullptr; n = 0;
+  }
+  // always a fresh allocation of exactly max(count, 1) elements (the old contents are gone); `zero` fills it in NULL-stream
+  // order (memset_now).  On failure the buffer is empty and the message names the size and `what`.
+  int alloc(size_t count, bool zero, const char *what = nullptr) {
+    free();
+    count = std::max<size_t>(count, 1);
+    const hipError_t e = PINNED ? hipHostMalloc((void **)&p, count * sizeof(T)) : hipMalloc((void **)&p, count * sizeof(T));
+    if (e != hipSuccess) {
+      p = nullptr;
+      (void)hipGetLastError();
+      return pmf_fail("cannot allocate %zu bytes of %s memory for %s: %s", count * sizeof(T), PINNED ? "pinned host" : "device",
+                      what ? what : "a library buffer", hipGetErrorString(e));
+    }
+    n = count;
+    pmf_live_bytes[PINNED] += (int64_t)bytes();
+    if (zero) {
+      if (PINNED) memset(p, 0, bytes());
+      else PMFCHK(memset_now(p, 0, bytes()));
+    }
+    return 0;
+  }
+  // grow-only, exact, and never a copy of the old contents: a no-op while count <= size()
+  int ensure(size_t count, bool zero, const char *what = nullptr) { return count <= n ? 0 : alloc(count, zero, what); }
+  int upload(const T *src, size_t count) {
+    if (count) HIPCHK(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+  }
+};
+template <typename T>
+using PinnedBuf = DevBuf<T, true>;
+
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
 struct ParamBuf {  // one trainable parameter tensor with its gradient, optimizer state and quadratic regularizer
-  float *p = nullptr, *g = nullptr, *acc = nullptr, *mom = nullptr;
-  float *wq = nullptr, *cq = nullptr;  // dense quadratic weights / centres: 0.5*wq*(p-cq)^2 (nullptr = none)
-  float *wl1 = nullptr;                // dense L1 weights w_k m_kj p: wl1*|p| (L1Regularizer / SelectiveL1Reg; nullptr = none)
-  int64_t n = 0;
+  DevBuf<float> p, g, acc, mom;
+  DevBuf<float> wq, cq;  // dense quadratic weights / centres: 0.5*wq*(p-cq)^2 (empty = none)
+  DevBuf<float> wl1;     // dense L1 weights w_k m_kj p: wl1*|p| (L1Regularizer / SelectiveL1Reg; empty = none)
+  int64_t n = 0;         // logical length (Kp x rows for X, Y)
   float bp1 = 0.f, bp2 = 0.f;  // Adam running beta powers
 };
 
@@ -45,8 +109,7 @@ struct PanelSlots {
   int64_t serial = -1;
   int BM = 0;
   bool ok = false;
-  uint8_t *pm = nullptr, *row_slot = nullptr;
-  int64_t pm_cap = 0, row_slot_cap = 0;   // bytes allocated (fused_pass_extents)
+  DevBuf<uint8_t> pm, row_slot;
 };
 
 // Cached work split of one column chunk of the fused data pass (see compute_work_split).
@@ -54,13 +117,13 @@ struct WorkSplit {
   int64_t key[11] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   int grid = 0;
   int64_t serial = 0;
-  int64_t *wg_begin = nullptr;     // [grid + 1] device: first work item of each workgroup
-  int32_t *c_off = nullptr, *c_idx = nullptr;   // per column tile of the chunk: the workgroups that visit it (CSR; k_gy_reduce)
-  int32_t *piece_base = nullptr;   // [grid] device: chunk-relative slot of each workgroup's first piece (gX partial buffer)
+  DevBuf<int64_t> wg_begin;        // [grid + 1] device: first work item of each workgroup
+  DevBuf<int32_t> c_off, c_idx;    // per column tile of the chunk: the workgroups that visit it (CSR; k_gy_reduce)
+  DevBuf<int32_t> piece_base;      // [grid] device: chunk-relative slot of each workgroup's first piece (gX partial buffer)
   std::vector<int32_t> h_piece_base;
   std::vector<int32_t> piece_rp;   // host: row panel of every piece, in slot order
   int32_t slot_base = 0;           // first slot of this chunk in the flat gX partial buffer (set with the CSR)
-  int32_t *d_piece_base_abs = nullptr;   // [grid] device: piece_base + slot_base
+  DevBuf<int32_t> d_piece_base_abs;      // [grid] device: piece_base + slot_base
 };
 
 // Cross-rank exchange of the sharded fit: rows are sharded, Y / column layers replicated; per epoch the
@@ -73,12 +136,10 @@ struct Comm {
   pmf_host_allreduce_fn host_fn = nullptr;
   void *host_user = nullptr;
   hipStream_t stream = nullptr;    // communication stream
-  void *stage = nullptr;           // pinned staging buffer of the host-staged transport
-  size_t stage_bytes = 0;
+  PinnedBuf<char> stage;           // pinned staging buffer of the host-staged transport, grown on demand
   int reserve_cus = 0;             // CUs left to the collective's kernels by the fused pass (RCCL transport)
   int cta_cap = 0;                 // workgroups the communicator is configured for (ncclConfig_t.maxCTAs); 0 = RCCL's default
-  void *dstage = nullptr;          // device staging buffer of pmf_comm_allreduce (host buffers), grown on demand
-  size_t dstage_bytes = 0;
+  DevBuf<char> dstage;             // device staging buffer of pmf_comm_allreduce (host buffers), grown on demand
   bool broken = false;             // a fit failed with collectives possibly unmatched: the communicator must be destroyed
   int64_t m_mean = 0;              // rows per rank averaged over the ranks (pmf_fit): the rank-invariant size behind the chunk count
   std::vector<hipEvent_t> ev_ready, ev_done;   // per chunk: gY slice complete / its all-reduce complete
@@ -95,16 +156,16 @@ struct NetReg {
   int64_t n = 0, V = 0;            // V = sum of v_k
   float p = 1.f;                   // mixture weight
   std::vector<int64_t> h_voff;     // [K + 1]
-  int64_t *voff = nullptr;         // device copy
-  int64_t *aa_rp = nullptr, *ab_rp = nullptr, *abt_rp = nullptr, *bb_rp = nullptr;
-  int32_t *aa_col = nullptr, *ab_col = nullptr, *abt_col = nullptr, *bb_col = nullptr;
-  float *aa_val = nullptr, *ab_val = nullptr, *abt_val = nullptr, *bb_val = nullptr;
-  float *u = nullptr;              // [V]
-  float *work = nullptr;           // [4 V] t, r, d, BB d of the factors whose v_k exceeds the LDS budget
-  float *PT = nullptr;             // [K][n] factor-major copy of the parameter, rebuilt every epoch
-  float *grad = nullptr;           // [Kp * n] p * (AA_k p_k + AB_k u_k), in the parameter's own layout (read by k_reg_step<true>)
-  int32_t *iters = nullptr;        // [K] CG iterations of the last solve
-  double *uloss = nullptr;         // [K] t'u + 0.5 u'BB u of the last solve
+  DevBuf<int64_t> voff;            // device copy
+  DevBuf<int64_t> aa_rp, ab_rp, abt_rp, bb_rp;
+  DevBuf<int32_t> aa_col, ab_col, abt_col, bb_col;
+  DevBuf<float> aa_val, ab_val, abt_val, bb_val;
+  DevBuf<float> u;                 // [V]
+  DevBuf<float> work;              // [4 V] t, r, d, BB d of the factors whose v_k exceeds the LDS budget
+  DevBuf<float> PT;                // [K][n] factor-major copy of the parameter, rebuilt every epoch
+  DevBuf<float> grad;              // [Kp * n] p * (AA_k p_k + AB_k u_k), in the parameter's own layout (read by k_reg_step<true>)
+  DevBuf<int32_t> iters;           // [K] CG iterations of the last solve
+  DevBuf<double> uloss;            // [K] t'u + 0.5 u'BB u of the last solve
   int rb = 1;                      // row blocks per factor of the gradient kernel (= loss partials per factor)
   int64_t vmax = 0;                // largest v_k
 };
@@ -116,11 +177,10 @@ struct pmf_ctx {
   int n_cu = 256;
   int64_t M = 0, N = 0;
   int K = 0, Kp = 0, KB = 0;
-  void *D = nullptr;   // tile-major copy of the data matrix, f32 (pmf_d_off) or bf16 (pmf_d_off16, `store`), always library-owned
+  DevBuf<char> D;      // tile-major copy of the data matrix, f32 (pmf_d_off) or bf16 (pmf_d_off16, `store`), always library-owned
   bool own_D = false;
   int64_t D_M = 0, D_Npad = 0, nRB = 0;
-  uint32_t *tflags = nullptr;     // per 32x32 tile of D: 1 = all 1024 entries finite (fast epilogue path of the fused kernel)
-  int64_t tflags_cap = 0;
+  DevBuf<uint32_t> tflags;        // per 32x32 tile of D: 1 = all 1024 entries finite (fast epilogue path of the fused kernel)
   bool tflags_valid = false;
   int store = PMF_STORE_F32;
   ParamBuf P[6];  // X, Y, logsigma, mu, logdelta, theta
@@ -129,34 +189,30 @@ struct pmf_ctx {
   std::vector<ViewDesc> views;
   std::vector<int64_t> val_off;  // per view offset into the flat logdelta/theta arrays
   std::vector<int64_t> bvb_off;  // per view offset into the flat per-(view,batch) arrays
-  int32_t *bor = nullptr;
-  float2 *btab = nullptr;
+  DevBuf<int32_t> bor;
+  DevBuf<float2> btab;
   bool views_dirty = true;        // `views` changed since the last upload
-  ViewDesc *d_views = nullptr;    // device copy of `views` for the fused kernel's global-gather fallback
-  float2 *LG = nullptr;           // [R * waves * 2][N][nbs] {S_G, S_Q}: the private tables of the layer pass (pmf_layers.hip.inc)
-  int64_t LG_cap = 0;
-  float *lgrad_part = nullptr;    // [block rows][2N + 2 nbt] private partials of k_layer_grad (fixed-order k_sum_parts)
-  size_t lgrad_part_cap = 0;
-  float2 *btd = nullptr;          // dense per-column batch table [ceil(N/32)*32][nbs] (fused kernels, layer pass); see k_dense_btab
-  int64_t btd_cap = 0;
+  DevBuf<ViewDesc> d_views;       // device copy of `views` for the fused kernel's global-gather fallback
+  DevBuf<float2> LG;              // [R * waves * 2][N][nbs] {S_G, S_Q}: the private tables of the layer pass (pmf_layers.hip.inc)
+  DevBuf<float> lgrad_part;       // [block rows][2N + 2 nbt] private partials of k_layer_grad (fixed-order k_sum_parts)
+  DevBuf<float2> btd;             // dense per-column batch table [ceil(N/32)*32][nbs] (fused kernels, layer pass); see k_dense_btab
   bool btd_ok = false;            // the dense table is built (every view has <= 255 batches)
   int nbs = 16;                   // slots per column of the dense table: 16, or the power of two above the largest batch count (0: no table)
-  int64_t colview_cap = 0;
-  uint8_t *colview = nullptr;     // [ceil(N/32)*32] view of every column, 255 = none (k_dense_btab)
+  DevBuf<uint8_t> colview;        // [ceil(N/32)*32] view of every column, 255 = none (k_dense_btab)
   std::vector<std::vector<int32_t>> h_bor;   // host copy of batch_of_row per view (panel-local slot maps)
   PanelSlots pslots[3];           // panel-local batch slots for row panels of 128 / 256 / 512 rows (ensure_panel_slots)
   int64_t views_serial = 0;       // bumped whenever a view's rows / shape change
   int last_kernel = 0;            // fused kernel family of the last data pass (pmf_debug_last_kernel)
   int last_bmode = 0, last_layer_path = 0;   // diagnostics (pmf_debug_last_path)
-  int32_t *d_val_view = nullptr;  // per flat value element: view id
+  DevBuf<int32_t> d_val_view;     // per flat value element: view id
   // noise model / prepared column parameters
-  int32_t *colmeta = nullptr;  // kind | (view+1)<<2
-  float *colw = nullptr;
-  float4 *colp = nullptr;
+  DevBuf<int32_t> colmeta;     // kind | (view+1)<<2
+  DevBuf<float> colw;
+  DevBuf<float4> colp;
   bool mixed = false;
   bool prepared = false;
   // ARD-type regularizer on Y
-  float *ard_alpha = nullptr, *ard_beta = nullptr;
+  DevBuf<float> ard_alpha, ard_beta;
   float ard_scale = 0.f;
   bool has_ard = false;
   bool ard_is_fsard = false;       // the attached term came from pmf_add_yreg_fsard (the only kind pmf_fsard_update_A writes beta into)
@@ -165,33 +221,29 @@ struct pmf_ctx {
   float lr = 1.f, eps = 1e-8f, b1 = 0.9f, b2 = 0.999f;
   bool state_init = false;
   // loss plumbing
-  double *loss_partial = nullptr;
+  DevBuf<double> loss_partial;    // the data pass's loss partials: n_macro of them are live (k_loss_reduce)
   std::vector<uint8_t> h_kind;    // host copy of the per-column noise kind (cost model of the work split)
   std::vector<int64_t> noise_s1, noise_e1;   // the noise model's column ranges as pmf_set_noise got them (pmf_stage_minimal_group_weights)
   std::vector<WorkSplit> splits;  // cached work split of every column chunk of the fused pass (compute_work_split)
   int n_chunks_req = 0;           // column chunks per data pass: 0 = automatic (1 on one GPU; pmf_comm_set_chunks)
-  float *gx_part = nullptr;       // [pieces][BM x Kp] per-piece partial sums of gX (fused kernel), summed by k_gx_reduce
-  size_t gx_part_cap = 0;         // floats
-  int32_t *gx_off = nullptr, *gx_idx = nullptr;   // per row panel: the slots of its pieces, in work-sequence order (CSR)
+  DevBuf<float> gx_part;          // [pieces][BM x Kp] per-piece partial sums of gX (fused kernel), summed by k_gx_reduce
+  DevBuf<int32_t> gx_off, gx_idx; // per row panel: the slots of its pieces, in work-sequence order (CSR)
   int64_t gx_serial = -1;         // sum of the splits' serials the CSR was built for
   int64_t split_serial = 0;       // bumped whenever a split is recomputed
   Comm comm;                      // cross-rank exchange (pmf_comm_init*); nranks == 1: none
   int last_chunks = 1;            // column chunks of the last pmf_fit's data pass (pmf_comm_info)
   hipEvent_t ev_host = nullptr;   // "the epoch's loss has reached the host" (pmf_fit)
   int64_t kind_version = 0;
-  float *gy_slabs = nullptr;      // [grid][Kp x N] private per-workgroup gY partial sums of the fused kernel
-  size_t gy_slabs_cap = 0;        // floats, the padding tile included
+  DevBuf<float> gy_slabs;         // [grid][Kp x N] private per-workgroup gY partial sums of the fused kernel, the padding tile included
   int precision = PMF_PREC_F32;   // products of the fused data pass: exact f32 MFMA, or split-bf16 (pmf_set_precision)
-  char *xsb = nullptr, *ysb = nullptr;   // split-bf16 operand images of X / sigma*Y, rebuilt every epoch (k_sb_split)
-  size_t xsb_cap = 0, ysb_cap = 0;       // bytes (xsb: its sixteen blocks of padding included)
-  float *sb8_scale = nullptr;     // [1 + chunks] power-of-two pre-scales of pmf_fused_sb8_kernel's f16 images: X, then Y per chunk
-  uint32_t *sb8_max = nullptr;    // [1 + chunks] bit patterns of max |operand| (k_sb8_absmax)
+  DevBuf<char> xsb, ysb;          // split-bf16 operand images of X / sigma*Y, rebuilt every epoch (k_sb_split; xsb: its sixteen blocks of padding included)
+  DevBuf<float> sb8_scale;        // [1 + chunks] power-of-two pre-scales of pmf_fused_sb8_kernel's f16 images: X, then Y per chunk
+  DevBuf<uint32_t> sb8_max;       // [1 + chunks] bit patterns of max |operand| (k_sb8_absmax)
   int64_t sb_launches = 0;        // fused launches that took the split-bf16 kernel (pmf_get_precision)
-  int64_t loss_cap = 0;
   int64_t n_macro = 0;
-  double *reg_partial = nullptr;  // [4][REG_SLOTS]
-  double *d_loss = nullptr;       // device [8]
-  double *h_loss = nullptr;       // pinned host [8]
+  DevBuf<double> reg_partial;     // [4][REG_SLOTS]
+  DevBuf<double> d_loss;          // device [8]
+  PinnedBuf<double> h_loss;       // pinned host [8]
   // fused-kernel timing
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;
   size_t ev_used = 0;
@@ -200,12 +252,10 @@ struct pmf_ctx {
   NetReg *net[2] = {nullptr, nullptr};   // NetworkRegularizer on X / Y (nullptr = none)
   int reg_counts[4] = {0, 0, 0, 0};  // used slots of the regularizer partial slabs (0 X, 1 Y, 2 column layers)
   // scratch
-  void *scratch = nullptr;
-  size_t scratch_bytes = 0;
+  DevBuf<char> scratch;
   // staging buffer of pmf_impute / pmf_impute_entries (at most 256 MiB unless one row of N predictions is larger), grown
   // lazily; not `scratch`, which those calls leave alone
-  void *impute_stage = nullptr;
-  size_t impute_stage_bytes = 0;
+  DevBuf<char> impute_stage;
   // largest dynamic-LDS size set so far per kernel ON THIS CONTEXT'S DEVICE (hipFuncSetAttribute is per device: a
   // process-wide cache would leave a second GPU's kernels without the attribute)
   PmfDynLds dyn_lds;
@@ -228,52 +278,6 @@ struct FusedGeom {
 };
 
 struct RegCounts { int c[4]; };
-
-// hipMemset on device memory is queued on the NULL stream and may return before it has run; the library's kernels and
-// copies run on a NON-BLOCKING stream, which the NULL stream does not order (memset_now, pmf_hip.hip).
-int memset_now(void *p, int v, size_t bytes);
-template <typename T>
-static int dev_alloc(T **p, size_t n, bool zero = true) {
-  if (*p) {
-    HIPCHK(hipFree(*p));
-    *p = nullptr;
-  }
-  if (n == 0) n = 1;
-  HIPCHK(hipMalloc((void **)p, n * sizeof(T)));
-  if (zero) PMFCHK(memset_now(*p, 0, n * sizeof(T)));
-  return 0;
-}
-template <typename T>
-static void dev_free(T **p) {
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-}
-
-// device / pinned host memory owned for the duration of a call (pmf_stages.hip, pmf_postprocess.hip)
-template <typename T>
-struct DevBuf {
-  T *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n) {
-    HIPCHK(hipMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)));
-    return 0;
-  }
-};
-template <typename T>
-struct PinnedBuf {
-  T *p = nullptr;
-  PinnedBuf() = default;
-  PinnedBuf(const PinnedBuf &) = delete;
-  PinnedBuf &operator=(const PinnedBuf &) = delete;
-  ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-  int alloc(size_t n) {
-    HIPCHK(hipHostMalloc((void **)&p, std::max<size_t>(n, 1) * sizeof(T)));
-    return 0;
-  }
-};
 
 __device__ __forceinline__ double block_reduce_sum(double v, double *sh) {
 #pragma unroll

@@ -198,74 +198,66 @@ extern "C" int pmf_fsard_update_A(pmf_ctx *c, int64_t col_start1, int64_t col_st
   if ((size_t)(n + (int64_t)K * (CW + 1)) * 4 > 150 * 1024) return pmf_fail("L x K too large for LDS");
   const int n_wg = (int)std::max<int64_t>(1, std::min<int64_t>(32, (Nv + CW - 1) / CW));
   // device buffers (freed on return)
-  float *dS = nullptr, *dal = nullptr, *dlam = nullptr, *dA = nullptr, *dAb = nullptr, *dssq = nullptr, *dgp = nullptr;
-  double *dlp = nullptr, *dst = nullptr;
-  int32_t *dis = nullptr;
-  auto cleanup = [&]() { dev_free(&dS); dev_free(&dal); dev_free(&dlam); dev_free(&dA); dev_free(&dAb); dev_free(&dssq); dev_free(&dgp); dev_free(&dlp); dev_free(&dst); dev_free(&dis); };
-  int rc = 0;
-  do {
-    if ((rc = dev_alloc(&dS, (size_t)(L * Nv), false)) < 0) break;
-    if ((rc = dev_alloc(&dal, (size_t)Nv, false)) < 0) break;
-    if ((rc = dev_alloc(&dlam, (size_t)K, false)) < 0) break;
-    if ((rc = dev_alloc(&dA, (size_t)n)) < 0) break;          // A .= 0 (featureset_ard.jl:286)
-    if ((rc = dev_alloc(&dAb, (size_t)n)) < 0) break;
-    if ((rc = dev_alloc(&dssq, (size_t)n, false)) < 0) break;
-    if ((rc = dev_alloc(&dgp, (size_t)(n_wg * n))) < 0) break;
-    if ((rc = dev_alloc(&dlp, (size_t)n_wg)) < 0) break;
-    if ((rc = dev_alloc(&dst, (size_t)8)) < 0) break;
-    if ((rc = dev_alloc(&dis, (size_t)8)) < 0) break;
-    hipError_t e = hipMemcpy(dS, S, sizeof(float) * (size_t)(L * Nv), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dal, alpha, sizeof(float) * (size_t)Nv, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dlam, lambda, sizeof(float) * (size_t)K, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dssq, ssq_grad, sizeof(float) * (size_t)n, hipMemcpyHostToDevice);
-    const int32_t is0[8] = {0, 0, 0, max_epochs, term_iter, 0, 0, 0};
-    if (e == hipSuccess) e = hipMemcpy(dis, is0, sizeof(is0), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { rc = pmf_fail("pmf_fsard_update_A: %s", hipGetErrorString(e)); break; }
-    FsardArgs a;
-    memset(&a, 0, sizeof(a));
-    a.Y = c->P[1].p; a.S = dS; a.alpha = dal; a.lambda = dlam; a.A = dA; a.A_best = dAb; a.ssq = dssq; a.gpart = dgp; a.lpart = dlp;
-    a.state = dst; a.istate = dis; a.beta_dev = (c->has_ard && c->ard_is_fsard && c->ard_beta) ? c->ard_beta + (col_start1 - 1) * c->Kp : nullptr;
-    a.c0 = col_start1 - 1; a.Nv = Nv; a.L = L; a.K = K; a.Kp = c->Kp; a.CW = CW; a.n_wg = n_wg;
-    a.alpha0 = alpha0; a.v0 = v0; a.lr = lr; a.atol = atol;
-    const size_t lds = (size_t)(n + (int64_t)K * (CW + 1)) * 4;
-    if ((rc = ensure_dyn_lds(c, (const void *)k_fsard_grad, lds)) < 0) break;
-    int32_t h_is[8];
-    // evaluations 0 .. max_epochs (the update after evaluation t gives A_{t+1}); the host looks at the `done` flag once
-    // per batch of iterations
-    const int batch = std::max(8, term_iter);
-    bool done = false;
-    for (int t = 0; t <= max_epochs && !done; t += batch) {
-      for (int q = 0; q < batch && t + q <= max_epochs; ++q) {
-        hipLaunchKernelGGL(k_fsard_grad, dim3(n_wg), dim3(256), lds, c->stream, a, 0);
-        hipLaunchKernelGGL(k_fsard_step, dim3(1), dim3(1024), 0, c->stream, a);
-      }
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(h_is, dis, sizeof(h_is), hipMemcpyDeviceToHost, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-      if (e != hipSuccess) { rc = pmf_fail("pmf_fsard_update_A: %s", hipGetErrorString(e)); break; }
-      done = h_is[0] != 0;
+  DevBuf<float> dS, dal, dlam, dA, dAb, dssq, dgp, dbeta_tmp;
+  DevBuf<double> dlp, dst;
+  DevBuf<int32_t> dis;
+  PMFCHK(dS.alloc((size_t)(L * Nv), false));
+  PMFCHK(dal.alloc((size_t)Nv, false));
+  PMFCHK(dlam.alloc((size_t)K, false));
+  PMFCHK(dA.alloc((size_t)n, true));          // A .= 0 (featureset_ard.jl:286)
+  PMFCHK(dAb.alloc((size_t)n, true));
+  PMFCHK(dssq.alloc((size_t)n, false));
+  PMFCHK(dgp.alloc((size_t)(n_wg * n), true));
+  PMFCHK(dlp.alloc((size_t)n_wg, true));
+  PMFCHK(dst.alloc(8, true));
+  PMFCHK(dis.alloc(8, true));
+  PMFCHK(dS.upload(S, (size_t)(L * Nv)));
+  PMFCHK(dal.upload(alpha, (size_t)Nv));
+  PMFCHK(dlam.upload(lambda, (size_t)K));
+  PMFCHK(dssq.upload(ssq_grad, (size_t)n));
+  const int32_t is0[8] = {0, 0, 0, max_epochs, term_iter, 0, 0, 0};
+  PMFCHK(dis.upload(is0, 8));
+  FsardArgs a;
+  memset(&a, 0, sizeof(a));
+  a.Y = c->P[1].p; a.S = dS; a.alpha = dal; a.lambda = dlam; a.A = dA; a.A_best = dAb; a.ssq = dssq; a.gpart = dgp; a.lpart = dlp;
+  a.state = dst; a.istate = dis; a.beta_dev = (c->has_ard && c->ard_is_fsard && c->ard_beta) ? c->ard_beta + (col_start1 - 1) * c->Kp : nullptr;
+  a.c0 = col_start1 - 1; a.Nv = Nv; a.L = L; a.K = K; a.Kp = c->Kp; a.CW = CW; a.n_wg = n_wg;
+  a.alpha0 = alpha0; a.v0 = v0; a.lr = lr; a.atol = atol;
+  const size_t lds = (size_t)(n + (int64_t)K * (CW + 1)) * 4;
+  PMFCHK(ensure_dyn_lds(c, (const void *)k_fsard_grad, lds));
+  int32_t h_is[8];
+  hipError_t e = hipSuccess;
+  // evaluations 0 .. max_epochs (the update after evaluation t gives A_{t+1}); the host looks at the `done` flag once
+  // per batch of iterations
+  const int batch = std::max(8, term_iter);
+  bool done = false;
+  for (int t = 0; t <= max_epochs && !done; t += batch) {
+    for (int q = 0; q < batch && t + q <= max_epochs; ++q) {
+      hipLaunchKernelGGL(k_fsard_grad, dim3(n_wg), dim3(256), lds, c->stream, a, 0);
+      hipLaunchKernelGGL(k_fsard_step, dim3(1), dim3(1024), 0, c->stream, a);
     }
-    if (rc < 0) break;
-    // A .= A_best ; beta[:, cr] = beta0 (v0 + A'S)   (featureset_ard.jl:272, 292)
-    float *dbeta_tmp = nullptr;
-    if (beta_out && !a.beta_dev) {   // no device regularizer array to write into: a temporary with the view's columns
-      if ((rc = dev_alloc(&dbeta_tmp, (size_t)(Nv * c->Kp))) < 0) break;
-      a.beta_dev = dbeta_tmp;
-    }
-    if (a.beta_dev) hipLaunchKernelGGL(k_fsard_grad, dim3(n_wg), dim3(256), lds, c->stream, a, 1);
-    double h_st[8];
-    e = hipMemcpyAsync(h_st, dst, sizeof(h_st), hipMemcpyDeviceToHost, c->stream);
+    e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_is, dis, sizeof(h_is), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(A, dAb, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(ssq_grad, dssq, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && beta_out)
-      e = hipMemcpy2D(beta_out, sizeof(float) * K, a.beta_dev, sizeof(float) * c->Kp, sizeof(float) * K, (size_t)Nv, hipMemcpyDeviceToHost);
-    dev_free(&dbeta_tmp);
-    if (e != hipSuccess) { rc = pmf_fail("pmf_fsard_update_A: %s", hipGetErrorString(e)); break; }
-    if (best_loss) *best_loss = h_st[0];
-    if (epochs_run) *epochs_run = h_is[2] - 1;
-  } while (0);
-  cleanup();
-  return rc;
+    if (e != hipSuccess) return pmf_fail("pmf_fsard_update_A: %s", hipGetErrorString(e));
+    done = h_is[0] != 0;
+  }
+  // A .= A_best ; beta[:, cr] = beta0 (v0 + A'S)   (featureset_ard.jl:272, 292)
+  if (beta_out && !a.beta_dev) {   // no device regularizer array to write into: a temporary with the view's columns
+    PMFCHK(dbeta_tmp.alloc((size_t)(Nv * c->Kp), true));
+    a.beta_dev = dbeta_tmp;
+  }
+  if (a.beta_dev) hipLaunchKernelGGL(k_fsard_grad, dim3(n_wg), dim3(256), lds, c->stream, a, 1);
+  double h_st[8];
+  e = hipMemcpyAsync(h_st, dst, sizeof(h_st), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_is, dis, sizeof(h_is), hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipMemcpy(A, dAb, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(ssq_grad, dssq, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && beta_out)
+    e = hipMemcpy2D(beta_out, sizeof(float) * K, a.beta_dev, sizeof(float) * c->Kp, sizeof(float) * K, (size_t)Nv, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return pmf_fail("pmf_fsard_update_A: %s", hipGetErrorString(e));
+  if (best_loss) *best_loss = h_st[0];
+  if (epochs_run) *epochs_run = h_is[2] - 1;
+  return 0;
 }

@@ -173,31 +173,6 @@ __global__ __launch_bounds__(256) void k_fsc_update(const FscArgs a, int t) {
   }
 }
 
-// device memory of one call; a failed allocation names its size
-template <typename T>
-struct FscBuf {
-  T *p = nullptr;
-  FscBuf() = default;
-  FscBuf(const FscBuf &) = delete;
-  FscBuf &operator=(const FscBuf &) = delete;
-  ~FscBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t n, const char *what, bool zero = false) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    const hipError_t e = hipMalloc((void **)&p, bytes);
-    if (e != hipSuccess) {
-      p = nullptr;
-      (void)hipGetLastError();
-      return pmf_fail("pmf_fsard_update_A_csr: cannot allocate %zu bytes for %s: %s", bytes, what, hipGetErrorString(e));
-    }
-    if (zero) PMFCHK(memset_now(p, 0, bytes));
-    return 0;
-  }
-  int upload(const T *src, size_t n) {
-    if (n) HIPCHK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return 0;
-  }
-};
-
 extern "C" int pmf_fsard_update_A_csr(pmf_ctx *c, int64_t col_start1, int64_t col_stop1, int L, const int64_t *rowptr,
                                       const int32_t *col, const float *val, const float *alpha, const float *lambda,
                                       float alpha0, float v0, float lr, float *ssq_grad, float *A, int max_epochs,
@@ -267,27 +242,27 @@ extern "C" int pmf_fsard_update_A_csr(pmf_ctx *c, int64_t col_start1, int64_t co
   const int g_rows = (int)((L + step - 1) / step);
   const int g_upd = (int)std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256));
   // ---- device buffers (freed on return)
-  FscBuf<int64_t> d_rp, d_cp;
-  FscBuf<int32_t> d_col, d_ri, d_is;
-  FscBuf<float> d_val, d_cv, d_al, d_lam, d_A, d_Ab, d_ssq, d_G, d_grad, d_beta_tmp;
-  FscBuf<double> d_lp, d_rpart, d_st;
-  PMFCHK(d_rp.alloc((size_t)L + 1, "rowptr"));
-  PMFCHK(d_col.alloc((size_t)nnz, "col"));
-  PMFCHK(d_val.alloc((size_t)nnz, "val"));
-  PMFCHK(d_cp.alloc((size_t)Nv + 1, "the column pointers of S"));
-  PMFCHK(d_ri.alloc((size_t)nnz, "the row indices of S by column"));
-  PMFCHK(d_cv.alloc((size_t)nnz, "the values of S by column"));
-  PMFCHK(d_al.alloc((size_t)Nv, "alpha"));
-  PMFCHK(d_lam.alloc((size_t)K, "lambda"));
-  PMFCHK(d_A.alloc((size_t)n, "A", true));                 // A .= 0 (featureset_ard.jl:286)
-  PMFCHK(d_Ab.alloc((size_t)n, "A_best", true));
-  PMFCHK(d_ssq.alloc((size_t)n, "ssq_grad"));
-  PMFCHK(d_G.alloc((size_t)(Nv * K), "the pull-back G"));
-  PMFCHK(d_grad.alloc((size_t)n, "grad_A"));
-  PMFCHK(d_lp.alloc((size_t)n_wg, "the loss partials", true));
-  PMFCHK(d_rpart.alloc((size_t)L, "the row partials", true));
-  PMFCHK(d_st.alloc(8, "the loop state", true));
-  PMFCHK(d_is.alloc(8, "the loop counters"));
+  DevBuf<int64_t> d_rp, d_cp;
+  DevBuf<int32_t> d_col, d_ri, d_is;
+  DevBuf<float> d_val, d_cv, d_al, d_lam, d_A, d_Ab, d_ssq, d_G, d_grad, d_beta_tmp;
+  DevBuf<double> d_lp, d_rpart, d_st;
+  PMFCHK(d_rp.alloc((size_t)L + 1, false, "rowptr"));
+  PMFCHK(d_col.alloc((size_t)nnz, false, "col"));
+  PMFCHK(d_val.alloc((size_t)nnz, false, "val"));
+  PMFCHK(d_cp.alloc((size_t)Nv + 1, false, "the column pointers of S"));
+  PMFCHK(d_ri.alloc((size_t)nnz, false, "the row indices of S by column"));
+  PMFCHK(d_cv.alloc((size_t)nnz, false, "the values of S by column"));
+  PMFCHK(d_al.alloc((size_t)Nv, false, "alpha"));
+  PMFCHK(d_lam.alloc((size_t)K, false, "lambda"));
+  PMFCHK(d_A.alloc((size_t)n, true, "A"));                 // A .= 0 (featureset_ard.jl:286)
+  PMFCHK(d_Ab.alloc((size_t)n, true, "A_best"));
+  PMFCHK(d_ssq.alloc((size_t)n, false, "ssq_grad"));
+  PMFCHK(d_G.alloc((size_t)(Nv * K), false, "the pull-back G"));
+  PMFCHK(d_grad.alloc((size_t)n, false, "grad_A"));
+  PMFCHK(d_lp.alloc((size_t)n_wg, true, "the loss partials"));
+  PMFCHK(d_rpart.alloc((size_t)L, true, "the row partials"));
+  PMFCHK(d_st.alloc(8, true, "the loop state"));
+  PMFCHK(d_is.alloc(8, false, "the loop counters"));
   PMFCHK(d_rp.upload(rowptr, (size_t)L + 1));
   PMFCHK(d_col.upload(col, (size_t)nnz));
   PMFCHK(d_val.upload(val, (size_t)nnz));
@@ -328,7 +303,7 @@ extern "C" int pmf_fsard_update_A_csr(pmf_ctx *c, int64_t col_start1, int64_t co
   }
   // A .= A_best ; beta[:, cr] = beta0 (v0 + A'S)   (featureset_ard.jl:272, 292)
   if (beta_out && !a.beta_dev) {   // no device regularizer array to write into: a temporary with the view's columns
-    PMFCHK(d_beta_tmp.alloc((size_t)(Nv * c->Kp), "beta", true));
+    PMFCHK(d_beta_tmp.alloc((size_t)(Nv * c->Kp), true, "beta"));
     a.beta_dev = d_beta_tmp.p;
   }
   if (a.beta_dev) hipLaunchKernelGGL(k_fsc_forward<true>, dim3(n_wg), dim3(256), 0, c->stream, a);

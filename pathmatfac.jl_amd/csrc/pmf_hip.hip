@@ -37,18 +37,9 @@ int memset_now(void *p, int v, size_t bytes) {
 
 static int param_alloc(ParamBuf &b, int64_t n) {
   b.n = n;
-  PMFCHK(dev_alloc(&b.p, n));
-  PMFCHK(dev_alloc(&b.g, n));
-  PMFCHK(dev_alloc(&b.acc, n));
-  PMFCHK(dev_alloc(&b.mom, n));
-  dev_free(&b.wq);
-  dev_free(&b.cq);
-  dev_free(&b.wl1);
+  for (auto *t : {&b.p, &b.g, &b.acc, &b.mom}) PMFCHK(t->alloc((size_t)n, true));   // (always fresh: the optimizer state restarts)
+  for (auto *t : {&b.wq, &b.cq, &b.wl1}) t->free();
   return 0;
-}
-static void param_free(ParamBuf &b) {
-  dev_free(&b.p); dev_free(&b.g); dev_free(&b.acc); dev_free(&b.mom); dev_free(&b.wq); dev_free(&b.cq); dev_free(&b.wl1);
-  b.n = 0;
 }
 
 int pmf_ensure_dyn_lds(PmfDynLds *cache, const void *kern, size_t lds) {
@@ -59,15 +50,6 @@ int pmf_ensure_dyn_lds(PmfDynLds *cache, const void *kern, size_t lds) {
   return 0;
 }
 int ensure_dyn_lds(pmf_ctx *c, const void *kern, size_t lds) { return pmf_ensure_dyn_lds(&c->dyn_lds, kern, lds); }
-
-static int ensure_scratch(pmf_ctx *c, size_t bytes) {
-  if (c->scratch_bytes >= bytes) return 0;
-  if (c->scratch) HIPCHK(hipFree(c->scratch));
-  c->scratch = nullptr;
-  HIPCHK(hipMalloc(&c->scratch, bytes));
-  c->scratch_bytes = bytes;
-  return 0;
-}
 
 // ------------------------------------------------------------------------------------------------
 // small kernels
@@ -561,10 +543,7 @@ static void fill_views(const pmf_ctx *c, ViewDesc *views, int64_t *val_off = nul
 }
 // room for the n loss partials of the pass about to be launched, which k_loss_reduce will then sum
 static int ensure_loss_partials(pmf_ctx *c, int64_t n) {
-  if (n > c->loss_cap) {
-    PMFCHK(dev_alloc(&c->loss_partial, (size_t)n));
-    c->loss_cap = n;
-  }
+  PMFCHK(c->loss_partial.ensure((size_t)n, true));
   c->n_macro = n;
   return 0;
 }
@@ -576,9 +555,9 @@ static int upload_padded(pmf_ctx *c, float *dst, const float *src, int64_t n, fl
     HIPCHK(hipStreamSynchronize(c->stream));
     return 0;
   }
-  PMFCHK(ensure_scratch(c, sizeof(float) * (size_t)(n * c->K)));
+  PMFCHK(c->scratch.ensure(sizeof(float) * (size_t)(n * c->K), false));
   HIPCHK(hipMemcpyAsync(c->scratch, src, sizeof(float) * (size_t)(n * c->K), hipMemcpyHostToDevice, c->stream));
-  k_pad_copy<<<nblocks(n * c->Kp, 256), 256, 0, c->stream>>>(dst, (const float *)c->scratch, c->Kp, c->K, n, padval);
+  k_pad_copy<<<nblocks(n * c->Kp, 256), 256, 0, c->stream>>>(dst, (const float *)c->scratch.p, c->Kp, c->K, n, padval);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -589,12 +568,34 @@ static int download_padded(pmf_ctx *c, float *dst_host, const float *src_dev, in
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
+// a call's temporary: n elements (not zeroed) holding a copy of src
 template <typename T>
-static int upload_vec(pmf_ctx *c, T *dst, const T *src, size_t n) {
+static int upload_new(DevBuf<T> &b, const T *src, size_t n) {
+  PMFCHK(b.alloc(n, false));
+  return b.upload(src, n);
+}
+template <typename T>
+static int upload_vec(pmf_ctx *c, std::common_type_t<T> *dst, const T *src, size_t n) {   // (T is deduced from src alone: dst may be a DevBuf)
   if (n == 0) return 0;
   HIPCHK(hipMemcpyAsync(dst, src, sizeof(T) * n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
+}
+
+// what set_K resets with the factors: the ARD-type term of Y; what data_shape_changed resets with the shape: everything
+// built from the batch views
+static void drop_ard(pmf_ctx *c) {
+  c->ard_alpha.free();
+  c->ard_beta.free();
+  c->has_ard = false;
+  c->ard_is_fsard = false;
+}
+static void drop_views(pmf_ctx *c) {
+  c->bor.free(); c->btab.free(); c->d_val_view.free(); c->d_views.free();   // the views as uploaded
+  c->btd.free(); c->colview.free();                                         // the dense table prepare() builds from them
+  c->LG.free(); c->lgrad_part.free();                                       // the layer pass's tables, sized by them
+  c->btd_ok = false;
+  c->views_dirty = true;
 }
 
 static int set_K(pmf_ctx *c, int K) {
@@ -608,10 +609,7 @@ static int set_K(pmf_ctx *c, int K) {
   PMFCHK(param_alloc(c->P[1], (int64_t)c->Kp * c->N));
   netreg_free(c, 0);
   netreg_free(c, 1);
-  dev_free(&c->ard_alpha);
-  dev_free(&c->ard_beta);
-  c->has_ard = false;
-  c->ard_is_fsard = false;
+  drop_ard(c);
   c->state_init = false;
   return 0;
 }
@@ -634,20 +632,20 @@ extern "C" int pmf_create(int device, pmf_ctx **out) {
   HIPCHK(hipGetDeviceProperties(&prop, device));
   if (std::string(prop.gcnArchName).find("gfx950") == std::string::npos)
     return pmf_fail("libpmf_hip is built for gfx950 (MI355X) only; device %d is %s", device, prop.gcnArchName);
-  pmf_ctx *c = new pmf_ctx();
+  std::unique_ptr<pmf_ctx> c(new pmf_ctx());   // (a failure below frees the context and what it owns)
   c->device = device;
   c->n_cu = prop.multiProcessorCount;
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   c->own_stream = true;
-  HIPCHK(hipMalloc((void **)&c->d_loss, sizeof(double) * 8));
-  HIPCHK(hipHostMalloc((void **)&c->h_loss, sizeof(double) * 8));
-  HIPCHK(hipMalloc((void **)&c->reg_partial, sizeof(double) * 4 * REG_SLOTS));
-  PMFCHK(memset_now(c->reg_partial, 0, sizeof(double) * 4 * REG_SLOTS));
+  if (c->d_loss.alloc(8, false) < 0 || c->h_loss.alloc(8, false) < 0 || c->reg_partial.alloc(4 * REG_SLOTS, true) < 0) {
+    (void)hipStreamDestroy(c->stream);
+    return -1;
+  }
   {
     const char *pe = getenv("PMF_PRECISION");   // development / benchmark override of the default (exact f32)
     if (pe && std::string(pe) == "bf16x3") c->precision = PMF_PREC_BF16X3;
   }
-  *out = c;
+  *out = c.release();
   return 0;
 }
 
@@ -655,25 +653,13 @@ extern "C" int pmf_destroy(pmf_ctx *c) {
   if (!c) return 0;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->stream);
-  for (auto &b : c->P) param_free(b);
+  // what is not memory: the communicator with its stream and events, the context's events and stream; every buffer goes
+  // with its owner in `delete c`
+  comm_release(c);
   netreg_free(c, 0);
   netreg_free(c, 1);
   lbfgs_free(c);
-  if (c->D) (void)hipFree(c->D);
-  c->D = nullptr;
-  dev_free(&c->tflags);
-  dev_free(&c->bor); dev_free(&c->btab); dev_free(&c->btd); c->btd_cap = 0; c->btd_ok = false; dev_free(&c->colview); c->colview_cap = 0; dev_free(&c->LG); c->LG_cap = 0; dev_free(&c->lgrad_part); c->lgrad_part_cap = 0; dev_free(&c->d_views); c->views_dirty = true; dev_free(&c->d_val_view);
-  dev_free(&c->colmeta); dev_free(&c->colw); dev_free(&c->colp);
-  dev_free(&c->ard_alpha); dev_free(&c->ard_beta);
-  comm_release(c);
-  for (auto &ps : c->pslots) { dev_free(&ps.pm); dev_free(&ps.row_slot); }
-  for (auto &ws : c->splits) { dev_free(&ws.wg_begin); dev_free(&ws.c_off); dev_free(&ws.c_idx); dev_free(&ws.piece_base); dev_free(&ws.d_piece_base_abs); }
-  dev_free(&c->gx_part); dev_free(&c->gx_off); dev_free(&c->gx_idx);
   if (c->ev_host) (void)hipEventDestroy(c->ev_host);
-  dev_free(&c->gy_slabs); dev_free(&c->xsb); dev_free(&c->ysb); dev_free(&c->sb8_scale); dev_free(&c->sb8_max); dev_free(&c->loss_partial); dev_free(&c->reg_partial); dev_free(&c->d_loss);
-  if (c->h_loss) (void)hipHostFree(c->h_loss);
-  if (c->scratch) (void)hipFree(c->scratch);
-  if (c->impute_stage) (void)hipFree(c->impute_stage);
   for (auto &e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
@@ -720,7 +706,7 @@ static int data_shape_changed(pmf_ctx *c, int64_t M, int64_t N) {
   if (M == c->M && N == c->N) return 0;
   c->M = M;
   c->N = N;
-  for (auto &b : c->P) param_free(b);
+  for (auto &b : c->P) b = ParamBuf();
   netreg_free(c, 0);
   netreg_free(c, 1);
   c->K = c->Kp = c->KB = 0;
@@ -730,13 +716,12 @@ static int data_shape_changed(pmf_ctx *c, int64_t M, int64_t N) {
   c->h_bor.clear();
   c->views_serial++;
   c->views.clear();
-  c->views_dirty = true;
   c->val_off.clear();
   c->bvb_off.clear();
-  dev_free(&c->bor); dev_free(&c->btab); dev_free(&c->btd); c->btd_cap = 0; c->btd_ok = false; dev_free(&c->colview); c->colview_cap = 0; dev_free(&c->LG); c->LG_cap = 0; dev_free(&c->lgrad_part); c->lgrad_part_cap = 0; dev_free(&c->d_views); c->views_dirty = true; dev_free(&c->d_val_view);
-  PMFCHK(dev_alloc(&c->colmeta, (size_t)N));
-  PMFCHK(dev_alloc(&c->colw, (size_t)N));
-  PMFCHK(dev_alloc(&c->colp, (size_t)N));
+  drop_views(c);
+  PMFCHK(c->colmeta.alloc((size_t)N, true));
+  PMFCHK(c->colw.alloc((size_t)N, true));
+  PMFCHK(c->colp.alloc((size_t)N, true));
   k_fill<<<nblocks(N, 256), 256, 0, c->stream>>>(c->colw, N, 1.f);
   HIPCHK(hipGetLastError());
   c->mixed = false;
@@ -754,10 +739,8 @@ static int alloc_tiled_D(pmf_ctx *c, int64_t M, int64_t N, int store) {
   const int64_t nRB = (M + 31) / 32;
   const int64_t nfl = nRB * 32 * Npad;
   const size_t esz = store == PMF_STORE_BF16 ? 2 : 4;
-  if (!(c->D && c->D_M == M && c->D_Npad == Npad && c->store == store)) {
-    if (c->D) (void)hipFree(c->D);
-    c->D = nullptr;
-    HIPCHK(hipMalloc(&c->D, esz * (size_t)nfl));
+  if (!(c->D && c->D_M == M && c->D_Npad == Npad && c->store == store)) {   // same shape and store: keep the buffer
+    PMFCHK(c->D.alloc(esz * (size_t)nfl, false));
     c->own_D = true;
     c->D_M = M;
     c->D_Npad = Npad;
@@ -765,8 +748,8 @@ static int alloc_tiled_D(pmf_ctx *c, int64_t M, int64_t N, int store) {
   }
   c->tflags_valid = false;
   c->store = store;
-  if (store == PMF_STORE_BF16) k_fill16<<<(int)std::min<int64_t>(nblocks(nfl, 256), 65536), 256, 0, c->stream>>>((uint16_t *)c->D, nfl, (uint16_t)0x7fc0);
-  else k_fill<<<(int)std::min<int64_t>(nblocks(nfl, 256), 65536), 256, 0, c->stream>>>((float *)c->D, nfl, __builtin_nanf(""));
+  if (store == PMF_STORE_BF16) k_fill16<<<(int)std::min<int64_t>(nblocks(nfl, 256), 65536), 256, 0, c->stream>>>((uint16_t *)c->D.p, nfl, (uint16_t)0x7fc0);
+  else k_fill<<<(int)std::min<int64_t>(nblocks(nfl, 256), 65536), 256, 0, c->stream>>>((float *)c->D.p, nfl, __builtin_nanf(""));
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -787,11 +770,11 @@ extern "C" int pmf_set_data(pmf_ctx *c, const float *D, int64_t M, int64_t N, in
   PMFCHK(alloc_tiled_D(c, M, N, store));
   // upload in column chunks of <= 256 MiB through a staging buffer, tiling each chunk on the device
   const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (64ll << 20) / std::max<int64_t>(M, 1)));
-  PMFCHK(ensure_scratch(c, sizeof(float) * (size_t)(M * chunk)));
+  PMFCHK(c->scratch.ensure(sizeof(float) * (size_t)(M * chunk), false));
   for (int64_t c0 = 0; c0 < N; c0 += chunk) {
     const int64_t nc = std::min(chunk, N - c0);
     HIPCHK(hipMemcpyAsync(c->scratch, D + c0 * M, sizeof(float) * (size_t)(M * nc), hipMemcpyHostToDevice, c->stream));
-    PMFCHK(tile_from_device(c, (const float *)c->scratch, c0, nc));
+    PMFCHK(tile_from_device(c, (const float *)c->scratch.p, c0, nc));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return 0;
@@ -880,11 +863,11 @@ extern "C" int pmf_set_n_batch_views(pmf_ctx *c, int n) {
   c->views_dirty = true;
   c->val_off.assign((size_t)n + 1, 0);
   c->bvb_off.assign((size_t)n + 1, 0);
-  param_free(c->P[4]);
-  param_free(c->P[5]);
-  dev_free(&c->btab);
-  dev_free(&c->d_val_view);
-  PMFCHK(dev_alloc(&c->bor, (size_t)std::max<int64_t>(1, (int64_t)n * c->M)));
+  c->P[4] = ParamBuf();
+  c->P[5] = ParamBuf();
+  c->btab.free();
+  c->d_val_view.free();
+  PMFCHK(c->bor.alloc((size_t)((int64_t)n * c->M), true));
   if (n > 0) PMFCHK(memset_now(c->bor, 0xFF, sizeof(int32_t) * (size_t)((int64_t)n * c->M)));
   PMFCHK(rebuild_colmeta_views(c));
   c->state_init = false;
@@ -938,12 +921,12 @@ extern "C" int pmf_set_batch_view(pmf_ctx *c, int v, int64_t s1, int64_t e1, int
       HIPCHK(hipMemcpy(c->P[4].p, old_ld.data(), sizeof(float) * old_ld.size(), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(c->P[5].p, old_th.data(), sizeof(float) * old_th.size(), hipMemcpyHostToDevice));
     }
-    PMFCHK(dev_alloc(&c->btab, (size_t)std::max<int64_t>(1, tot)));
+    PMFCHK(c->btab.alloc((size_t)tot, true));
     std::vector<int32_t> vv((size_t)std::max<int64_t>(1, tot), 0);
     for (int u = 0; u < c->n_bv; ++u)
       for (int64_t e = c->val_off[u]; e < c->val_off[u + 1]; ++e) vv[(size_t)e] = u;
-    PMFCHK(dev_alloc(&c->d_val_view, vv.size()));
-    HIPCHK(hipMemcpy(c->d_val_view, vv.data(), sizeof(int32_t) * vv.size(), hipMemcpyHostToDevice));
+    PMFCHK(c->d_val_view.alloc(vv.size(), true));
+    PMFCHK(c->d_val_view.upload(vv.data(), vv.size()));
     c->state_init = false;
   }
   const int64_t off = c->val_off[v];
@@ -997,19 +980,15 @@ static int add_quad_ranges(pmf_ctx *c, int which, int n_groups, const int64_t *s
   const int64_t n = which == 0 ? c->M : c->N;
   for (int g = 0; g < n_groups; ++g)
     if (s1[g] < 1 || e1[g] > n || s1[g] > e1[g]) return pmf_fail("regularizer range %d: bad %lld:%lld (n=%lld)", g, (long long)s1[g], (long long)e1[g], (long long)n);
-  if (!b.wq) PMFCHK(dev_alloc(&b.wq, (size_t)b.n));
-  int64_t *ds = nullptr, *de = nullptr;
-  float *dw = nullptr;
-  PMFCHK(dev_alloc(&ds, (size_t)n_groups, false));
-  PMFCHK(dev_alloc(&de, (size_t)n_groups, false));
-  PMFCHK(dev_alloc(&dw, (size_t)n_groups * c->K, false));
-  HIPCHK(hipMemcpy(ds, s1, sizeof(int64_t) * n_groups, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(de, e1, sizeof(int64_t) * n_groups, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(dw, w, sizeof(float) * (size_t)n_groups * c->K, hipMemcpyHostToDevice));
+  if (!b.wq) PMFCHK(b.wq.alloc((size_t)b.n, true));
+  DevBuf<int64_t> ds, de;
+  DevBuf<float> dw;
+  PMFCHK(upload_new(ds, s1, (size_t)n_groups));
+  PMFCHK(upload_new(de, e1, (size_t)n_groups));
+  PMFCHK(upload_new(dw, w, (size_t)n_groups * c->K));
   k_expand_group<<<nblocks(b.n, 256), 256, 0, c->stream>>>(b.wq, c->Kp, c->K, n, ds, de, dw, n_groups, p);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  dev_free(&ds); dev_free(&de); dev_free(&dw);
   return 0;
 }
 static int add_quad_l2(pmf_ctx *c, int which, const float *w, float p) {
@@ -1018,8 +997,8 @@ static int add_quad_l2(pmf_ctx *c, int which, const float *w, float p) {
 }
 extern "C" int pmf_clear_xreg(pmf_ctx *c) {
   PMFCHK(ctx_bind(c));
-  dev_free(&c->P[0].wq);
-  dev_free(&c->P[0].wl1);
+  c->P[0].wq.free();
+  c->P[0].wl1.free();
   netreg_free(c, 0);
   return 0;
 }
@@ -1033,8 +1012,8 @@ extern "C" int pmf_add_xreg_group(pmf_ctx *c, int n, const int64_t *s1, const in
 }
 extern "C" int pmf_clear_yreg(pmf_ctx *c) {
   PMFCHK(ctx_bind(c));
-  dev_free(&c->P[1].wq);
-  dev_free(&c->P[1].wl1);
+  c->P[1].wq.free();
+  c->P[1].wl1.free();
   netreg_free(c, 1);
   c->has_ard = false;
   c->ard_is_fsard = false;
@@ -1055,22 +1034,17 @@ extern "C" int pmf_add_yreg_ard(pmf_ctx *c, int n_ranges, const int64_t *s1, con
   if (c->has_ard) return pmf_fail("only one ARD-type term (ARD or FeatureSetARD) is supported on Y");
   for (int r = 0; r < n_ranges; ++r)
     if (s1[r] < 1 || e1[r] > c->N || s1[r] > e1[r]) return pmf_fail("ARD range %d: bad %lld:%lld", r, (long long)s1[r], (long long)e1[r]);
-  if (!c->ard_alpha) PMFCHK(dev_alloc(&c->ard_alpha, (size_t)c->N));
-  if (!c->ard_beta) PMFCHK(dev_alloc(&c->ard_beta, (size_t)c->P[1].n));
-  int64_t *ds = nullptr, *de = nullptr;
-  float *da = nullptr, *db = nullptr;
-  PMFCHK(dev_alloc(&ds, (size_t)n_ranges, false));
-  PMFCHK(dev_alloc(&de, (size_t)n_ranges, false));
-  PMFCHK(dev_alloc(&da, (size_t)n_ranges, false));
-  PMFCHK(dev_alloc(&db, (size_t)n_ranges, false));
-  HIPCHK(hipMemcpy(ds, s1, sizeof(int64_t) * n_ranges, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(de, e1, sizeof(int64_t) * n_ranges, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(da, alpha, sizeof(float) * n_ranges, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(db, beta, sizeof(float) * n_ranges, hipMemcpyHostToDevice));
+  if (!c->ard_alpha) PMFCHK(c->ard_alpha.alloc((size_t)c->N, true));
+  if (!c->ard_beta) PMFCHK(c->ard_beta.alloc((size_t)c->P[1].n, true));
+  DevBuf<int64_t> ds, de;
+  DevBuf<float> da, db;
+  PMFCHK(upload_new(ds, s1, (size_t)n_ranges));
+  PMFCHK(upload_new(de, e1, (size_t)n_ranges));
+  PMFCHK(upload_new(da, alpha, (size_t)n_ranges));
+  PMFCHK(upload_new(db, beta, (size_t)n_ranges));
   k_expand_ard<<<nblocks(c->P[1].n, 256), 256, 0, c->stream>>>(c->ard_alpha, c->ard_beta, c->Kp, c->N, ds, de, da, db, n_ranges);
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
-  dev_free(&ds); dev_free(&de); dev_free(&da); dev_free(&db);
   c->ard_scale = p;
   c->has_ard = true;
   c->ard_is_fsard = false;
@@ -1080,8 +1054,8 @@ extern "C" int pmf_add_yreg_fsard(pmf_ctx *c, const float *alpha, const float *b
   PMFCHK(ctx_bind(c));
   if (c->K == 0) return pmf_fail("factors must be set before their regularizers");
   if (c->has_ard) return pmf_fail("only one ARD-type term (ARD or FeatureSetARD) is supported on Y");
-  if (!c->ard_alpha) PMFCHK(dev_alloc(&c->ard_alpha, (size_t)c->N));
-  if (!c->ard_beta) PMFCHK(dev_alloc(&c->ard_beta, (size_t)c->P[1].n));
+  if (!c->ard_alpha) PMFCHK(c->ard_alpha.alloc((size_t)c->N, true));
+  if (!c->ard_beta) PMFCHK(c->ard_beta.alloc((size_t)c->P[1].n, true));
   PMFCHK(upload_vec(c, c->ard_alpha, alpha, (size_t)c->N));
   PMFCHK(upload_padded(c, c->ard_beta, beta, c->N, 1.f));
   c->ard_scale = p;
@@ -1095,58 +1069,47 @@ extern "C" int pmf_set_layer_regs(pmf_ctx *c, int n_ranges, const int64_t *s1, c
                                   const float *w_ld, const float *c_ld, const float *w_th, const float *c_th) {
   PMFCHK(ctx_bind(c));
   if (c->N == 0) return pmf_fail("data not set");
-  for (int which = 2; which <= 5; ++which) { dev_free(&c->P[which].wq); dev_free(&c->P[which].cq); }
+  for (int which = 2; which <= 5; ++which) { c->P[which].wq.free(); c->P[which].cq.free(); }
   if (n_ranges > 0) {
-    int64_t *ds = nullptr, *de = nullptr;
-    float *dw = nullptr, *dc = nullptr;
-    PMFCHK(dev_alloc(&ds, (size_t)n_ranges, false));
-    PMFCHK(dev_alloc(&de, (size_t)n_ranges, false));
-    PMFCHK(dev_alloc(&dw, (size_t)n_ranges, false));
-    PMFCHK(dev_alloc(&dc, (size_t)n_ranges, false));
-    HIPCHK(hipMemcpy(ds, s1, sizeof(int64_t) * n_ranges, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(de, e1, sizeof(int64_t) * n_ranges, hipMemcpyHostToDevice));
+    DevBuf<int64_t> ds, de;
+    DevBuf<float> dw, dc;
+    PMFCHK(upload_new(ds, s1, (size_t)n_ranges));
+    PMFCHK(upload_new(de, e1, (size_t)n_ranges));
     for (int t = 0; t < 2; ++t) {
       const float *w = t == 0 ? w_ls : w_mu, *cc = t == 0 ? c_ls : c_mu;
       if (!w || !cc) continue;
       ParamBuf &b = c->P[2 + t];
-      PMFCHK(dev_alloc(&b.wq, (size_t)c->N));
-      PMFCHK(dev_alloc(&b.cq, (size_t)c->N));
-      HIPCHK(hipMemcpy(dw, w, sizeof(float) * n_ranges, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(dc, cc, sizeof(float) * n_ranges, hipMemcpyHostToDevice));
+      PMFCHK(b.wq.alloc((size_t)c->N, true));
+      PMFCHK(b.cq.alloc((size_t)c->N, true));
+      PMFCHK(upload_new(dw, w, (size_t)n_ranges));
+      PMFCHK(upload_new(dc, cc, (size_t)n_ranges));
       k_expand_colparam<<<nblocks(c->N, 256), 256, 0, c->stream>>>(b.wq, b.cq, c->N, ds, de, dw, dc, n_ranges);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(c->stream));
     }
-    dev_free(&ds); dev_free(&de); dev_free(&dw); dev_free(&dc);
   }
   if (c->n_bv > 0 && c->P[4].n > 0) {
     const int64_t nbt = c->bvb_off[c->n_bv];
     std::vector<int32_t> nbs((size_t)c->n_bv);
     for (int v = 0; v < c->n_bv; ++v) nbs[v] = c->views[v].nb;
-    int32_t *dnb = nullptr;
-    int64_t *dvo = nullptr, *dbo = nullptr;
-    float *dw = nullptr, *dc = nullptr;
-    PMFCHK(dev_alloc(&dnb, (size_t)c->n_bv, false));
-    PMFCHK(dev_alloc(&dvo, (size_t)c->n_bv + 1, false));
-    PMFCHK(dev_alloc(&dbo, (size_t)c->n_bv + 1, false));
-    PMFCHK(dev_alloc(&dw, (size_t)nbt, false));
-    PMFCHK(dev_alloc(&dc, (size_t)nbt, false));
-    HIPCHK(hipMemcpy(dnb, nbs.data(), sizeof(int32_t) * c->n_bv, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dvo, c->val_off.data(), sizeof(int64_t) * (c->n_bv + 1), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dbo, c->bvb_off.data(), sizeof(int64_t) * (c->n_bv + 1), hipMemcpyHostToDevice));
+    DevBuf<int32_t> dnb;
+    DevBuf<int64_t> dvo, dbo;
+    DevBuf<float> dw, dc;
+    PMFCHK(upload_new(dnb, nbs.data(), (size_t)c->n_bv));
+    PMFCHK(upload_new(dvo, c->val_off.data(), (size_t)c->n_bv + 1));
+    PMFCHK(upload_new(dbo, c->bvb_off.data(), (size_t)c->n_bv + 1));
     for (int t = 0; t < 2; ++t) {
       const float *w = t == 0 ? w_ld : w_th, *cc = t == 0 ? c_ld : c_th;
       if (!w || !cc) continue;
       ParamBuf &b = c->P[4 + t];
-      PMFCHK(dev_alloc(&b.wq, (size_t)b.n));
-      PMFCHK(dev_alloc(&b.cq, (size_t)b.n));
-      HIPCHK(hipMemcpy(dw, w, sizeof(float) * (size_t)nbt, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(dc, cc, sizeof(float) * (size_t)nbt, hipMemcpyHostToDevice));
+      PMFCHK(b.wq.alloc((size_t)b.n, true));
+      PMFCHK(b.cq.alloc((size_t)b.n, true));
+      PMFCHK(upload_new(dw, w, (size_t)nbt));
+      PMFCHK(upload_new(dc, cc, (size_t)nbt));
       k_expand_batchreg<<<nblocks(b.n, 256), 256, 0, c->stream>>>(b.wq, b.cq, b.n, c->d_val_view, dvo, dnb, dbo, dw, dc);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(c->stream));
     }
-    dev_free(&dnb); dev_free(&dvo); dev_free(&dbo); dev_free(&dw); dev_free(&dc);
   }
   return 0;
 }
@@ -1204,7 +1167,7 @@ static int prepare(pmf_ctx *c) {
   c->btd_ok = false;
   c->nbs = c->n_bv > 0 ? 0 : 16;   // (0: no dense table; 16: the layer pass's tables without batch views)
   if (c->n_bv > 0) {
-    if (!c->d_views) PMFCHK(dev_alloc(&c->d_views, (size_t)PMF_MAXV, false));   // (prepare() runs every layer epoch: no re-allocation)
+    PMFCHK(c->d_views.ensure((size_t)PMF_MAXV, false));   // (prepare() runs every layer epoch: no re-allocation)
     if (c->views_dirty) {
       HIPCHK(hipMemcpyAsync(c->d_views, c->views.data(), sizeof(ViewDesc) * (size_t)c->n_bv, hipMemcpyHostToDevice, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
@@ -1217,14 +1180,8 @@ static int prepare(pmf_ctx *c) {
     const int64_t Npad = (c->N + 31) / 32 * 32;
     if (nb_max <= 255 && (Npad << shift) < (1ll << 31)) {   // (the kernels index the table with 32 bits)
       c->nbs = 1 << shift;
-      if (Npad * c->nbs > c->btd_cap) {
-        PMFCHK(dev_alloc(&c->btd, (size_t)(Npad * c->nbs), false));
-        c->btd_cap = Npad * c->nbs;
-      }
-      if (Npad > c->colview_cap) {
-        PMFCHK(dev_alloc(&c->colview, (size_t)Npad, false));
-        c->colview_cap = Npad;
-      }
+      PMFCHK(c->btd.ensure((size_t)(Npad * c->nbs), false));
+      PMFCHK(c->colview.ensure((size_t)Npad, false));
       DenseBtabArgs da;
       memset(&da, 0, sizeof(da));
       da.colmeta = c->colmeta; da.btab = c->btab; da.btd = c->btd; da.colview = c->colview; da.N = c->N; da.Npad = Npad; da.nbs_shift = shift;
@@ -1258,10 +1215,7 @@ __global__ void k_tile_flags(const void *__restrict__ D, int64_t ntiles, uint32_
 static int ensure_tile_flags(pmf_ctx *c) {
   if (c->tflags_valid) return 0;
   const int64_t ntiles = c->nRB * (c->D_Npad / 32);
-  if (ntiles > c->tflags_cap) {
-    PMFCHK(dev_alloc(&c->tflags, (size_t)ntiles, false));
-    c->tflags_cap = ntiles;
-  }
+  PMFCHK(c->tflags.ensure((size_t)ntiles, false));
   if (ntiles > 0x7fffffff) return pmf_fail("too many tiles");
   k_tile_flags<<<(unsigned)ntiles, 256, 0, c->stream>>>(c->D, ntiles, c->tflags, c->store == PMF_STORE_BF16);
   HIPCHK(hipGetLastError());
@@ -1443,11 +1397,11 @@ static int compute_work_split(pmf_ctx *c, WorkSplit &ws, int grid, int64_t n_rp,
       ws.piece_rp.push_back((int32_t)rp);
     }
   }
-  PMFCHK(dev_alloc(&ws.wg_begin, (size_t)grid + 1, false));
-  PMFCHK(dev_alloc(&ws.c_off, (size_t)n_ct + 1, false));
-  PMFCHK(dev_alloc(&ws.c_idx, h_idx.size(), false));
-  PMFCHK(dev_alloc(&ws.piece_base, (size_t)grid, false));
-  PMFCHK(dev_alloc(&ws.d_piece_base_abs, (size_t)grid, false));
+  PMFCHK(ws.wg_begin.alloc((size_t)grid + 1, false));
+  PMFCHK(ws.c_off.alloc((size_t)n_ct + 1, false));
+  PMFCHK(ws.c_idx.alloc(h_idx.size(), false));
+  PMFCHK(ws.piece_base.alloc((size_t)grid, false));
+  PMFCHK(ws.d_piece_base_abs.alloc((size_t)grid, false));
   HIPCHK(hipMemcpyAsync(ws.wg_begin, wb.data(), sizeof(int64_t) * ((size_t)grid + 1), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(ws.c_off, h_off.data(), sizeof(int32_t) * h_off.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(ws.c_idx, h_idx.data(), sizeof(int32_t) * h_idx.size(), hipMemcpyHostToDevice, c->stream));
@@ -1516,13 +1470,8 @@ static int ensure_panel_slots(pmf_ctx *c, int BM, PanelSlots **out) {
   ps.BM = BM;
   ps.serial = c->views_serial;
   if (ok) {
-    ps.pm_cap = ps.row_slot_cap = 0;
-    PMFCHK(dev_alloc(&ps.pm, pm.size(), false));
-    PMFCHK(dev_alloc(&ps.row_slot, std::max<size_t>(rs.size(), 1), false));
-    ps.pm_cap = (int64_t)pm.size();
-    ps.row_slot_cap = (int64_t)std::max<size_t>(rs.size(), 1);
-    HIPCHK(hipMemcpy(ps.pm, pm.data(), pm.size(), hipMemcpyHostToDevice));
-    if (!rs.empty()) HIPCHK(hipMemcpy(ps.row_slot, rs.data(), rs.size(), hipMemcpyHostToDevice));
+    PMFCHK(upload_new(ps.pm, pm.data(), pm.size()));
+    PMFCHK(upload_new(ps.row_slot, rs.data(), rs.size()));
   }
   return 0;
 }
@@ -1699,12 +1648,7 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
   // columns without clamping (they are accumulated and never stored): one tile of padding at THIS Kp keeps those loads in
   // bounds (the capacity counts the padding: a buffer allocated at a smaller Kp has less of it)
   const size_t gy_need = (size_t)g.grid_max * (size_t)slab_stride + (size_t)PMF_BN * (size_t)c->Kp;
-  if (want_gy && gy_need > c->gy_slabs_cap) {
-    dev_free(&c->gy_slabs);
-    c->gy_slabs_cap = 0;
-    PMFCHK(dev_alloc(&c->gy_slabs, gy_need, false));
-    c->gy_slabs_cap = gy_need;
-  }
+  if (want_gy) PMFCHK(c->gy_slabs.ensure(gy_need, false));
   if (want_gx && serial_sum != c->gx_serial) {
     // slot map of the gX partial slabs: chunk s owns slots [slot_base, slot_base + pieces); per row panel, its slots in
     // work-sequence order (chunk, then segment, then position inside the unit) -- the order k_gx_reduce sums them in
@@ -1716,7 +1660,7 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
       for (size_t p = 0; p < ws.piece_rp.size(); ++p) lists[(size_t)ws.piece_rp[p]].push_back(base + (int32_t)p);
       std::vector<int32_t> abs(ws.h_piece_base);
       for (auto &v : abs) v += base;
-      HIPCHK(hipMemcpy(ws.d_piece_base_abs, abs.data(), sizeof(int32_t) * abs.size(), hipMemcpyHostToDevice));
+      PMFCHK(ws.d_piece_base_abs.upload(abs.data(), abs.size()));
       base += (int32_t)ws.piece_rp.size();
     }
     std::vector<int32_t> off((size_t)g.n_rp + 1, 0), idx;
@@ -1725,10 +1669,8 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
       off[(size_t)rp + 1] = (int32_t)idx.size();
     }
     if (idx.empty()) idx.push_back(0);
-    PMFCHK(dev_alloc(&c->gx_off, off.size(), false));
-    PMFCHK(dev_alloc(&c->gx_idx, idx.size(), false));
-    HIPCHK(hipMemcpy(c->gx_off, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->gx_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice));
+    PMFCHK(upload_new(c->gx_off, off.data(), off.size()));
+    PMFCHK(upload_new(c->gx_idx, idx.data(), idx.size()));
     c->gx_serial = serial_sum;
   }
   if (want_gx) {
@@ -1737,13 +1679,7 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     // followed by an sb8 pass reuses the split and the slot map, and needs twice the bytes)
     size_t pieces = 0;
     for (int s = 0; s < g.S; ++s) pieces += c->splits[(size_t)s].piece_rp.size();
-    const size_t need = pieces * (size_t)f.BM() * (size_t)c->Kp;
-    if (need > c->gx_part_cap) {
-      dev_free(&c->gx_part);
-      c->gx_part_cap = 0;
-      PMFCHK(dev_alloc(&c->gx_part, need, false));   // every slot is written whole by its piece before it is read
-      c->gx_part_cap = need;
-    }
+    PMFCHK(c->gx_part.ensure(pieces * (size_t)f.BM() * (size_t)c->Kp, false));   // every slot is written whole by its piece before it is read
   }
   PMFCHK(ensure_tile_flags(c));
   if (f.img != IMG_NONE) {
@@ -1754,11 +1690,11 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     // X images + PMF_XSB_PAD row blocks: sb_split_x writes whole panels, roundup(nRB, nblk) blocks.  The capacity counts
     // the padding at THIS xblk (a buffer allocated for narrower images may hold fewer bytes of it).
     const size_t xb = ((size_t)c->nRB + PMF_XSB_PAD) * xblk, yb = (size_t)g.n_ct_all * yblk;
-    if (xb > c->xsb_cap) { dev_free(&c->xsb); c->xsb_cap = 0; PMFCHK(dev_alloc(&c->xsb, xb, true)); c->xsb_cap = xb; }
-    if (yb > c->ysb_cap) { dev_free(&c->ysb); c->ysb_cap = 0; PMFCHK(dev_alloc(&c->ysb, yb, false)); c->ysb_cap = yb; }
-    if (f.img == IMG_SB8 && !c->sb8_scale) {
-      PMFCHK(dev_alloc(&c->sb8_scale, (size_t)(1 + PMF_MAX_CHUNKS), false));
-      PMFCHK(dev_alloc(&c->sb8_max, (size_t)(1 + PMF_MAX_CHUNKS)));
+    PMFCHK(c->xsb.ensure(xb, true));    // (the padding blocks are zeroed here, once)
+    PMFCHK(c->ysb.ensure(yb, false));
+    if (f.img == IMG_SB8) {
+      PMFCHK(c->sb8_scale.ensure((size_t)(1 + PMF_MAX_CHUNKS), false));
+      PMFCHK(c->sb8_max.ensure((size_t)(1 + PMF_MAX_CHUNKS), true));
     }
   }
   return 0;
@@ -1784,20 +1720,20 @@ int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
   const int64_t gx_slot_stride = (int64_t)f.BM() * Kp, slab_stride = Kp * c->N;
   int n = 0;
   // every piece stores its whole BM x Kp partial at slot * gx_slot_stride; the slots of all chunks are numbered through
-  out[n++] = {"gx_part", want_gx ? pieces * gx_slot_stride * 4 : 0, (int64_t)c->gx_part_cap * 4};
+  out[n++] = {"gx_part", want_gx ? pieces * gx_slot_stride * 4 : 0, (int64_t)c->gx_part.bytes()};
   // workgroup wg < grid works in gy_slabs + wg * slab_stride: the live columns of its tiles, sb8 the whole last tile
   out[n++] = {"gy_slabs", want_gy ? ((grid_top - 1) * slab_stride + (f.img == IMG_SB8 ? Npad * Kp : slab_stride)) * 4 : 0,
-              (int64_t)c->gy_slabs_cap * 4};
+              (int64_t)c->gy_slabs.bytes()};
   // row blocks < nRB (clamped); sb8 and its split whole panels of nblk blocks
-  out[n++] = {"xsb", f.img != IMG_NONE ? (c->nRB + f.nblk - 1) / f.nblk * f.nblk * f.xblk : 0, (int64_t)c->xsb_cap};
-  out[n++] = {"ysb", f.img != IMG_NONE ? g.n_ct_all * f.yblk : 0, (int64_t)c->ysb_cap};
+  out[n++] = {"xsb", f.img != IMG_NONE ? (c->nRB + f.nblk - 1) / f.nblk * f.nblk * f.xblk : 0, (int64_t)c->xsb.bytes()};
+  out[n++] = {"ysb", f.img != IMG_NONE ? g.n_ct_all * f.yblk : 0, (int64_t)c->ysb.bytes()};
   // all 32 columns of every tile, the last slot of a column the identity
-  out[n++] = {"btd", bt ? (Npad << nbs_shift) * (int64_t)sizeof(float2) : 0, c->btd_cap * (int64_t)sizeof(float2)};
-  out[n++] = {"colview", bt ? Npad : 0, c->colview_cap};
-  out[n++] = {"tflags", g.n_ct_all * c->nRB * 4, c->tflags_cap * 4};
-  out[n++] = {"loss_partial", grid_sum * 8, c->loss_cap * 8};
-  out[n++] = {"pm", bt ? g.n_rp * c->n_bv * 16 : 0, bt ? g.ps->pm_cap : 0};
-  out[n++] = {"row_slot", bt ? (int64_t)c->n_bv * c->M : 0, bt ? g.ps->row_slot_cap : 0};
+  out[n++] = {"btd", bt ? (Npad << nbs_shift) * (int64_t)sizeof(float2) : 0, (int64_t)c->btd.bytes()};
+  out[n++] = {"colview", bt ? Npad : 0, (int64_t)c->colview.bytes()};
+  out[n++] = {"tflags", g.n_ct_all * c->nRB * 4, (int64_t)c->tflags.bytes()};
+  out[n++] = {"loss_partial", grid_sum * 8, (int64_t)c->loss_partial.bytes()};
+  out[n++] = {"pm", bt ? g.n_rp * c->n_bv * 16 : 0, bt ? (int64_t)g.ps->pm.bytes() : 0};
+  out[n++] = {"row_slot", bt ? (int64_t)c->n_bv * c->M : 0, bt ? (int64_t)g.ps->row_slot.bytes() : 0};
   static_assert(PMF_PASS_EXTENTS == 10, "fused_pass_extents");
   return n;
 }
@@ -1886,8 +1822,8 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   }
 #ifdef PMF_STAMPS
   {
-    static unsigned long long *d_stamps = nullptr;
-    if (!d_stamps) HIPCHK(hipMalloc((void **)&d_stamps, sizeof(unsigned long long) * 16 * 8 * 1024));
+    static DevBuf<unsigned long long> d_stamps;
+    PMFCHK(d_stamps.ensure((size_t)16 * 8 * 1024, false));
     HIPCHK(hipMemsetAsync(d_stamps, 0, sizeof(unsigned long long) * 16 * 8 * 1024, c->stream));
     a.stamps = d_stamps;
     g_stamps = d_stamps;
@@ -2006,10 +1942,7 @@ static int launch_layer_grad(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
   const int64_t nbt = c->n_bv > 0 ? c->val_off[c->n_bv] : 0;
   a.nbt = nbt;
   a.part_stride = 2 * c->N + 2 * nbt;
-  if ((size_t)(a.part_stride * gy) > c->lgrad_part_cap) {
-    PMFCHK(dev_alloc(&c->lgrad_part, (size_t)(a.part_stride * gy), false));
-    c->lgrad_part_cap = (size_t)(a.part_stride * gy);
-  }
+  PMFCHK(c->lgrad_part.ensure((size_t)(a.part_stride * gy), false));
   a.part = c->lgrad_part;
   PMFCHK(col_walk_launch(c, {k_layer_grad<1>, k_layer_grad<2>, k_layer_grad<3>, k_layer_grad<4>}, a, gx, gy, "layer-gradient"));
   PMFCHK(sum_parts(c, a.part, a.part_stride, (int)gy, a.g_mu, c->N));
@@ -2047,10 +1980,7 @@ static int launch_layer_pass(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
   // fixed order by k_layer_reduce.  R <= ceil(4 n_cu / n_seg) keeps R * N near 4 n_cu * 64 columns (~130 MB of tables at
   // nbs = 16) while n_seg < 4 n_cu; from n_seg >= 4 n_cu on R = 1 and the tables grow with N (2 NW * N * nbs float2).
   const int64_t lg_stride = c->N * nbs, n_parts = R * lnw * 2;
-  if (lg_stride * n_parts > c->LG_cap) {
-    PMFCHK(dev_alloc(&c->LG, (size_t)(lg_stride * n_parts), false));
-    c->LG_cap = lg_stride * n_parts;
-  }
+  PMFCHK(c->LG.ensure((size_t)(lg_stride * n_parts), false));
   HIPCHK(hipMemsetAsync(c->LG, 0, sizeof(float2) * (size_t)(lg_stride * n_parts), c->stream));
   if (with_loss) PMFCHK(ensure_loss_partials(c, grid));
   LayerPassArgs a;
@@ -2189,6 +2119,12 @@ extern "C" int pmf_debug_pass_extents(pmf_ctx *c, int update_X, int update_Y, co
   }
   if (n_out) *n_out = n;
   return cap_override ? check_pass_extents(e, n) : 0;
+}
+
+extern "C" int pmf_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes) {
+  if (device_bytes) *device_bytes = pmf_live_bytes[0].load();
+  if (pinned_bytes) *pinned_bytes = pmf_live_bytes[1].load();
+  return 0;
 }
 
 extern "C" int pmf_epoch_begin(pmf_ctx *c, const pmf_fit_opts *o) {
@@ -2339,15 +2275,14 @@ extern "C" int pmf_forward(pmf_ctx *c, float *Z_host) {
   PMFCHK(ctx_bind(c));
   if (!Z_host) return pmf_fail("null output");
   const size_t bytes = sizeof(float) * (size_t)(c->M * c->N);
-  float *Z = nullptr;
-  HIPCHK(hipMalloc((void **)&Z, bytes));
+  DevBuf<float> Z;
+  PMFCHK(Z.alloc((size_t)(c->M * c->N), false));
   int rc = run_forward(c, Z, 0, 0, 0.f, 0.f);
   if (rc == 0) {
     hipError_t e = hipMemcpyAsync(Z_host, Z, bytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) rc = pmf_fail("copy back failed: %s", hipGetErrorString(e));
   }
-  (void)hipFree(Z);
   return rc;
 }
 
@@ -2356,15 +2291,6 @@ extern "C" int pmf_forward(pmf_ctx *c, float *Z_host) {
 // ------------------------------------------------------------------------------------------------
 #define PMF_IMPUTE_STAGE_MAX ((size_t)256 << 20)   // the bound of pmf_set_data's upload chunks
 
-static int ensure_impute_stage(pmf_ctx *c, size_t bytes) {
-  if (c->impute_stage_bytes >= bytes) return 0;
-  if (c->impute_stage) HIPCHK(hipFree(c->impute_stage));
-  c->impute_stage = nullptr;
-  c->impute_stage_bytes = 0;
-  HIPCHK(hipMalloc(&c->impute_stage, bytes));
-  c->impute_stage_bytes = bytes;
-  return 0;
-}
 
 // what every impute call checks before it touches the device.  The context needs M, N (a data matrix has been set: it is
 // what fixes them), factors and complete batch views; the values of D only for PMF_IMPUTE_KEEP_OBSERVED.
@@ -2429,9 +2355,9 @@ extern "C" int pmf_impute(pmf_ctx *c, int flags, int64_t row_start1, int64_t row
     if (v > 0) ch = std::min<int64_t>(v, cap);
   }
   ch = std::min(ch, rows);
-  PMFCHK(ensure_impute_stage(c, sizeof(float) * (size_t)(ch * c->N)));
+  PMFCHK(c->impute_stage.ensure(sizeof(float) * (size_t)(ch * c->N), false));
   PMFCHK(prepare(c));
-  float *stage = (float *)c->impute_stage;
+  float *stage = (float *)c->impute_stage.p;
   for (int64_t r0 = row_start1 - 1; r0 < row_stop1; r0 += ch) {
     const int64_t nr = std::min(ch, row_stop1 - r0);
     PMFCHK(impute_launch(c, flags, r0, r0 + nr, stage, nr));
@@ -2453,9 +2379,9 @@ extern "C" int pmf_impute_entries(pmf_ctx *c, int flags, int64_t n, const int64_
       return pmf_fail("pmf_impute_entries: entry %lld = (%lld, %lld) is outside 1..%lld x 1..%lld", (long long)e, (long long)rows1[e],
                       (long long)cols1[e], (long long)c->M, (long long)c->N);
   const int64_t ch = std::min<int64_t>(n, 1ll << 22);   // 20 bytes of staging per entry
-  PMFCHK(ensure_impute_stage(c, (size_t)ch * (2 * sizeof(int64_t) + sizeof(float))));
+  PMFCHK(c->impute_stage.ensure((size_t)ch * (2 * sizeof(int64_t) + sizeof(float)), false));
   PMFCHK(prepare(c));
-  int64_t *d_rows = (int64_t *)c->impute_stage, *d_cols = d_rows + ch;
+  int64_t *d_rows = (int64_t *)c->impute_stage.p, *d_cols = d_rows + ch;
   float *d_out = (float *)(d_cols + ch);
   for (int64_t e0 = 0; e0 < n; e0 += ch) {
     const int64_t ne = std::min(ch, n - e0);
@@ -2482,7 +2408,7 @@ extern "C" int pmf_synth_data(pmf_ctx *c, uint64_t seed, float noise, float frac
   PMFCHK(ctx_bind(c));
   if (!c->D) return pmf_fail("data buffer not allocated (pmf_set_data_device(ctx, NULL, M, N, store))");
   c->tflags_valid = false;
-  PMFCHK(run_forward(c, (float *)c->D, 1, seed, noise, frac_nan, c->nRB));
+  PMFCHK(run_forward(c, (float *)c->D.p, 1, seed, noise, frac_nan, c->nRB));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
@@ -2506,8 +2432,8 @@ int stats_pass(pmf_ctx *c, int use_factors, bool want_cols, bool want_batch, con
   a.use_factors = use_factors;
   // scratch: [results nfl][gy private partial vectors of nfl]; every entry of a partial vector is written by its block row,
   // the block rows are then added in fixed order (k_sum_parts): no float atomics, bitwise reproducible statistics
-  PMFCHK(ensure_scratch(c, sizeof(float) * std::max<size_t>(nfl * (size_t)(gy + 1), 1)));
-  float *buf = (float *)c->scratch, *part = buf + nfl;
+  PMFCHK(c->scratch.ensure(sizeof(float) * std::max<size_t>(nfl * (size_t)(gy + 1), 1), false));
+  float *buf = (float *)c->scratch.p, *part = buf + nfl;
   a.part_stride = (int64_t)nfl;
   if (want_cols) { a.col_n = part; a.col_sum = part + c->N; a.col_sumsq = part + 2 * c->N; a.col_sqerr = part + 3 * c->N; a.col_ssqg = part + 4 * c->N; }
   a.b_n = nbt ? part + ncol : nullptr;

@@ -31,21 +31,14 @@ struct LbVec { float *x, *y; };         // the X segment and the Y segment of on
 struct LbfgsState {
   int K = 0, m = 0;
   int64_t M = 0, N = 0, nX = 0, nY = 0;
-  float *pool = nullptr;                // (2 m + 4) vectors: g, g_old, orig, m + 1 step vectors (p and S), m of Y
-  size_t pool_bytes = 0;
-  double *part = nullptr;               // [LB_SLABS][3][LB_MAXB]
-  double *cf = nullptr;                 // [CF_N]
-  double *h_out = nullptr;              // pinned [8]
+  DevBuf<float> pool;                   // (2 m + 4) vectors: g, g_old, orig, m + 1 step vectors (p and S), m of Y
+  DevBuf<double> part;                  // [LB_SLABS][3][LB_MAXB]
+  DevBuf<double> cf;                    // [CF_N]
+  PinnedBuf<double> h_out;              // pinned [8]
 };
 
 void lbfgs_free(pmf_ctx *c) {
-  LbfgsState *st = c->lbfgs;
-  if (!st) return;
-  dev_free(&st->pool);
-  dev_free(&st->part);
-  dev_free(&st->cf);
-  if (st->h_out) (void)hipHostFree(st->h_out);
-  delete st;
+  delete c->lbfgs;
   c->lbfgs = nullptr;
 }
 
@@ -58,18 +51,13 @@ static int lbfgs_ensure(pmf_ctx *c, int m) {
   st->K = c->K; st->M = c->M; st->N = c->N; st->m = m;
   st->nX = (int64_t)c->Kp * c->M;
   st->nY = (int64_t)c->Kp * c->N;
-  const size_t bytes = (size_t)(2 * m + 4) * (size_t)(st->nX + st->nY) * sizeof(float);
-  if (hipMalloc((void **)&st->pool, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    st->pool = nullptr;
-    lbfgs_free(c);
-    return pmf_fail("pmf_fit_lbfgs: cannot allocate %zu bytes for %d vectors of %lld floats (m = %d)", bytes, 2 * m + 4,
-                    (long long)((int64_t)c->Kp * (c->M + c->N)), m);
+  char what[96];
+  snprintf(what, sizeof(what), "pmf_fit_lbfgs: %d vectors of %lld floats (m = %d)", 2 * m + 4, (long long)(st->nX + st->nY), m);
+  if (st->pool.alloc((size_t)(2 * m + 4) * (size_t)(st->nX + st->nY), false, what) < 0 ||
+      st->part.alloc((size_t)LB_SLABS * 3 * LB_MAXB, true) < 0 || st->cf.alloc((size_t)CF_N, true) < 0 || st->h_out.alloc(8, false) < 0) {
+    lbfgs_free(c);   // (sets no error of its own)
+    return -1;
   }
-  st->pool_bytes = bytes;
-  PMFCHK(dev_alloc(&st->part, (size_t)LB_SLABS * 3 * LB_MAXB));
-  PMFCHK(dev_alloc(&st->cf, (size_t)CF_N));
-  HIPCHK(hipHostMalloc((void **)&st->h_out, sizeof(double) * 8));
   return 0;
 }
 

@@ -194,11 +194,6 @@ void netreg_free(pmf_ctx *c, int which) {
   if (!r) return;
   (void)hipSetDevice(c->device);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  dev_free(&r->voff);
-  dev_free(&r->aa_rp); dev_free(&r->ab_rp); dev_free(&r->abt_rp); dev_free(&r->bb_rp);
-  dev_free(&r->aa_col); dev_free(&r->ab_col); dev_free(&r->abt_col); dev_free(&r->bb_col);
-  dev_free(&r->aa_val); dev_free(&r->ab_val); dev_free(&r->abt_val); dev_free(&r->bb_val);
-  dev_free(&r->u); dev_free(&r->work); dev_free(&r->PT); dev_free(&r->grad); dev_free(&r->iters); dev_free(&r->uloss);
   delete r;
   c->net[which] = nullptr;
 }
@@ -248,10 +243,9 @@ static int check_csr(const pmf_csr &m, int64_t rows, int64_t cols, const char *n
 }
 
 template <typename T>
-static int upload_new(T **dst, const std::vector<T> &h) {
-  PMFCHK(dev_alloc(dst, h.size(), false));
-  if (!h.empty()) HIPCHK(hipMemcpy(*dst, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-  return 0;
+static int upload_new(DevBuf<T> &dst, const std::vector<T> &h) {
+  PMFCHK(dst.alloc(h.size(), false));
+  return dst.upload(h.data(), h.size());
 }
 
 // one family of blocks concatenated: row pointers made absolute, `rows(k)` rows for factor k (plus one closing entry each)
@@ -266,6 +260,11 @@ struct CsrCat {
     rp.push_back(base + nnz);
     col.insert(col.end(), m.col, m.col + nnz);
     val.insert(val.end(), m.val, m.val + nnz);
+  }
+  int upload(DevBuf<int64_t> &d_rp, DevBuf<int32_t> &d_col, DevBuf<float> &d_val) const {
+    PMFCHK(upload_new(d_rp, rp));
+    PMFCHK(upload_new(d_col, col));
+    return upload_new(d_val, val);
   }
 };
 
@@ -316,24 +315,21 @@ static int add_network(pmf_ctx *c, int which, int K, const pmf_csr *AA, const pm
   r->K = K; r->n = n; r->V = V; r->p = p; r->h_voff = voff;
   for (int k = 0; k < K; ++k) r->vmax = std::max(r->vmax, voff[(size_t)k + 1] - voff[(size_t)k]);
   r->rb = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, NETREG_SLOTS / K));
-  int rc = 0;
-  do {
-    if ((rc = upload_new(&r->voff, voff)) < 0) break;
-    if ((rc = upload_new(&r->aa_rp, aa.rp)) < 0 || (rc = upload_new(&r->aa_col, aa.col)) < 0 || (rc = upload_new(&r->aa_val, aa.val)) < 0) break;
-    if ((rc = upload_new(&r->ab_rp, ab.rp)) < 0 || (rc = upload_new(&r->ab_col, ab.col)) < 0 || (rc = upload_new(&r->ab_val, ab.val)) < 0) break;
-    if ((rc = upload_new(&r->abt_rp, abt.rp)) < 0 || (rc = upload_new(&r->abt_col, abt.col)) < 0 || (rc = upload_new(&r->abt_val, abt.val)) < 0) break;
-    if ((rc = upload_new(&r->bb_rp, bb.rp)) < 0 || (rc = upload_new(&r->bb_col, bb.col)) < 0 || (rc = upload_new(&r->bb_val, bb.val)) < 0) break;
-    if ((rc = upload_new(&r->u, hu)) < 0) break;
-    if ((rc = dev_alloc(&r->work, r->vmax > NETREG_V_LDS ? (size_t)(4 * V) : 0)) < 0) break;
-    if ((rc = dev_alloc(&r->PT, (size_t)(K * n))) < 0 || (rc = dev_alloc(&r->grad, (size_t)c->P[which].n)) < 0) break;
-    if ((rc = dev_alloc(&r->iters, (size_t)K)) < 0 || (rc = dev_alloc(&r->uloss, (size_t)K)) < 0) break;
-  } while (0);
-  if (rc < 0) {
-    const std::string msg = pmf_last_error();
-    netreg_free(c, which);
-    return pmf_fail("%s", msg.c_str());
-  }
-  return 0;
+  const int rc = [&]() -> int {
+    PMFCHK(upload_new(r->voff, voff));
+    PMFCHK(aa.upload(r->aa_rp, r->aa_col, r->aa_val));
+    PMFCHK(ab.upload(r->ab_rp, r->ab_col, r->ab_val));
+    PMFCHK(abt.upload(r->abt_rp, r->abt_col, r->abt_val));
+    PMFCHK(bb.upload(r->bb_rp, r->bb_col, r->bb_val));
+    PMFCHK(upload_new(r->u, hu));
+    PMFCHK(r->work.alloc(r->vmax > NETREG_V_LDS ? (size_t)(4 * V) : 0, true));
+    PMFCHK(r->PT.alloc((size_t)(K * n), true));
+    PMFCHK(r->grad.alloc((size_t)c->P[which].n, true));
+    PMFCHK(r->iters.alloc((size_t)K, true));
+    return r->uloss.alloc((size_t)K, true);
+  }();
+  if (rc < 0) netreg_free(c, which);   // (sets no error of its own: the message of the failed step stays)
+  return rc;
 }
 
 extern "C" int pmf_add_xreg_network(pmf_ctx *c, int K, const pmf_csr *AA, const pmf_csr *AB, const pmf_csr *BB, const float *const *u0, float p) {
@@ -373,7 +369,7 @@ static int add_l1(pmf_ctx *c, int which, const float *w, const uint8_t *mask, fl
   for (int64_t j = 0; j < n; ++j)
     for (int k = 0; k < c->K; ++k)
       if (!mask || mask[j * c->K + k]) h[(size_t)(j * c->Kp + k)] += p * w[k];
-  if (!b.wl1) PMFCHK(dev_alloc(&b.wl1, (size_t)b.n, false));
+  PMFCHK(b.wl1.ensure((size_t)b.n, false));
   HIPCHK(hipMemcpy(b.wl1, h.data(), sizeof(float) * h.size(), hipMemcpyHostToDevice));
   return 0;
 }

@@ -268,10 +268,10 @@ struct GramPlan {
       }
     }
     gfirst[n] = (int32_t)pieces.size();
-    PMFCHK(d_pieces.alloc(pieces.size()));
-    PMFCHK(d_gfirst.alloc(gfirst.size()));
-    PMFCHK(slab.alloc(pieces.size() * (size_t)E));
-    PMFCHK(out.alloc((size_t)n * (size_t)E));
+    PMFCHK(d_pieces.alloc(pieces.size(), false));
+    PMFCHK(d_gfirst.alloc(gfirst.size(), false));
+    PMFCHK(slab.alloc(pieces.size() * (size_t)E, false));
+    PMFCHK(out.alloc((size_t)n * (size_t)E, false));
     return 0;
   }
 };
@@ -424,9 +424,9 @@ extern "C" int pmf_stage_whiten(pmf_ctx *c, int64_t M_total, int n_views, const 
   const int64_t one = 1, all = c->M;
   PMFCHK(B.gx.plan(c->K, 1, &one, &all, true));
   PMFCHK(B.gy.plan(c->K, n_views, starts1, stops1, true));
-  PMFCHK(B.d_xr.alloc((size_t)c->K));
-  PMFCHK(B.d_cs.alloc((size_t)n_views));
-  PMFCHK(B.d_rng.alloc(2 * (size_t)n_views));
+  PMFCHK(B.d_xr.alloc((size_t)c->K, false));
+  PMFCHK(B.d_cs.alloc((size_t)n_views, false));
+  PMFCHK(B.d_rng.alloc(2 * (size_t)n_views, false));
   B.xr.assign((size_t)c->K, 0.0);
   B.yd.assign((size_t)n_views * (size_t)c->K, 0.0);
   B.cs.assign((size_t)n_views, 0.0);
@@ -464,7 +464,7 @@ extern "C" int pmf_stage_rotate_by_svd(pmf_ctx *c, double *sing_out, double *U_o
   RotateBufs B;
   const int64_t one = 1, all = c->N;
   PMFCHK(B.g.plan(c->K, 1, &one, &all, false));
-  PMFCHK(B.d_U.alloc((size_t)c->K * c->K));
+  PMFCHK(B.d_U.alloc((size_t)c->K * c->K, false));
   B.G.assign((size_t)c->K * c->K, 0.0);
   B.U.assign((size_t)c->K * c->K, 0.0);
   B.lam.assign((size_t)c->K, 0.0);
@@ -506,7 +506,7 @@ extern "C" int pmf_stage_reorder_by_importance(pmf_ctx *c, int32_t *perm_out) {
   ReorderBufs B;
   const int64_t one = 1, all = c->N;
   PMFCHK(B.g.plan(c->K, 1, &one, &all, true));
-  PMFCHK(B.d_perm.alloc((size_t)c->K));
+  PMFCHK(B.d_perm.alloc((size_t)c->K, false));
   B.ssq.assign((size_t)c->K, 0.0);
   B.perm.assign((size_t)c->K, 0);
   return comm_error_exit(c, reorder_body(c, perm_out, B));

@@ -290,7 +290,7 @@ static int init_logsigma_body(pmf_ctx *c, DevBuf<double> &st) {
 extern "C" int pmf_stage_init_logsigma(pmf_ctx *c) {
   PMFCHK(stage_ready(c, "pmf_stage_init_logsigma", c ? c->M : 0));
   DevBuf<double> st;
-  PMFCHK(st.alloc((size_t)(5 * c->N)));
+  PMFCHK(st.alloc((size_t)(5 * c->N), false));
   return comm_error_exit(c, init_logsigma_body(c, st));
 }
 
@@ -308,7 +308,7 @@ static int reweight_body(pmf_ctx *c, int64_t M_total, DevBuf<double> &st) {
 extern "C" int pmf_stage_reweight_col_losses(pmf_ctx *c, int64_t M_total) {
   PMFCHK(stage_ready(c, "pmf_stage_reweight_col_losses", M_total));
   DevBuf<double> st;
-  PMFCHK(st.alloc((size_t)(5 * c->N)));
+  PMFCHK(st.alloc((size_t)(5 * c->N), false));
   return comm_error_exit(c, reweight_body(c, M_total, st));
 }
 extern "C" int pmf_get_noise_weights(pmf_ctx *c, float *w) {
@@ -344,9 +344,9 @@ extern "C" int pmf_stage_minimal_group_weights(pmf_ctx *c, int64_t M_total, floa
   DevBuf<double> st;
   DevBuf<int64_t> rng;
   DevBuf<float> out;
-  PMFCHK(st.alloc((size_t)(5 * c->N)));
-  PMFCHK(rng.alloc(2 * nr));
-  PMFCHK(out.alloc(nr));
+  PMFCHK(st.alloc((size_t)(5 * c->N), false));
+  PMFCHK(rng.alloc(2 * nr, false));
+  PMFCHK(out.alloc(nr, false));
   return comm_error_exit(c, group_weights_body(c, M_total, w_out, st, rng, out));
 }
 
@@ -355,16 +355,16 @@ struct EmBufs {   // what one pmf_stage_theta_delta_em call owns
   DevBuf<double> d_delta2, theta64, bcount, bsq, mom, part, d_diff;
   PinnedBuf<double> h_diff;
   int alloc(int64_t N, int64_t nbt, int64_t n_rows) {
-    PMFCHK(d_sigma2.alloc((size_t)N));
-    PMFCHK(theta_lsq.alloc((size_t)nbt));
-    PMFCHK(theta64.alloc((size_t)nbt));
-    PMFCHK(d_delta2.alloc((size_t)nbt));
-    PMFCHK(bcount.alloc((size_t)nbt));
-    PMFCHK(bsq.alloc((size_t)nbt));
-    PMFCHK(mom.alloc((size_t)(4 * n_rows)));
-    PMFCHK(part.alloc(2 * ST_MAXB));
-    PMFCHK(d_diff.alloc(1));
-    PMFCHK(h_diff.alloc(1));
+    PMFCHK(d_sigma2.alloc((size_t)N, false));
+    PMFCHK(theta_lsq.alloc((size_t)nbt, false));
+    PMFCHK(theta64.alloc((size_t)nbt, false));
+    PMFCHK(d_delta2.alloc((size_t)nbt, false));
+    PMFCHK(bcount.alloc((size_t)nbt, false));
+    PMFCHK(bsq.alloc((size_t)nbt, false));
+    PMFCHK(mom.alloc((size_t)(4 * n_rows), false));
+    PMFCHK(part.alloc(2 * ST_MAXB, false));
+    PMFCHK(d_diff.alloc(1, false));
+    PMFCHK(h_diff.alloc(1, false));
     return 0;
   }
 };
