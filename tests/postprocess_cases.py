@@ -9,7 +9,14 @@ Bounds (derived, not tuned):
                 factor 2 of slack; ref is numpy float64 on the float32 inputs.
   (b) stored    |got - ref64| <= 2^-23 |ref64| + 1e-10 max|ref64|: one float32 rounding of a float64 value whose own error is
                 far below 1e-10; NaN and +-inf positions identical.  (whiten! stores Y twice, as the host does: two roundings
-                of 2^-24 each, 2^-23 + 2^-48 in all, the last term far inside the absolute one.)"""
+                of 2^-24 each, 2^-23 + 2^-48 in all, the last term far inside the absolute one.)
+
+EDGE_SHAPES / EDGE_VIEWS (tests/test_gpu_postprocess_edges.py on the device, guarded on the CPU by
+tests/test_postprocess_edge_cases.py) sit on the seams of csrc/pmf_postprocess.hip that SHAPES does not reach: K = 31, 32, 64,
+65, 96, 97 around the template classes of k_pp_gram / k_pp_rotate and Kp = 96; N of 2049, 2176, 4100 (two and three Gram pieces
+of Y, a last piece of 1 and of 4 columns) and 2047 (one column short of a piece); M and N one short of, equal to and one past
+a tile of the in-place kernels k_pp_rotate (256, 128, 64 columns by K class) and k_pp_permute (64).  EDGE_VIEWS leaves columns
+in no view (the -1 of pp_find_range), puts views across and exactly on piece seams, and has 3, 2, 36, 3, 65 and 1 ranges."""
 from functools import lru_cache
 
 import numpy as np
@@ -17,6 +24,17 @@ import numpy as np
 SHAPES = [(1, 5, 7), (6, 331, 96), (33, 257, 1068), (128, 4099, 1068)]
 GRAM_CHUNK = 2048
 VIEWS = {7: [(1, 3), (4, 7)], 96: [(1, 48), (49, 96)], 1068: [(1, 1), (2, 3), (4, 1028), (1029, 1068)]}
+
+# (K, M, N) on the seams of pmf_postprocess.hip; what each one hits is asserted in tests/test_postprocess_edge_cases.py
+EDGE_SHAPES = [(31, 255, 257), (32, 256, 2049), (64, 129, 2176), (65, 63, 4100), (96, 70, 130), (97, 64, 2047)]
+EDGE_VIEWS = {
+    257: [(1, 1), (2, 2), (4, 256)],                                         # columns 3 and 257 are in no view
+    2049: [(2, 2040), (2045, 2049)],                                         # 1 and 2041..2044 in no view; view 2 across the seam
+    2176: [(61 * i + 1, 61 * i + 60) for i in range(35)] + [(2136, 2176)],   # 36 views, a one-column gap between each pair
+    4100: [(1, 2048), (2049, 4096), (4097, 4100)],                           # views end exactly on the seams
+    130: [(2 * i + 1, 2 * i + 2) for i in range(65)],
+    2047: [(1, 2047)],
+}
 
 
 @lru_cache(maxsize=None)

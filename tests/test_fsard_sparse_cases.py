@@ -2,7 +2,9 @@
 capacity (tests/fsard_sparse_ref.py): on the float64 oracle and the float32 restatement alone, every row lies above
 fsard_ref.CAPACITY, has a non-trivial A, keeps every decision of its loop at least fsard_ref.MARGIN from its threshold, and
 the float32 restatement stays within fsard_ref.MEASURED -- so the device bound of these rows is fsard_ref.TOL, the same as
-for the dense entry.  Also: the dense -> CSR helper against np.nonzero, and the `kernel=` argument of update_A_."""
+for the dense entry.  Also: the dense -> CSR helper against np.nonzero, and the `kernel=` argument of update_A_.
+At the end: the rows past one grid (fsard_sparse_ref.GRID_ROWS, run by tests/test_gpu_fsard_csr_grid.py) -- the launch
+geometry restated from the text of pmf_fsard_csr.hip, what each row makes the kernels do, and the same per-row guard."""
 import types
 
 import numpy as np
@@ -115,3 +117,77 @@ def test_update_A_refuses_an_unknown_kernel(pkg, kernel):
     with pytest.raises(ValueError, match="kernel"):
         pkg.update_A_(reg, np.zeros((2, 3), F), kernel=kernel)
     assert pkg.featureset_ard.FSARD_DENSE_CAPACITY == fr.CAPACITY
+
+
+# ---- the rows past one grid (fs.GRID_ROWS; tests/test_gpu_fsard_csr_grid.py) ---------------------------------------------------
+def test_launch_constants_are_read_from_the_source():
+    """A changed cap or block size fails here; an unmatched pattern gives None and fails too, instead of emptying the rows."""
+    sc = fs.csr_source_constants()
+    assert sc == dict(N_WG_CAP=2048, G_UPD_CAP=4096, UPD_THREADS=256, WAVES=4, LANES=64, KP_WIDE=64, K_PACKED=32, PER=True,
+                      DECIDE_THREADS=1024, UPD_BLOCK=256, FORWARD_TRIP=True), sc
+    assert sc["UPD_THREADS"] == sc["UPD_BLOCK"]                                 # g_upd counts blocks of the size it launches
+
+
+def test_grid_rows_leave_one_grid_where_they_say():
+    rows, sc = fs.GRID_ROWS, fs.csr_source_constants()
+    assert list(rows) == ["Nv8197_K33", "Nv16500_K65", "Nv16390_K25", "Nv32800_K16_mid", "LK_8200x128"]
+    assert fs.GRID_WIDE == tuple(rows)[:4]
+    geo = {n: fs.launch_geometry(s["L"], s["K"], s["Nv"]) for n, s in rows.items()}
+    want = {"Nv8197_K33": dict(kp=64, step=4, per=5, trips=2, empty=408), "Nv16500_K65": dict(kp=64, step=4, per=9, trips=3),
+            "Nv16390_K25": dict(kp=32, step=8, per=9, trips=2), "Nv32800_K16_mid": dict(kp=16, step=16, per=17, trips=2)}
+    for n in fs.GRID_WIDE:
+        g = geo[n]
+        assert g["n_wg"] == sc["N_WG_CAP"] > sc["DECIDE_THREADS"]               # k_fsc_decide: more than one partial per thread
+        assert g["per"] > g["step"] and g["trips"] >= 2                         # k_fsc_forward: more than one trip over the slice
+        assert {k: g[k] for k in want[n]} == want[n], (n, g)
+        assert g["upd_trips"] == 1
+    assert sum(1 for n in fs.GRID_WIDE if geo[n]["per"] % geo[n]["step"]) >= 2   # slices that are no multiple of the step
+    assert any(g["n_wg"] * g["per"] - rows[n]["Nv"] >= g["per"] and g["empty"] > 0 for n, g in geo.items())   # workgroups without a column
+    assert rows["Nv16500_K65"]["K"] > 64                                        # two factors per lane
+    assert [64 // geo[n]["kp"] for n in fs.GRID_WIDE] == [1, 1, 2, 4]           # columns per wave
+    mid = rows["Nv32800_K16_mid"]
+    assert mid["c0"] > 1 and mid["c0"] + mid["Nv"] - 1 < mid["N"]               # a view at neither end of the model
+    big = rows["LK_8200x128"]
+    assert big["L"] * big["K"] > sc["G_UPD_CAP"] * sc["UPD_BLOCK"] and geo["LK_8200x128"]["g_upd"] == sc["G_UPD_CAP"]
+    assert geo["LK_8200x128"]["upd_trips"] == 2                                 # k_fsc_update: the second grid-stride trip
+    # no row of the first table does any of this
+    for s in fs.SPARSE_ROWS.values():
+        g = fs.launch_geometry(s["L"], s["K"], s["Nv"])
+        assert g["trips"] == 1 and g["empty"] == 0 and g["n_wg"] <= sc["DECIDE_THREADS"] and g["upd_trips"] == 1
+    assert all("max_epochs" not in s for s in rows.values())                    # the default 6 epochs
+    assert fs.GRID_AGAINST_DENSE == fs.GRID_WIDE[:3] and all(rows[n]["L"] * rows[n]["K"] <= fr.CAPACITY for n in fs.GRID_AGAINST_DENSE)
+    assert set(fs.GRID_REPRO) == {"Nv8197_K33", "LK_8200x128"} and fs.GRID_EARLY_STOP[0] == "Nv8197_K33"
+
+
+@pytest.mark.parametrize("name", list(fs.GRID_ROWS))
+def test_grid_row_is_not_vacuous_and_float32_stays_within_the_recorded_discrepancy(name):
+    c, o = fs.grid_row(name)
+    S = c["S"]
+    assert not S[c["zero_row"]].any() and not S[:, c["zero_col"]].any()        # an empty set and an uncovered column
+    assert np.mean(o["A"] > 0) >= 0.10 and o["A"].max() > 0.05, (np.mean(o["A"] > 0), o["A"].max())
+    margin = fr.decision_margin(o["trace"], c["atol"])
+    r = fr.run_f32(c)
+    e = fr.errors(r, o, fr.fresh_ssq(c))
+    print(f"FSARD_GRID_CPU {name} " + " ".join(f"{k}={v:.3e}" for k, v in e.items())
+          + f" margin={margin:.3e} epochs={o['epochs']} branches={''.join(s['branch'] for s in o['trace'])}")
+    assert margin >= fr.MARGIN, margin
+    assert o["epochs"] == c["max_epochs"] == 6 and r["epochs"] == o["epochs"]
+    for k, v in e.items():
+        assert v <= fr.MEASURED[k], (k, v)
+
+
+def test_the_early_stop_at_width_ends_before_max_epochs_with_its_margin():
+    rule = fs.early_stop_rule()
+    assert fs.GRID_EARLY_STOP[1] in fr.STOP_RULES and rule == {k: fr.STOP_RULES[fs.GRID_EARLY_STOP[1]][k] for k in rule}
+    c, o = fs.early_stop_run()
+    margin = fr.decision_margin(o["trace"], rule["atol"])
+    r = fr.run_f32(c, **rule)
+    e = fr.errors(r, o, fr.fresh_ssq(c))
+    print(f"FSARD_GRID_CPU early stop {fs.GRID_EARLY_STOP} " + " ".join(f"{k}={v:.3e}" for k, v in e.items())
+          + f" margin={margin:.3e} epochs={o['epochs']} branches={''.join(s['branch'] for s in o['trace'])}")
+    assert margin >= fr.MARGIN, margin
+    assert 0 < o["epochs"] == r["epochs"] < rule["max_epochs"]                 # the counter ends the loop, not max_epochs
+    assert (o["epochs"] + 1) % max(8, rule["term_iter"]) != 0                   # ... inside a batch: launches are queued past the end
+    assert o["A"].max() > 0.05
+    for k, v in e.items():
+        assert v <= fr.MEASURED[k], (k, v)
