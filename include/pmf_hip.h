@@ -33,10 +33,12 @@ extern "C" {
 
 typedef struct pmf_ctx pmf_ctx;
 
-/* noise-model kinds (src/util.jl:128 VALID_LOSSES; MatFac NormalNoise / BernoulliNoise / PoissonNoise) */
+/* noise-model kinds (src/util.jl:128 VALID_LOSSES; MatFac NormalNoise / BernoulliNoise / PoissonNoise, and
+ * SquaredHingeNoise / OrdinalSqHingeNoise as two instances of one kind with three thresholds per column) */
 #define PMF_NOISE_NORMAL 0
 #define PMF_NOISE_BERNOULLI 1
 #define PMF_NOISE_POISSON 2
+#define PMF_NOISE_SQ_HINGE 3
 
 /* optimizers: AdaGrad = Flux.Optimise.AdaGrad as constructed at src/fit.jl:41-43 and applied through
  * src/optimizers.jl:6-13 ; Adam = Flux.Optimise.Adam (named by the north-star; no reference call site) */
@@ -136,6 +138,17 @@ int pmf_get_batch_view(pmf_ctx *ctx, int v, float *logdelta, float *theta);
  * MF.set_weight! (src/fit.jl:157, 180) */
 int pmf_set_noise(pmf_ctx *ctx, int n_ranges, const int64_t *starts1, const int64_t *stops1, const int32_t *kinds,
                   const float *weights);
+
+/* Thresholds t0 <= t1 <= t2 (each may be +-Inf) of the columns of kind PMF_NOISE_SQ_HINGE.  SELF-SPECIFIED model (DESIGN.md
+ * section 2): an observed entry y has class c = clamp((int)(y + 0.5), 0, 3) and the bin (lo, hi] = ((-Inf, t0, t1, t2)[c],
+ * (t0, t1, t2, +Inf)[c]); its loss is 0.5 w (relu(1 - (z - lo))^2 + relu(1 - (hi - z))^2), an infinite bound contributing
+ * nothing.  pmf_set_noise gives every kind-3 column (0, +Inf, +Inf): bernoulli_sq_hinge on 0/1 data.  ordinal_sq_hinge3
+ * on 1/2/3 data is (-Inf, t1, t2).  The thresholds are constants of the fit.
+ *   pmf_set_noise_thresholds : thr holds 3 floats per range; fails (and changes nothing) unless every column of every range is
+ *                              of kind 3 and t0 <= t1 <= t2.
+ *   pmf_get_noise_thresholds : 3 x N floats (column j at thr[3 j]), NaN for the columns of the other kinds. */
+int pmf_set_noise_thresholds(pmf_ctx *ctx, int n_ranges, const int64_t *starts1, const int64_t *stops1, const float *thr);
+int pmf_get_noise_thresholds(pmf_ctx *ctx, float *thr);
 
 /* matfac.X_reg.  A regularizer is a sum of terms p_t * reg_t (CompositeRegularizer, src/regularizers.jl:616-643).
  *   pmf_clear_xreg            : `X -> 0`                    (src/fit.jl:769, src/transform.jl:70)

@@ -13,7 +13,10 @@ import numpy as np
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libpmf_hip.so"
 
-NOISE = {"normal": 0, "bernoulli": 1, "poisson": 2}
+# bernoulli_sq_hinge and ordinal_sq_hinge3 are one kind (3) with different thresholds per column (set_noise_thresholds)
+NOISE = {"normal": 0, "bernoulli": 1, "poisson": 2, "bernoulli_sq_hinge": 3, "ordinal_sq_hinge3": 3}
+# the thresholds (t0, t1, t2) a kind-3 range gets by name.  ordinal_sq_hinge3's default is OURS (symmetric about 0, unit spacing)
+HINGE_THRESHOLDS = {"bernoulli_sq_hinge": (0.0, np.inf, np.inf), "ordinal_sq_hinge3": (-np.inf, -0.5, 0.5)}
 OPT = {"adagrad": 0, "adam": 1}
 STORE = {"f32": 0, "bf16": 1}
 TERM = {0: "max_epochs", 1: "loss_increase", 2: "abs_tol", 3: "rel_tol", 4: "nonfinite"}
@@ -119,6 +122,7 @@ EXPORTS = [
     "pmf_gram", "pmf_stage_lambda_max", "pmf_stage_whiten", "pmf_stage_rotate_by_svd", "pmf_stage_reorder_by_importance",
     "pmf_debug_postprocess_times",
     "pmf_fsard_update_A_csr",
+    "pmf_set_noise_thresholds", "pmf_get_noise_thresholds",
 ]
 
 COMM_ID_BYTES = 128
@@ -334,6 +338,23 @@ class Context:
         self._chk(self.lib.pmf_set_noise(self._h, len(k), _i64p(s), _i64p(e), k.ctypes.data_as(C.POINTER(C.c_int32)),
                                          _fp(w)))
         self.n_noise_ranges = len(k)
+        # a range named ordinal_sq_hinge3 gets that model's default thresholds (the library's default for kind 3 is bernoulli_sq_hinge's)
+        named = [(r, HINGE_THRESHOLDS[x]) for r, x in zip(ranges, kinds) if x == "ordinal_sq_hinge3"]
+        if named:
+            self.set_noise_thresholds([r for r, _ in named], [t for _, t in named])
+
+    def set_noise_thresholds(self, ranges, thresholds):
+        """pmf_set_noise_thresholds: (t0, t1, t2), t0 <= t1 <= t2 and each possibly +-inf, for every listed (1-based, inclusive)
+        column range; every column of a range must be of kind 3 (bernoulli_sq_hinge / ordinal_sq_hinge3)."""
+        s, e = _ranges(ranges)
+        t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(len(s), 3))
+        self._chk(self.lib.pmf_set_noise_thresholds(self._h, len(s), _i64p(s), _i64p(e), _fp(t)))
+
+    def get_noise_thresholds(self):
+        """pmf_get_noise_thresholds: (N, 3) thresholds, NaN for the columns of the other kinds."""
+        t = np.zeros((self.N, 3), np.float32)
+        self._chk(self.lib.pmf_get_noise_thresholds(self._h, _fp(t)))
+        return t
 
     # ---- regularizers
     def clear_xreg(self):

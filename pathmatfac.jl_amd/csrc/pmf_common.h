@@ -105,6 +105,10 @@ struct FusedArgs {
   // pmf_fused_sb8_kernel: power-of-two pre-scales of the f16 operand images of X and of sigma*Y (device scalars written by
   // k_sb8_scale right before the images; the forward accumulators are multiplied by 1 / (sx sy))
   const float *sb_scale_x, *sb_scale_y;
+  // per column the PMF_HT-float table of class bounds of the kind-3 (squared hinge) columns (pmf_hinge_terms), padded to a
+  // multiple of PMF_DPAD columns; read in that branch of pmf_noise only.  LAST: appended so that no other explicit kernarg
+  // offset moved.
+  const float *htab;
 };
 
 __device__ __forceinline__ int pmf_rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
@@ -126,8 +130,38 @@ __device__ __forceinline__ float2 pmf_batch_dt(const ViewDesc &vd, const float2 
 
 // loss and dloss/dz of one entry.  SELF-SPECIFIED noise models (MatFac is un-vendored):
 //   normal 0.5 w (z-y)^2 ; bernoulli w (softplus(z) - y z) ; poisson w (exp(z) - y z)
-__device__ __forceinline__ void pmf_noise(int kind, float z, float y, float w, float &l, float &g) {
-  if (kind == PMF_NOISE_NORMAL) {
+//   sq_hinge (kind 3, thresholds t = {t0, t1, t2} of the column, each possibly +-Inf): class c = clamp((int)(y + 0.5), 0, 3),
+//   bin (lo, hi] = ((-Inf, t0, t1, t2)[c], (t0, t1, t2, +Inf)[c]), a = relu(1 - (z - lo)), b = relu(1 - (hi - z)) with an
+//   infinite bound contributing 0 (a select of its own: 1 - (z - (+Inf)) is +Inf); 0.5 w (a^2 + b^2), g = w (b - a).
+//   bernoulli_sq_hinge = (0, +Inf, +Inf) on 0/1 data, ordinal_sq_hinge3 = (-Inf, t1, t2) on 1/2/3 data.
+// The model reads the bounds of a class from a per-column TABLE of PMF_HT floats the host builds from the thresholds
+// (hinge_table, pmf_hip.hip): T[c] = lo of class c, T[4 + c] = hi of class c, where the infinite bounds that must contribute
+// nothing are stored with the sign that makes them do so (lo = -Inf: 1 - (z + Inf) = -Inf, relu 0; hi = +Inf likewise) --
+// the select on +-Inf is made once per column on the host, not per entry.  The table array is padded, like D, to a multiple
+// of PMF_DPAD columns (the pad holds bernoulli_sq_hinge's table): the pad columns of a tile read in range without a clamp, and
+// a lane's 16 columns are one base address plus immediate offsets.
+#define PMF_HT 8
+// the two margin violations of an entry (a: below the bin's lower bound + 1, b: above its upper bound - 1)
+__device__ __forceinline__ void pmf_hinge_terms(float z, float y, const float *T, float &a, float &b) {
+  const int c = (int)fminf(fmaxf(y + 0.5f, 0.f), 3.f);   // (NaN -> 0: a missing entry is masked by the caller)
+  const float lo = T[c], hi = T[4 + c];
+  a = fmaxf(0.f, 1.f - (z - lo));
+  b = fmaxf(0.f, 1.f - (hi - z));
+}
+// inverse link of kind 3: the number of thresholds strictly below z (0/1 for bernoulli_sq_hinge, 1..3 for ordinal_sq_hinge3)
+__device__ __forceinline__ float pmf_hinge_class(float z, const float4 t) { return (float)((t.x < z) + (t.y < z) + (t.z < z)); }
+
+// tp: the column's table of bounds (PMF_HT floats), read in the kind-3 branch only.  HINGE = false: a fused kernel compiled
+// without MIXED only ever sees normal columns and the dead columns of a ragged tile (code 3, weight 0, masked by the caller);
+// it keeps those on the last branch, which they always took, and carries no squared-hinge code.
+template <bool HINGE = true>
+__device__ __forceinline__ void pmf_noise(int kind, float z, float y, float w, const float *tp, float &l, float &g) {
+  if (HINGE && kind == PMF_NOISE_SQ_HINGE) {
+    float a, b;
+    pmf_hinge_terms(z, y, tp, a, b);
+    l = 0.5f * w * fmaf(a, a, b * b);
+    g = w * (b - a);
+  } else if (kind == PMF_NOISE_NORMAL) {
     const float d = z - y;
     g = w * d;
     l = 0.5f * g * d;
@@ -404,6 +438,7 @@ struct LayerPassArgs {
   double *loss_partial;    // one per workgroup; null = the loss is computed elsewhere (combined epochs)
   int64_t M, N;
   int32_t n_bv, n_ct, n_rp, n_seg, R;
+  const float *htab;       // per column table of class bounds of the kind-3 columns (pmf_hinge_terms)
 };
 
 struct LayerMapArgs {
@@ -438,6 +473,7 @@ struct ImputeArgs {
   int64_t row0, row1;      // 0-based, [row0, row1)
   int64_t rp0, n_rp;       // the 32 NW-row panels (absolute numbering) that meet the row range
   int32_t n_bv, n_ct, n_seg, R, flags;
+  const float4 *thr;       // per column thresholds of the kind-3 columns
 };
 
 struct ImputeEntriesArgs {
@@ -450,6 +486,7 @@ struct ImputeEntriesArgs {
   float *out;
   int64_t n, M;
   int32_t Kp, K, flags;
+  const float4 *thr;
 };
 
 // ---- launchers exported by the kernel files

@@ -209,6 +209,10 @@ struct pmf_ctx {
   DevBuf<int32_t> colmeta;     // kind | (view+1)<<2
   DevBuf<float> colw;
   DevBuf<float4> colp;
+  DevBuf<float4> thr;          // per column {t0, t1, t2, 0}, N padded to a multiple of PMF_DPAD: thresholds of the kind-3 columns ((0, +Inf, +Inf)
+                               // elsewhere).  thr and htab exist while the noise model has a column that is not normal (upload_thresholds)
+  DevBuf<float> htab;          // per column the PMF_HT-float table of class bounds built from thr (pmf_hinge_terms), same padding
+  std::vector<float> h_thr;    // host copy, 3 per column (pmf_get_noise_thresholds; NaN for the other kinds)
   bool mixed = false;
   bool prepared = false;
   // ARD-type regularizer on Y

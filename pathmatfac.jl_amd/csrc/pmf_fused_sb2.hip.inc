@@ -327,8 +327,8 @@ __global__ __launch_bounds__(256, 1) void pmf_fused_sb2_kernel(const FusedArgs a
             z = fmaf(z, dl, Cmu[ci] + dt.y);
           }
           float l, g;
-          if (kmode == 3) pmf_noise(Cmt[ci] & 3, z, y, wj, l, g);
-          else pmf_noise(kmode, z, y, wj, l, g);
+          if (kmode == 3) pmf_noise<MIXED>(Cmt[ci] & 3, z, y, wj, a.htab + (j0 + 4 * h) * PMF_HT + PMF_HT * ((r & 3) + 8 * (r >> 2)), l, g);
+          else pmf_noise(kmode, z, y, wj, nullptr, l, g);
           lsum += ok ? l : 0.f;
           acc[rb][r] = ok ? (BATCH ? g * dl : g) : 0.f;
         };

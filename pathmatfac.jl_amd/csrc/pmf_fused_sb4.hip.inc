@@ -367,8 +367,8 @@ __global__ __launch_bounds__(256, 1) void pmf_fused_sb4_kernel(const FusedArgs a
         } else {
           const bool ok = pmf_finite(y) && row_ok;
           float l, g;
-          if (kmode == 3) pmf_noise(Cmt[cb0 + (r & 3) + 8 * (r >> 2)] & 3, z, y, wj, l, g);
-          else pmf_noise(kmode, z, y, wj, l, g);
+          if (kmode == 3) pmf_noise<MIXED>(Cmt[cb0 + (r & 3) + 8 * (r >> 2)] & 3, z, y, wj, a.htab + (j0 + 4 * h) * PMF_HT + PMF_HT * ((r & 3) + 8 * (r >> 2)), l, g);
+          else pmf_noise(kmode, z, y, wj, nullptr, l, g);
           lsum += ok ? l : 0.f;
           acc[r] = ok ? (BATCH ? g * dl : g) : 0.f;
         }

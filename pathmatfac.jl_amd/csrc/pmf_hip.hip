@@ -259,6 +259,7 @@ struct ColWalkArgs {
   int d_bf16;
   const float *X, *Y;
   const float4 *colp;
+  const float *htab;    // per column table of class bounds of the kind-3 columns (pmf_hinge_terms)
   const int32_t *bor;
   const float2 *btab;
   int64_t M, N, nRB;
@@ -278,7 +279,8 @@ struct ColWalk {
   int tid;
   int64_t j, jc, r0, r1;   // column, column clamped to the matrix, row range of this block row
   bool col_ok;
-  float4 cp;
+  float4 cp;        // column parameters of column jc
+  const float *ht;  // its table of class bounds (kind 3)
   int kind, v;
   ViewDesc vd;
   float4 yr[Kp / 4];
@@ -294,6 +296,7 @@ struct ColWalk {
     r1 = r0 + a.rows_per_block;
     if (r1 > a.M) r1 = a.M;
     cp = a.colp[jc];
+    ht = a.htab + jc * PMF_HT;
     const int meta = __float_as_int(cp.w);
     kind = pmf_meta_kind(meta);
     v = pmf_meta_view(meta);
@@ -371,7 +374,7 @@ __global__ __launch_bounds__(64) void k_layer_grad(const LayerGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_lg[];
   __shared__ double sh[4];
   ColWalk<KB> w(a, smem_lg);
-  const int kind = w.col_ok ? w.kind : 3;   // (pad columns: the Poisson branch, zeroed below)
+  const int kind = w.kind;   // (pad columns walk the last column again; zeroed below)
   const float4 cp = w.cp;
   float smu = 0.f, sls = 0.f;
   double lacc = 0.0;
@@ -388,8 +391,8 @@ __global__ __launch_bounds__(64) void k_layer_grad(const LayerGradArgs a) {
       const float z1 = acc * cp.x;
       const float z = fmaf(z1, dt.x, cp.y + dt.y);
       float l, g;
-      pmf_noise(kind, z, yv, cp.z, l, g);
-      const bool ok = (kind != 3) && pmf_finite(yv);
+      pmf_noise(kind, z, yv, cp.z, w.ht, l, g);
+      const bool ok = w.col_ok && pmf_finite(yv);
       if (!ok) { l = 0.f; g = 0.f; }
       lacc += (double)l;
       smu += g;
@@ -444,11 +447,16 @@ __global__ __launch_bounds__(64) void k_stats(const StatsArgs a) {
       const float yv = w.data(i);
       if (!pmf_finite(yv)) continue;
       const float z = fmaf(acc * cp.x, dt.x, cp.y + dt.y);
-      float pred, g;
-      if (w.kind == PMF_NOISE_NORMAL) { pred = z; g = cp.z * (z - yv); }
-      else if (w.kind == PMF_NOISE_BERNOULLI) { pred = 1.f / (1.f + __expf(-z)); g = cp.z * (pred - yv); }
-      else { pred = __expf(z); g = cp.z * (pred - yv); }
-      const float r = pred - yv;
+      float r;   // residual: prediction - y; squared hinge: the signed margin violation b - a (= g / w, as z - y is for a normal column)
+      if (w.kind == PMF_NOISE_NORMAL) r = z - yv;
+      else if (w.kind == PMF_NOISE_BERNOULLI) r = 1.f / (1.f + __expf(-z)) - yv;
+      else if (w.kind == PMF_NOISE_POISSON) r = __expf(z) - yv;
+      else {
+        float ha, hb;
+        pmf_hinge_terms(z, yv, w.ht, ha, hb);
+        r = hb - ha;
+      }
+      const float g = cp.z * r;
       sn += 1.f; s1 += yv; s2 += yv * yv; se += r * r; sg += g * g;
       if (b >= 0) {
         w.sum(0, b) += 1.f;
@@ -477,6 +485,7 @@ __global__ __launch_bounds__(64) void k_stats(const StatsArgs a) {
 struct ForwardArgs {
   const float *X, *Y;
   const float4 *colp;
+  const float4 *thr;
   const int32_t *bor;
   const float2 *btab;
   float *Z;
@@ -521,6 +530,7 @@ __global__ __launch_bounds__(256) void k_forward(const ForwardArgs a) {
     const int kind = pmf_meta_kind(meta);
     if (kind == PMF_NOISE_NORMAL) z += a.noise * nrm;
     else if (kind == PMF_NOISE_BERNOULLI) z = (z + a.noise * nrm) > 0.f ? 1.f : 0.f;
+    else if (kind == PMF_NOISE_SQ_HINGE) z = pmf_hinge_class(z + a.noise * nrm, a.thr[j]);   // the class of the noisy prediction
     else z = floorf(__expf(fminf(z, 10.f)));
     const float u3 = (r2 >> 40) * (1.0f / 16777216.0f);
     if (u3 < a.frac_nan) z = __int_as_float(0x7fc00000);
@@ -722,6 +732,9 @@ static int data_shape_changed(pmf_ctx *c, int64_t M, int64_t N) {
   PMFCHK(c->colmeta.alloc((size_t)N, true));
   PMFCHK(c->colw.alloc((size_t)N, true));
   PMFCHK(c->colp.alloc((size_t)N, true));
+  c->thr.free();     // (allocated by the first noise model that is not all-normal: upload_thresholds)
+  c->htab.free();
+  c->h_thr.clear();
   k_fill<<<nblocks(N, 256), 256, 0, c->stream>>>(c->colw, N, 1.f);
   HIPCHK(hipGetLastError());
   c->mixed = false;
@@ -947,29 +960,97 @@ extern "C" int pmf_get_batch_view(pmf_ctx *c, int v, float *logdelta, float *the
 }
 
 // ---- noise model -------------------------------------------------------------------------------
+// The table pmf_hinge_terms reads, from the thresholds t0 <= t1 <= t2 of one column: T[c] = lower bound of class c =
+// (-Inf, t0, t1, t2)[c], T[4 + c] = its upper bound = (t0, t1, t2, +Inf)[c].  An infinite bound of either sign contributes
+// nothing: a lower bound of +Inf (a class the column never holds) is stored as -Inf, an upper bound of -Inf as +Inf, so that
+// relu(1 - (z - lo)) and relu(1 - (hi - z)) are 0 there without a select per entry.
+static void hinge_table(const float t[3], float *T) {
+  T[0] = -INFINITY;
+  T[7] = INFINITY;
+  for (int k = 0; k < 3; ++k) {
+    T[1 + k] = std::isinf(t[k]) ? -INFINITY : t[k];
+    T[4 + k] = std::isinf(t[k]) ? INFINITY : t[k];
+  }
+}
+// device images of h_thr: {t0, t1, t2, 0} and the table per column; the columns of the other kinds and the pad columns hold
+// bernoulli_sq_hinge's (0, +Inf, +Inf).  Only a model with a column that is not normal has them: nothing else reads them
+// (the MIXED kernels do, for the dead columns of a ragged tile too), and an all-normal fit allocates what it always did.
+static int upload_thresholds(pmf_ctx *c) {
+  if (!c->mixed) return 0;
+  const size_t np = (size_t)((c->N + PMF_DPAD - 1) / PMF_DPAD * PMF_DPAD);
+  PMFCHK(c->thr.ensure(np, false, "the noise thresholds"));
+  PMFCHK(c->htab.ensure(np * PMF_HT, false, "the noise threshold tables"));
+  std::vector<float4> t(np, make_float4(0.f, INFINITY, INFINITY, 0.f));
+  std::vector<float> T(np * PMF_HT);
+  for (size_t j = 0; j < np; ++j) {
+    if ((int64_t)j < c->N && !std::isnan(c->h_thr[j * 3])) t[j] = make_float4(c->h_thr[j * 3], c->h_thr[j * 3 + 1], c->h_thr[j * 3 + 2], 0.f);
+    const float tj[3] = {t[j].x, t[j].y, t[j].z};
+    hinge_table(tj, &T[j * PMF_HT]);
+  }
+  PMFCHK(c->thr.upload(t.data(), np));
+  return c->htab.upload(T.data(), T.size());
+}
+
 extern "C" int pmf_set_noise(pmf_ctx *c, int n_ranges, const int64_t *s1, const int64_t *e1, const int32_t *kinds,
                              const float *weights) {
   PMFCHK(ctx_bind(c));
   if (c->N == 0) return pmf_fail("data not set");
-  std::vector<int32_t> meta((size_t)c->N, 3);
+  std::vector<int32_t> meta((size_t)c->N, 0);
+  std::vector<uint8_t> covered((size_t)c->N, 0);
   bool mixed = false;
   for (int r = 0; r < n_ranges; ++r) {
     if (s1[r] < 1 || e1[r] > c->N || s1[r] > e1[r]) return pmf_fail("noise range %d: bad columns %lld:%lld", r, (long long)s1[r], (long long)e1[r]);
-    if (kinds[r] < 0 || kinds[r] > 2) return pmf_fail("noise range %d: unsupported kind %d (normal=0, bernoulli=1, poisson=2)", r, kinds[r]);
+    if (kinds[r] < 0 || kinds[r] > 3) return pmf_fail("noise range %d: unsupported kind %d (normal=0, bernoulli=1, poisson=2, sq_hinge=3)", r, kinds[r]);
     if (kinds[r] != PMF_NOISE_NORMAL) mixed = true;
-    for (int64_t j = s1[r] - 1; j < e1[r]; ++j) meta[(size_t)j] = kinds[r];
+    for (int64_t j = s1[r] - 1; j < e1[r]; ++j) { meta[(size_t)j] = kinds[r]; covered[(size_t)j] = 1; }
   }
   for (int64_t j = 0; j < c->N; ++j)
-    if (meta[(size_t)j] == 3) return pmf_fail("noise model does not cover column %lld", (long long)(j + 1));
+    if (!covered[(size_t)j]) return pmf_fail("noise model does not cover column %lld", (long long)(j + 1));
+  // thresholds: (0, +Inf, +Inf) -- bernoulli_sq_hinge -- for the kind-3 columns (pmf_set_noise_thresholds changes them);
+  // the other kinds never read theirs (the same finite-or-Inf values on the device, NaN in what the getter reports)
+  std::vector<float> h_thr((size_t)c->N * 3);
+  for (int64_t j = 0; j < c->N; ++j) {
+    const bool hg = meta[(size_t)j] == PMF_NOISE_SQ_HINGE;
+    h_thr[(size_t)j * 3 + 0] = hg ? 0.f : NAN;
+    h_thr[(size_t)j * 3 + 1] = h_thr[(size_t)j * 3 + 2] = hg ? INFINITY : NAN;
+  }
   HIPCHK(hipStreamSynchronize(c->stream));
   HIPCHK(hipMemcpy(c->colmeta, meta.data(), sizeof(int32_t) * (size_t)c->N, hipMemcpyHostToDevice));
+  c->h_thr.swap(h_thr);
   if (weights) HIPCHK(hipMemcpy(c->colw, weights, sizeof(float) * (size_t)c->N, hipMemcpyHostToDevice));
   c->mixed = mixed;
+  PMFCHK(upload_thresholds(c));
   c->noise_s1.assign(s1, s1 + n_ranges);
   c->noise_e1.assign(e1, e1 + n_ranges);
   c->h_kind.assign(meta.begin(), meta.end());
   c->kind_version++;
   PMFCHK(rebuild_colmeta_views(c));
+  return 0;
+}
+
+extern "C" int pmf_set_noise_thresholds(pmf_ctx *c, int n_ranges, const int64_t *s1, const int64_t *e1, const float *thr) {
+  PMFCHK(ctx_bind(c));
+  if (c->N == 0 || (int64_t)c->h_kind.size() != c->N || (int64_t)c->h_thr.size() != 3 * c->N)
+    return pmf_fail("the noise model must be set before its thresholds");
+  for (int r = 0; r < n_ranges; ++r) {
+    if (s1[r] < 1 || e1[r] > c->N || s1[r] > e1[r]) return pmf_fail("threshold range %d: bad columns %lld:%lld", r, (long long)s1[r], (long long)e1[r]);
+    const float *t = thr + 3 * r;
+    if (!(t[0] <= t[1] && t[1] <= t[2])) return pmf_fail("threshold range %d: need t0 <= t1 <= t2, got (%g, %g, %g)", r, t[0], t[1], t[2]);
+    for (int64_t j = s1[r] - 1; j < e1[r]; ++j)
+      if (c->h_kind[(size_t)j] != PMF_NOISE_SQ_HINGE)
+        return pmf_fail("threshold range %d: column %lld is of noise kind %d, not sq_hinge (3)", r, (long long)(j + 1), (int)c->h_kind[(size_t)j]);
+  }
+  for (int r = 0; r < n_ranges; ++r)
+    for (int64_t j = s1[r] - 1; j < e1[r]; ++j)
+      for (int q = 0; q < 3; ++q) c->h_thr[(size_t)j * 3 + q] = thr[3 * r + q];
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return upload_thresholds(c);
+}
+
+extern "C" int pmf_get_noise_thresholds(pmf_ctx *c, float *thr) {
+  PMFCHK(ctx_bind(c));
+  if (c->N == 0 || (int64_t)c->h_thr.size() != 3 * c->N) return pmf_fail("the noise model is not set");
+  memcpy(thr, c->h_thr.data(), sizeof(float) * c->h_thr.size());
   return 0;
 }
 
@@ -1307,24 +1388,30 @@ __global__ __launch_bounds__(256) void k_gx_reduce(const float *__restrict__ par
 // (22, right for the exact kernel at K = 64) cost the split kernels 7-22 % and the exact kernel at K <= 32 12 %.
 // With batch layers EVERY tile pays the table look-ups (w_batch, from the batch-only against the plain launch at the same size),
 // which lowers the Bernoulli tiles' relative weight.
-static void noise_tile_weights(int KB, bool split, bool batch, int64_t &w_gauss, int64_t &w_bern, int64_t &w_pois) {
+// A squared-hinge tile always runs the per-column path (its thresholds are per column).  Its weight is UNMEASURED: it starts
+// from the Poisson tile's (PMF_W_HINGE overrides it).
+static void noise_tile_weights(int KB, bool split, bool batch, int64_t &w_gauss, int64_t &w_bern, int64_t &w_pois, int64_t &w_hinge) {
   static const int64_t wb_exact[4] = {26, 22, 20, 20}, wb_split[4] = {31, 30, 24, 24};
   static const int64_t we_exact[4] = {6, 6, 5, 4}, we_split[4] = {12, 8, 6, 6};   // (swept on the all-features launch: PMF_W_BATCH)
   w_bern = (split ? wb_split : wb_exact)[KB - 1];
   if (getenv("PMF_W_BERN")) w_bern = std::max(16, atoi(getenv("PMF_W_BERN")));
   w_pois = 16 + ((w_bern - 16) * 5 + 3) / 6;       // (exp only against exp + log + rcp: the exact kernel's 21 against 22)
   if (getenv("PMF_W_POIS")) w_pois = std::max(16, atoi(getenv("PMF_W_POIS")));
+  w_hinge = w_pois;                                // (unmeasured)
+  if (getenv("PMF_W_HINGE")) w_hinge = std::max(16, atoi(getenv("PMF_W_HINGE")));
   int64_t w_batch = batch ? (split ? we_split : we_exact)[KB - 1] : 0;
   if (batch && getenv("PMF_W_BATCH")) w_batch = std::max(0, atoi(getenv("PMF_W_BATCH")));
   w_gauss = 16 + w_batch;
   w_bern += w_batch;
   w_pois += w_batch;
+  w_hinge += w_batch;
 }
 
 static int compute_work_split(pmf_ctx *c, WorkSplit &ws, int grid, int64_t n_rp, int64_t ct0, int64_t n_ct, int64_t tps, int64_t n_cseg, bool split) {
-  int64_t w_gauss, w_bern, w_pois;
-  noise_tile_weights(c->KB, split, c->n_bv > 0, w_gauss, w_bern, w_pois);
-  const int64_t key[11] = {c->M, c->N, c->Kp, grid, n_rp, tps, n_cseg, c->kind_version, ct0, n_ct, c->mixed ? (w_gauss * 64 + w_bern) * 64 + w_pois : 0};
+  int64_t w_gauss, w_bern, w_pois, w_hinge;
+  noise_tile_weights(c->KB, split, c->n_bv > 0, w_gauss, w_bern, w_pois, w_hinge);
+  const int64_t key[11] = {c->M, c->N, c->Kp, grid, n_rp, tps, n_cseg, c->kind_version, ct0, n_ct,
+                           c->mixed ? ((w_gauss * 64 + w_bern) * 64 + w_pois) * 64 + w_hinge : 0};
   if (ws.wg_begin && memcmp(key, ws.key, sizeof(key)) == 0) return 0;
   std::vector<int64_t> tw((size_t)n_ct, w_gauss);
   if (c->mixed && (int64_t)c->h_kind.size() == c->N) {
@@ -1332,7 +1419,7 @@ static int compute_work_split(pmf_ctx *c, WorkSplit &ws, int grid, int64_t n_rp,
       int64_t wmax = w_gauss;
       for (int64_t j = (ct0 + ct) * 32; j < std::min<int64_t>(c->N, (ct0 + ct) * 32 + 32); ++j) {
         const int k = c->h_kind[(size_t)j];
-        wmax = std::max<int64_t>(wmax, k == PMF_NOISE_BERNOULLI ? w_bern : (k == PMF_NOISE_POISSON ? w_pois : w_gauss));
+        wmax = std::max<int64_t>(wmax, k == PMF_NOISE_BERNOULLI ? w_bern : (k == PMF_NOISE_POISSON ? w_pois : (k == PMF_NOISE_SQ_HINGE ? w_hinge : w_gauss)));
       }
       tw[(size_t)ct] = wmax;
     }
@@ -1803,7 +1890,7 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   a.tflags = c->tflags;
   a.wg_begin = ws.wg_begin;
   a.D = c->D; a.X = c->P[0].p; a.Y = c->P[1].p; a.gX = c->P[0].g; a.gY = c->P[1].g;
-  a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.loss_partial = c->loss_partial + loss_off;
+  a.colp = c->colp; a.htab = c->htab; a.bor = c->bor; a.btab = c->btab; a.loss_partial = c->loss_partial + loss_off;
   a.btd = g.bmode == 1 ? c->btd : nullptr; a.n_bv = c->n_bv;
   if (g.bmode == 1) {
     a.pm = g.ps->pm; a.row_slot = g.ps->row_slot; a.colview = c->colview;
@@ -1883,7 +1970,7 @@ static int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy) {
 // ---- host side of the column walk (k_layer_grad / k_stats)
 // The shared arguments and the grid: gx blocks of 64 columns x gy block rows of a.rows_per_block rows.
 static void col_walk_fill(pmf_ctx *c, ColWalkArgs &a, int &gx, int64_t &gy) {
-  a.D = c->D; a.d_bf16 = c->store == PMF_STORE_BF16; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab;
+  a.D = c->D; a.d_bf16 = c->store == PMF_STORE_BF16; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.htab = c->htab; a.bor = c->bor; a.btab = c->btab;
   a.M = c->M; a.N = c->N; a.nRB = c->nRB; a.Kp = c->Kp; a.K = c->K;
   fill_views(c, a.views, a.val_off);
   a.max_nb = 1;
@@ -1985,7 +2072,7 @@ static int launch_layer_pass(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss) 
   if (with_loss) PMFCHK(ensure_loss_partials(c, grid));
   LayerPassArgs a;
   memset(&a, 0, sizeof(a));
-  a.D = c->D; a.d_bf16 = c->store == PMF_STORE_BF16; a.nRB = c->nRB; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor;
+  a.D = c->D; a.d_bf16 = c->store == PMF_STORE_BF16; a.nRB = c->nRB; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.htab = c->htab; a.bor = c->bor;
   a.btd = c->n_bv > 0 ? c->btd : nullptr; a.LG = c->LG; a.lg_stride = lg_stride; a.loss_partial = with_loss ? c->loss_partial : nullptr;
   a.M = c->M; a.N = c->N; a.n_bv = c->n_bv; a.n_ct = (int)n_ct; a.n_rp = (int)n_rp; a.n_seg = (int)n_seg; a.R = (int)R;
   a.nbs_shift = nbs_shift;
@@ -2261,7 +2348,7 @@ static int run_forward(pmf_ctx *c, float *Zdev, int synth, uint64_t seed, float 
   PMFCHK(prepare(c));
   ForwardArgs a;
   memset(&a, 0, sizeof(a));
-  a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.Z = Zdev;
+  a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.thr = c->thr; a.bor = c->bor; a.btab = c->btab; a.Z = Zdev;
   a.z_bf16 = nRB > 0 && c->store == PMF_STORE_BF16;
   a.M = c->M; a.N = c->N; a.nRB = nRB; a.Kp = c->Kp; a.K = c->K; a.synth = synth; a.seed = seed; a.noise = noise; a.frac_nan = frac_nan;
   fill_views(c, a.views);
@@ -2317,7 +2404,7 @@ static int impute_launch(pmf_ctx *c, int flags, int64_t row0, int64_t row1, floa
   const int64_t BM = 32 * nw;
   ImputeArgs a;
   memset(&a, 0, sizeof(a));
-  a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
+  a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.thr = c->thr; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
   a.D = c->D; a.nRB = c->nRB; a.out = out_dev; a.ld = ld; a.M = c->M; a.N = c->N; a.row0 = row0; a.row1 = row1;
   a.rp0 = row0 / BM;
   a.n_rp = (row1 - 1) / BM + 1 - a.rp0;
@@ -2389,7 +2476,7 @@ extern "C" int pmf_impute_entries(pmf_ctx *c, int flags, int64_t n, const int64_
     HIPCHK(hipMemcpyAsync(d_cols, cols1 + e0, sizeof(int64_t) * (size_t)ne, hipMemcpyHostToDevice, c->stream));
     ImputeEntriesArgs a;
     memset(&a, 0, sizeof(a));
-    a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
+    a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.thr = c->thr; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
     a.rows1 = d_rows; a.cols1 = d_cols; a.out = d_out; a.n = ne; a.M = c->M; a.Kp = c->Kp; a.K = c->K; a.flags = flags;
     PMFCHK(pmf_launch_impute_entries(c->stream, a));
     HIPCHK(hipMemcpyAsync(out_host + e0, d_out, sizeof(float) * (size_t)ne, hipMemcpyDeviceToHost, c->stream));

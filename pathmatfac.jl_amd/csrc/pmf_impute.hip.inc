@@ -4,7 +4,9 @@
 // every column's noise model (:3-13, 27-35).  Per entry, with z1 = sigma_j a_ij:
 //   z = z1 + mu_j                                  (default)
 //   z = z1 delta_bj + mu_j + theta_bj              (PMF_IMPUTE_BATCH; delta = 1, theta = 0 for a row in no batch)
-//   normal -> z ; bernoulli -> 1 / (1 + e^-z) ; poisson -> e^z      (PMF_IMPUTE_LINK: z for every column)
+//   normal -> z ; bernoulli -> 1 / (1 + e^-z) ; poisson -> e^z ; sq_hinge -> the number of the column's thresholds strictly
+//   below z (the bin rule of impute.jl:15-25: 0/1 for bernoulli_sq_hinge, 1..3 for ordinal_sq_hinge3)
+//                                                                  (PMF_IMPUTE_LINK: z for every column)
 // and, with PMF_IMPUTE_KEEP_OBSERVED, the stored entry of D wherever it is finite.
 //
 // Structure (gfx950): that of pmf_layer_kernel.  A workgroup owns PMF_LS = 2 column tiles and a range of 32 NW-row panels;
@@ -19,7 +21,8 @@
 
 // the two rules the MFMA kernel and the per-entry kernel share
 __device__ __forceinline__ float pmf_impute_batch(float z1, float mu, float2 dt) { return fmaf(z1, dt.x, mu + dt.y); }
-__device__ __forceinline__ float pmf_impute_invlink(int kind, float z) {
+__device__ __forceinline__ float pmf_impute_invlink(int kind, float z, const float4 *tp) {   // tp: read for kind 3 only
+  if (kind == PMF_NOISE_SQ_HINGE) return pmf_hinge_class(z, *tp);
   if (kind == PMF_NOISE_BERNOULLI) {
     // 1 / (1 + e^-z) without an infinite intermediate: e = e^-|z| <= 1
     const float e = __expf(-fabsf(z));
@@ -92,6 +95,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(co
     }
     __syncthreads();
     // one noise kind in the whole tile (the usual case: columns are sorted by distribution): a wave-uniform branch
+    // (a tile of kind-3 columns takes the per-column path, tk = 3: its thresholds are per column)
     int tk[LS];
 #pragma unroll
     for (int t = 0; t < LS; ++t) {
@@ -181,10 +185,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(co
         }
         if (tk[t] == PMF_NOISE_BERNOULLI) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = pmf_impute_invlink(PMF_NOISE_BERNOULLI, acc[r]);
+          for (int r = 0; r < 16; ++r) acc[r] = pmf_impute_invlink(PMF_NOISE_BERNOULLI, acc[r], nullptr);
         } else if (tk[t] == PMF_NOISE_POISSON) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = pmf_impute_invlink(PMF_NOISE_POISSON, acc[r]);
+          for (int r = 0; r < 16; ++r) acc[r] = pmf_impute_invlink(PMF_NOISE_POISSON, acc[r], nullptr);
         } else if (tk[t] == 3) {
 #pragma unroll
           for (int c4 = 0; c4 < 4; ++c4) {
@@ -192,7 +196,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(co
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
               const int meta = u == 0 ? mt4.x : (u == 1 ? mt4.y : (u == 2 ? mt4.z : mt4.w));
-              acc[4 * c4 + u] = pmf_impute_invlink(pmf_meta_kind(meta), acc[4 * c4 + u]);
+              acc[4 * c4 + u] = pmf_impute_invlink(pmf_meta_kind(meta), acc[4 * c4 + u], a.thr + (int64_t)(ct0 + t) * BN + 4 * h + (8 * c4 + u));
             }
           }
         }
@@ -235,5 +239,5 @@ __global__ __launch_bounds__(256) void k_impute_entries(const ImputeEntriesArgs 
   } else {
     z += cp.y;
   }
-  a.out[e] = pmf_impute_invlink((a.flags & PMF_IMPUTE_LINK) != 0 ? PMF_NOISE_NORMAL : pmf_meta_kind(meta), z);
+  a.out[e] = pmf_impute_invlink((a.flags & PMF_IMPUTE_LINK) != 0 ? PMF_NOISE_NORMAL : pmf_meta_kind(meta), z, a.thr + j);
 }

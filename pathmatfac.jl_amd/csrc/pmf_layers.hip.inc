@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_layer_kernel(con
     }
     for (int c = tid; c < nt * 32; c += NT) {
       const int64_t j = (int64_t)ct0 * BN + c;
-      const float4 cp = j < N ? a.colp[j] : make_float4(0.f, 0.f, 0.f, __int_as_float(3));
+      const float4 cp = j < N ? a.colp[j] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));   // pad column: meta < 0 (no view, masked below)
       Cmu[c] = cp.y; Cw[c] = cp.z; Cmt[c] = __float_as_int(cp.w);
     }
     for (int e = tid; e < ((nt * 32) << bsh); e += NT)
@@ -173,9 +173,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_layer_kernel(con
             const float z = fmaf(z1, dt.x, muj + dt.y);
             const float y = dcur.get(r);
             float l, g;
-            if (MIXED) pmf_noise(meta & 3, z, y, wj, l, g);
-            else pmf_noise(PMF_NOISE_NORMAL, z, y, wj, l, g);
-            const bool ok = pmf_finite(y) && row_ok && (meta & 3) != 3;
+            if (MIXED) pmf_noise(meta & 3, z, y, wj, a.htab + ((int64_t)(ct0 + t) * BN + 4 * h) * PMF_HT + PMF_HT * (8 * c4 + u), l, g);
+            else pmf_noise(PMF_NOISE_NORMAL, z, y, wj, nullptr, l, g);
+            const bool ok = pmf_finite(y) && row_ok && meta >= 0;   // (meta < 0: a pad column)
             lsum += ok ? l : 0.f;
             g = ok ? g : 0.f;
             acc[r] = g;

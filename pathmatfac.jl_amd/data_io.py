@@ -170,9 +170,10 @@ def var_filter(data, feature_groups, frac):
 def model_from_data_file(omic_file, omic_types, K=10, use_batch=True, use_conditions=True, var_filter_frac=1.0,
                          distribution_map=None, **model_kwargs):
     """The data side of fit_matfac.jl's main (:193-246, 285): load, variance filter, sort the samples by condition, attach
-    batches, then PathMatFacModel(D; ...) = make_model.  `distribution_map` overrides script_util.jl's DISTRIBUTION_MAP (the
-    library implements "normal", "bernoulli", "poisson": the hinge / ordinal losses of the production map are out of
-    scope, DESIGN.md section 8, so a caller that holds mutation / cna columns must say which supported loss to use)."""
+    batches, then PathMatFacModel(D; ...) = make_model.  `distribution_map` overrides script_util.jl's DISTRIBUTION_MAP.  The
+    library implements every loss of that map: "normal", "bernoulli_sq_hinge" (mutation: 0/1 data) and "ordinal_sq_hinge3"
+    (cna: classes 1/2/3, thresholds settable through CompositeNoise.set_thresholds_), besides "bernoulli" and "poisson";
+    only "ordinal3" is out of scope."""
     D, sample_ids, sample_conditions, genes, assays = load_omic_data(omic_file, omic_types)
     keep = var_filter(D, assays, var_filter_frac)                                           # :208-209
     D, genes, assays = D[:, keep], genes[keep], assays[keep]

@@ -34,7 +34,9 @@ const FSARD_DATA = IdDict{Any,Matrix{Float32}}()   # FeatureSetARDReg => the all
 const FSARD_DENSE_CAPACITY = 16384            # L * K that pmf_fsard_update_A accepts (A in one workgroup's LDS)
 
 const TERM_CODES = ("max_epochs", "loss_increase", "abs_tol", "rel_tol", "nonfinite")
-const NOISE_KIND = Dict("normal" => Cint(0), "bernoulli" => Cint(1), "poisson" => Cint(2))
+# bernoulli_sq_hinge and ordinal_sq_hinge3 are ONE kind of the library (PMF_NOISE_SQ_HINGE) with per-column thresholds
+const NOISE_KIND = Dict("normal" => Cint(0), "bernoulli" => Cint(1), "poisson" => Cint(2),
+                        "bernoulli_sq_hinge" => Cint(3), "ordinal_sq_hinge3" => Cint(3))
 
 struct FitOpts            # pmf_fit_opts
     update_X::Cint; update_Y::Cint; update_col_layers::Cint; frozen_layers::Cint; frozen_regs::Cint
@@ -217,10 +219,23 @@ function data_context!(owner, data; device::Integer=0)
     return ctx
 end
 
-# MatFac noise structs -> the ABI's names: NormalNoise -> "normal", BernoulliNoise -> "bernoulli", PoissonNoise -> "poisson".
+# MatFac noise structs -> the ABI's names: NormalNoise -> "normal", BernoulliNoise -> "bernoulli", PoissonNoise -> "poisson",
+# SquaredHingeNoise -> "bernoulli_sq_hinge", OrdinalSqHingeNoise -> "ordinal_sq_hinge3" (simulate_params.jl:224-238).
 # (MatFac.jl is un-vendored: the per-column weight field set by MF.set_weight! (src/fit.jl:157,180) is assumed to be
 #  `weight`; adjust this one accessor if the struct names it differently.)
-noise_name(n) = lowercase(replace(string(nameof(typeof(n))), "Noise" => ""))
+const NOISE_STRUCT_NAMES = Dict("squaredhinge" => "bernoulli_sq_hinge", "ordinalsqhinge" => "ordinal_sq_hinge3")
+function noise_name(n)
+    s = lowercase(replace(string(nameof(typeof(n))), "Noise" => ""))
+    return get(NOISE_STRUCT_NAMES, s, s)
+end
+# (t0, t1, t2) of a squared-hinge range: SquaredHingeNoise has none of its own -> (0, Inf, Inf); OrdinalSqHingeNoise keeps
+# ext_thresholds = [-Inf, t1, t2, Inf] (simulate_params.jl:230-238), whose interior is sent behind a -Inf
+function hinge_thresholds(n)
+    noise_name(n) == "ordinal_sq_hinge3" || return Float32[0, Inf, Inf]
+    t = f32(collect(n.ext_thresholds[2:end-1]))
+    length(t) == 2 || error("ordinal_sq_hinge3 takes three classes, got $(length(t) + 1)")
+    return Float32[-Inf, t[1], t[2]]
+end
 noise_weights(nm) = vcat([collect(n.weight) for n in nm.noises]...)
 
 unwrap(l) = isa(l, PM.FrozenLayer) ? l.layer : l
@@ -304,6 +319,13 @@ function marshal!(ctx, mf; with_regs::Bool=true)
     w = f32(noise_weights(nm))
     GC.@preserve s e kinds w chk(ccall((:pmf_set_noise, LIB[]), Cint,
         (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Cint}, Ptr{Cfloat}), ctx, length(s), s, e, kinds, w))
+    hinge = findall(==(NOISE_KIND["ordinal_sq_hinge3"]), kinds)
+    if !isempty(hinge)
+        hs, he = s[hinge], e[hinge]
+        thr = vcat([hinge_thresholds(nm.noises[r]) for r in hinge]...)
+        GC.@preserve hs he thr chk(ccall((:pmf_set_noise_thresholds, LIB[]), Cint,
+            (Ptr{Cvoid}, Cint, Ptr{Int64}, Ptr{Int64}, Ptr{Cfloat}), ctx, length(hs), hs, he, thr))
+    end
     chk(ccall((:pmf_clear_xreg, LIB[]), Cint, (Ptr{Cvoid},), ctx)); with_regs && add_reg!(ctx, :X, mf.X_reg)
     chk(ccall((:pmf_clear_yreg, LIB[]), Cint, (Ptr{Cvoid},), ctx)); with_regs && add_reg!(ctx, :Y, mf.Y_reg)
     marshal_layer_regs!(ctx, mf.col_transform_reg, nviews)

@@ -11,12 +11,16 @@ from .regularizers import (BatchArrayReg, ColParamReg, FrozenRegularizer, Sequen
 from .util import ids_to_ranges, unique
 
 VALID_LOSSES = ["normal", "bernoulli", "bernoulli_sq_hinge", "poisson", "ordinal3", "ordinal_sq_hinge3"]  # util.jl:128
-SUPPORTED_LOSSES = ("normal", "bernoulli", "poisson")
+SUPPORTED_LOSSES = ("normal", "bernoulli", "poisson", "bernoulli_sq_hinge", "ordinal_sq_hinge3")
+# thresholds (t0, t1, t2) of the two squared-hinge models (one kind of the library, include/pmf_hip.h).  SELF-SPECIFIED
+# (DESIGN.md section 2): ordinal_sq_hinge3's default (-0.5, 0.5) is ours, MatFac's is not visible.
+HINGE_THRESHOLDS = {"bernoulli_sq_hinge": (0.0, np.inf, np.inf), "ordinal_sq_hinge3": (-np.inf, -0.5, 0.5)}
 
 
 class CompositeNoise:
     """MatFac's CompositeNoise{noises, col_ranges} as used at src/fit.jl:227, plus the per-column weights set by
-    MF.set_weight! (src/fit.jl:157, 180)."""
+    MF.set_weight! (src/fit.jl:157, 180).  `thresholds` has one entry per range: None, or the (t0, t1, t2) of a
+    squared-hinge range (constants of the fit, set_thresholds_)."""
 
     def __init__(self, feature_distributions):
         dists = list(feature_distributions)
@@ -28,10 +32,27 @@ class CompositeNoise:
             if d not in SUPPORTED_LOSSES:
                 raise NotImplementedError(f"noise model {d!r} is not implemented by the HIP path "
                                           f"(supported: {SUPPORTED_LOSSES}); see DESIGN.md 'out of scope'")
+        self.thresholds = [HINGE_THRESHOLDS.get(d) for d in self.noises]
         self.weights = np.ones(len(dists), dtype=np.float32)
 
     def set_weight_(self, w):
         self.weights = np.asarray(w, dtype=np.float32).copy()
+
+    def set_thresholds_(self, name_or_index, t):
+        """Thresholds of one squared-hinge range, by its distribution name or its index among the ranges:
+        bernoulli_sq_hinge takes one number (or (t0, inf, inf)), ordinal_sq_hinge3 two (t1, t2) (or (-inf, t1, t2))."""
+        r = self.noises.index(name_or_index) if isinstance(name_or_index, str) else int(name_or_index)
+        if self.thresholds[r] is None:
+            raise ValueError(f"noise model {self.noises[r]!r} has no thresholds")
+        t = [float(x) for x in np.atleast_1d(t)]
+        if len(t) != 3:
+            want = 1 if self.noises[r] == "bernoulli_sq_hinge" else 2
+            if len(t) != want:
+                raise ValueError(f"{self.noises[r]!r} takes {want} threshold(s) or the full triple, got {len(t)}")
+            t = [t[0], np.inf, np.inf] if want == 1 else [-np.inf, t[0], t[1]]
+        if not (t[0] <= t[1] <= t[2]):
+            raise ValueError(f"thresholds must be ordered, got {t}")
+        self.thresholds[r] = tuple(t)
 
 
 class MatFacModel:
@@ -90,6 +111,9 @@ def marshal(mf, ctx, with_xreg=True, with_yreg=True):
     ctx.set_batch_views(views)
     nm = mf.noise_model
     ctx.set_noise([(r.start, r.stop) for r in nm.col_ranges], list(nm.noises), nm.weights)
+    hinge = [(r, t) for r, t in zip(nm.col_ranges, nm.thresholds) if t is not None]
+    if hinge:
+        ctx.set_noise_thresholds([(r.start, r.stop) for r, _ in hinge], [t for _, t in hinge])
     ctx.clear_xreg()
     if with_xreg:
         mf.X_reg.add_to(ctx, "X")

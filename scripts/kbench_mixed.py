@@ -1,5 +1,7 @@
 """Fused-kernel timing of the general path (development aid): mixed Gaussian / Bernoulli columns, two batch views
-(scale + shift per (batch, column)), missing entries.  python scripts/kbench_mixed.py M N K"""
+(scale + shift per (batch, column)), missing entries.  python scripts/kbench_mixed.py M N K
+PMF_MIXED_KIND=bernoulli_sq_hinge|ordinal_sq_hinge3|poisson declares the non-Gaussian columns as that model instead of
+Bernoulli (the cost of a squared-hinge tile on the per-column path against the Bernoulli run on the same box)."""
 import sys
 import time
 from pathlib import Path
@@ -25,11 +27,12 @@ for (s, e) in ((1, h), (h + 1, N)):
                       theta=(0.1 * rng.standard_normal((nb, nv))).astype(np.float32)))
 ctx.set_batch_views(views if mode in ("all", "batch") else [])
 nbern = int(sys.argv[5]) if len(sys.argv) > 5 else N // 5
+mixed_kind = os.environ.get("PMF_MIXED_KIND", "bernoulli")
 if mode in ("all", "mixed"):
     if nbern >= N:   # every column Bernoulli: the per-tile cost of that noise model without any imbalance
-        ctx.set_noise([(1, N)], ["bernoulli"], np.ones(N, np.float32))
+        ctx.set_noise([(1, N)], [mixed_kind], np.ones(N, np.float32))
     else:
-        ctx.set_noise([(1, nbern), (nbern + 1, N)], ["bernoulli", "normal"], np.ones(N, np.float32))
+        ctx.set_noise([(1, nbern), (nbern + 1, N)], [mixed_kind, "normal"], np.ones(N, np.float32))
 else:
     ctx.set_noise([(1, N)], ["normal"], np.ones(N, np.float32))
 ctx.synth_data(seed=7, noise=0.1, frac_nan=0.05 if mode in ("all", "nan") else 0.0)
@@ -42,5 +45,5 @@ r = ctx.fit(update_X=True, update_Y=True, max_epochs=5, epoch=3, abs_tol=0, rel_
 wall = (time.time() - t0) / 3
 ms, n = ctx.kernel_time()
 fl = 6.0 * M * N * K
-print(f"[{mode}] {M}x{N} K={K}: epoch wall {wall*1e3:.2f} ms; fused kernel {ms:.3f} ms x{n} -> {fl/ms/1e9:.1f} TF/s "
+print(f"[{mode}{'' if mixed_kind == 'bernoulli' else ' ' + mixed_kind}] {M}x{N} K={K}: epoch wall {wall*1e3:.2f} ms; fused kernel {ms:.3f} ms x{n} -> {fl/ms/1e9:.1f} TF/s "
       f"({fl/ms/1e9/157.3*100:.1f}% of f32 MFMA peak); loss {r['loss'][0]:.5g} -> {r['loss'][-1]:.5g} {r['term_code']} nb={nb} path={ctx.last_path()} kernel family {ctx.last_kernel()} precision {ctx.get_precision()}")
