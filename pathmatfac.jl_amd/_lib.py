@@ -571,6 +571,22 @@ class Context:
         self._chk(self.lib.pmf_get_opt_state(self._h, PARAM[which], int(view), _fp(acc), _fp(mom)))
         return acc, mom
 
+    def _fsard_call(self, entry, start1, stop1, L, Nv, s_args, alpha, lam, alpha0, v0, lr, ssq_grad, max_epochs, term_iter,
+                    atol):
+        """What the two update_A! entries share: alpha, lambda and ssq_grad as the library takes them, the outputs, the call
+        (s_args: the entry's form of S) and the returned tuple."""
+        al = np.ascontiguousarray(alpha, dtype=np.float32)
+        lm = np.ascontiguousarray(lam, dtype=np.float32)
+        if ssq_grad.dtype != np.float32 or not ssq_grad.flags.c_contiguous or ssq_grad.shape != (L, self.K):
+            raise PMFError("ssq_grad must be a C-contiguous float32 L x K array")
+        A = np.zeros((L, self.K), np.float32)
+        beta = np.zeros((self.K, max(Nv, 0)), np.float32, order="F")
+        best, ep = C.c_double(0), C.c_int(0)
+        self._chk(entry(self._h, C.c_int64(start1), C.c_int64(stop1), int(L), *s_args, _fp(al), _fp(lm), C.c_float(alpha0),
+                        C.c_float(v0), C.c_float(lr), _fp(ssq_grad), _fp(A), int(max_epochs), int(term_iter),
+                        C.c_double(atol), C.byref(best), C.byref(ep), _fp(beta)))
+        return A, beta, best.value, ep.value
+
     def fsard_update_A(self, start1, stop1, S, alpha, lam, alpha0, v0, lr, ssq_grad, max_epochs=1000, term_iter=20,
                        atol=1e-5):
         """update_A! for one view on the device (pmf_fsard_update_A).  S: L x Nv, ssq_grad: L x K (updated in place).
@@ -579,18 +595,8 @@ class Context:
         L, Nv = S.shape
         if Nv != stop1 - start1 + 1:
             raise PMFError("S must have one column per column of the view")
-        al = np.ascontiguousarray(alpha, dtype=np.float32)
-        lm = np.ascontiguousarray(lam, dtype=np.float32)
-        if ssq_grad.dtype != np.float32 or not ssq_grad.flags.c_contiguous or ssq_grad.shape != (L, self.K):
-            raise PMFError("ssq_grad must be a C-contiguous float32 L x K array")
-        A = np.zeros((L, self.K), np.float32)
-        beta = np.zeros((self.K, Nv), np.float32, order="F")
-        best, ep = C.c_double(0), C.c_int(0)
-        self._chk(self.lib.pmf_fsard_update_A(self._h, C.c_int64(start1), C.c_int64(stop1), int(L), _fp(S), _fp(al), _fp(lm),
-                                              C.c_float(alpha0), C.c_float(v0), C.c_float(lr), _fp(ssq_grad), _fp(A),
-                                              int(max_epochs), int(term_iter), C.c_double(atol), C.byref(best), C.byref(ep),
-                                              _fp(beta)))
-        return A, beta, best.value, ep.value
+        return self._fsard_call(self.lib.pmf_fsard_update_A, start1, stop1, L, Nv, (_fp(S),), alpha, lam, alpha0, v0, lr,
+                                ssq_grad, max_epochs, term_iter, atol)
 
     def fsard_update_A_csr(self, start1, stop1, S, alpha, lam, alpha0, v0, lr, ssq_grad, max_epochs=1000, term_iter=20,
                            atol=1e-5):
@@ -619,16 +625,9 @@ class Context:
         lm = np.ascontiguousarray(lam, dtype=np.float32)
         if al.size != Nv or lm.size != self.K:
             raise PMFError("alpha must have one entry per column of the view and lambda one per factor")
-        if ssq_grad.dtype != np.float32 or not ssq_grad.flags.c_contiguous or ssq_grad.shape != (L, self.K):
-            raise PMFError("ssq_grad must be a C-contiguous float32 L x K array")
-        A = np.zeros((L, self.K), np.float32)
-        beta = np.zeros((self.K, max(Nv, 0)), np.float32, order="F")
-        best, ep = C.c_double(0), C.c_int(0)
-        self._chk(self.lib.pmf_fsard_update_A_csr(
-            self._h, C.c_int64(start1), C.c_int64(stop1), int(L), _i64p(rowptr), col.ctypes.data_as(C.POINTER(C.c_int32)),
-            _fp(val), _fp(al), _fp(lm), C.c_float(alpha0), C.c_float(v0), C.c_float(lr), _fp(ssq_grad), _fp(A),
-            int(max_epochs), int(term_iter), C.c_double(atol), C.byref(best), C.byref(ep), _fp(beta)))
-        return A, beta, best.value, ep.value
+        s_args = (_i64p(rowptr), col.ctypes.data_as(C.POINTER(C.c_int32)), _fp(val))
+        return self._fsard_call(self.lib.pmf_fsard_update_A_csr, start1, stop1, L, Nv, s_args, al, lm, alpha0, v0, lr,
+                                ssq_grad, max_epochs, term_iter, atol)
 
     def forward(self):
         Z = np.zeros((self.M, self.N), np.float32, order="F")

@@ -5,6 +5,7 @@
 //   pmf_comm_fit.hip  cross-rank exchange (RCCL via dlopen / host-staged transport) and the epoch loop pmf_fit
 //   pmf_fsard.hip     the FeatureSetARD update_A! solver (ISTA on the device; dense S, A in LDS, L x K <= 16384)
 //   pmf_fsard_csr.hip the same solver on a sparse S with A in device memory (no bound on L x K)
+//   pmf_fsard_loop.h  what those two share: the loop's formulas, bookkeeping and ISTA update, its checks and host driver
 //   pmf_netreg.hip    NetworkRegularizer (per-factor CG solve + sparse gradient) and the L1 / SelectiveL1 weights
 //   pmf_lbfgs.hip     L-BFGS over (X, Y): total gradient, history, two-loop recursion, backtracking (pmf_fit_lbfgs)
 //   pmf_stages.hip    the closed-form stages between the GD stages on the device statistics (pmf_stage_*)
@@ -293,6 +294,17 @@ __device__ __forceinline__ double block_reduce_sum(double v, double *sh) {
   if (threadIdx.x == 0)
     for (int q = 0; q < (int)(blockDim.x >> 6); ++q) s += sh[q];
   return s;  // valid on thread 0
+}
+// sum over a workgroup of 256 threads in a fixed order: lanes by shuffles, the four waves in index order; every thread
+// gets it, and sh (4 doubles) is free again on return
+__device__ __forceinline__ double block_all_sum_256(double v, double *sh) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  const double s = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+  __syncthreads();
+  return s;
 }
 
 // ---- the regularizer + optimizer step kernel's arguments (k_reg_step, pmf_hip.hip) and the per-entry value and gradient

@@ -72,21 +72,11 @@ static inline double *lb_slab(const LbfgsState *st, int t) { return st->part + (
 __device__ __forceinline__ float4 *lb_at(const LbVec &v, int64_t i, int64_t n04) {
   return i < n04 ? reinterpret_cast<float4 *>(v.x) + i : reinterpret_cast<float4 *>(v.y) + (i - n04);
 }
-// sum over the workgroup in a fixed order (lanes by shuffles, waves in index order); every thread gets the value
-__device__ __forceinline__ double lb_block_sum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-  __syncthreads();
-  return s;
-}
 // the sum of a slab row of nb partials, by every workgroup alike
 __device__ __forceinline__ double lb_slab_sum(const double *row, int nb, double *sh) {
   double v = 0.0;
   for (int q = threadIdx.x; q < nb; q += 256) v += row[q];
-  return lb_block_sum(v, sh);
+  return block_all_sum_256(v, sh);
 }
 __device__ __forceinline__ void lb_acc(double &d, const float4 &a, const float4 &b) {
   d += (double)(a.x * b.x);
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(256) void k_lb_grad(const LbGradArgs a) {
     }
   }
   if (a.have_old) {
-    const double s0 = lb_block_sum(d0, sh), s1 = lb_block_sum(d1, sh);
+    const double s0 = block_all_sum_256(d0, sh), s1 = block_all_sum_256(d1, sh);
     if (threadIdx.x == 0) { a.part[blockIdx.x] = s0; a.part[LB_MAXB + blockIdx.x] = s1; }
   }
 }
@@ -163,7 +153,7 @@ __global__ __launch_bounds__(256) void k_lb_dot(const LbVec va, const LbVec vb, 
     lb_acc(d0, x, y);
     lb_acc(d1, x, x);
   }
-  const double s0 = lb_block_sum(d0, sh), s1 = lb_block_sum(d1, sh);
+  const double s0 = block_all_sum_256(d0, sh), s1 = block_all_sum_256(d1, sh);
   if (threadIdx.x == 0) { part[blockIdx.x] = s0; part[LB_MAXB + blockIdx.x] = s1; }
 }
 // one workgroup: <s,y> and <y,y> of history slot k from the partials of k_lb_grad / k_lb_dot
@@ -221,11 +211,11 @@ __global__ __launch_bounds__(256) void k_lb_sweep(const LbSweepArgs a) {
     if (a.dots & 2) { lb_acc(d1, p, p); lb_acc(d2, p, g4); }
   }
   if (a.dots & 1) {
-    const double s = lb_block_sum(d0, sh);
+    const double s = block_all_sum_256(d0, sh);
     if (threadIdx.x == 0) a.part[blockIdx.x] = s;
   }
   if (a.dots & 2) {
-    const double s1 = lb_block_sum(d1, sh), s2 = lb_block_sum(d2, sh);
+    const double s1 = block_all_sum_256(d1, sh), s2 = block_all_sum_256(d2, sh);
     if (threadIdx.x == 0) { a.part[LB_MAXB + blockIdx.x] = s1; a.part[2 * LB_MAXB + blockIdx.x] = s2; }
   }
 }

@@ -45,17 +45,6 @@ __global__ __launch_bounds__(256) void k_netreg_transpose(const float *__restric
   }
 }
 
-// sum over the workgroup, the same value on every thread: lanes by xor shuffles, waves in index order
-__device__ __forceinline__ double netreg_allsum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-  __syncthreads();
-  return s;
-}
-
 struct NetSolveArgs {
   const float *PT;
   const int64_t *voff, *abt_rp, *bb_rp;
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(256) void k_netreg_solve(const NetSolveArgs a) {
     acc += (double)s * (double)s;
     if (lds) u[i] = ug[i];
   }
-  const double tt = netreg_allsum(acc, sh);       // (its barriers also publish t and u)
+  const double tt = block_all_sum_256(acc, sh);       // (its barriers also publish t and u)
   if (tt == 0.0) {                                // t = 0: u = 0 exactly
     for (int i = tid; i < v; i += 256) ug[i] = 0.f;
     if (tid == 0) { a.iters[k] = 0; a.uloss[k] = 0.0; }
@@ -111,7 +100,7 @@ __global__ __launch_bounds__(256) void k_netreg_solve(const NetSolveArgs a) {
     d[i] = ri;
     acc += (double)ri * (double)ri;
   }
-  double rr = netreg_allsum(acc, sh);
+  double rr = block_all_sum_256(acc, sh);
   const double stop2 = (NETREG_RTOL * NETREG_RTOL) * tt;
   int it = 0;
   while (rr > stop2 && it < 2 * v) {
@@ -123,7 +112,7 @@ __global__ __launch_bounds__(256) void k_netreg_solve(const NetSolveArgs a) {
       q[i] = s;
       acc += (double)d[i] * (double)s;
     }
-    const double dq = netreg_allsum(acc, sh);
+    const double dq = block_all_sum_256(acc, sh);
     if (!(dq > 0.0)) break;                       // (BB is positive definite: only reachable with a malformed matrix)
     const float alpha = (float)(rr / dq);
     acc = 0.0;
@@ -133,7 +122,7 @@ __global__ __launch_bounds__(256) void k_netreg_solve(const NetSolveArgs a) {
       r[i] = ri;
       acc += (double)ri * (double)ri;
     }
-    const double rr_new = netreg_allsum(acc, sh);
+    const double rr_new = block_all_sum_256(acc, sh);
     const float beta = (float)(rr_new / rr);
     for (int i = tid; i < v; i += 256) d[i] = r[i] + beta * d[i];
     rr = rr_new;
@@ -148,7 +137,7 @@ __global__ __launch_bounds__(256) void k_netreg_solve(const NetSolveArgs a) {
     const double ui = (double)u[i];
     acc += (double)t[i] * ui + 0.5 * ui * s;
   }
-  const double ul = netreg_allsum(acc, sh);
+  const double ul = block_all_sum_256(acc, sh);
   if (lds)
     for (int i = tid; i < v; i += 256) ug[i] = u[i];
   if (tid == 0) { a.iters[k] = it; a.uloss[k] = ul; }

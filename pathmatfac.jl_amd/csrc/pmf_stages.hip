@@ -22,16 +22,6 @@
 static inline unsigned st_grid(int64_t n) { return (unsigned)std::max<int64_t>(1, (n + 255) / 256); }
 #define ST_MAXB 1024   // workgroups of the theta update at most = partials per sum of the stopping rule
 
-// sum over the workgroup (256 threads) in a fixed order: lanes by shuffles, waves in index order; every thread gets it
-__device__ __forceinline__ double st_block_sum(double v, double *sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const double s = ((sh[0] + sh[1]) + sh[2]) + sh[3];
-  __syncthreads();
-  return s;
-}
 __device__ __forceinline__ bool st_finite(double x) { return fabs(x) <= 1.7976931348623157e308; }   // (false for NaN)
 
 // Four consecutive elements per thread: 128-bit loads and stores for a whole quad at a 16-byte aligned address (`vec`:
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(256) void k_stage_group(const double *__restrict__ 
     ssig += sig * sig;
     svar += var * n;
   }
-  const double a = st_block_sum(ssig, sh), b = st_block_sum(svar, sh);
+  const double a = block_all_sum_256(ssig, sh), b = block_all_sum_256(svar, sh);
   if (threadIdx.x == 0) out[blockIdx.x] = (float)(K * (a / (double)(j1 - j0)) / (b / M_total));
 }
 
@@ -138,13 +128,13 @@ __device__ __forceinline__ void em_row_moments(const T *__restrict__ x, int64_t 
                                                double &mean, double &var) {
   double s = 0.0;
   for (int64_t jj = threadIdx.x; jj < Nv; jj += 256) s += (double)x[base + jj * nb];
-  mean = st_block_sum(s, sh) / (double)Nv;
+  mean = block_all_sum_256(s, sh) / (double)Nv;
   double q = 0.0;
   for (int64_t jj = threadIdx.x; jj < Nv; jj += 256) {
     const double d = (double)x[base + jj * nb] - mean;
     q += d * d;
   }
-  var = st_block_sum(q, sh) / (double)(Nv - 1);   // N_v = 1: 0 / 0 = NaN, absorbed by the updates' NaN rules
+  var = block_all_sum_256(q, sh) / (double)(Nv - 1);   // N_v = 1: 0 / 0 = NaN, absorbed by the updates' NaN rules
 }
 // mom = [theta mean | theta var | alpha | beta], n_rows doubles each
 __global__ __launch_bounds__(256) void k_em_moments(const double *__restrict__ theta, const double *__restrict__ delta2,
@@ -212,7 +202,7 @@ __global__ __launch_bounds__(256) void k_em_theta(const EmArgs a) {
     st_st4(a.theta64, e0, cnt, true, t64);
     st_st4(a.theta, e0, cnt, true, tn);
   }
-  const double sn = st_block_sum(num, sh), sd = st_block_sum(den, sh);
+  const double sn = block_all_sum_256(num, sh), sd = block_all_sum_256(den, sh);
   if (threadIdx.x == 0) {
     a.part[blockIdx.x] = sn;
     a.part[ST_MAXB + blockIdx.x] = sd;
@@ -225,7 +215,7 @@ __global__ __launch_bounds__(256) void k_em_diff(const double *__restrict__ part
     num += part[q];
     den += part[ST_MAXB + q];
   }
-  const double sn = st_block_sum(num, sh), sd = st_block_sum(den, sh);
+  const double sn = block_all_sum_256(num, sh), sd = block_all_sum_256(den, sh);
   if (threadIdx.x == 0) out[0] = sn / sd;
 }
 __global__ __launch_bounds__(256) void k_em_delta2(const EmArgs a) {

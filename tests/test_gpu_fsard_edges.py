@@ -302,17 +302,17 @@ def _refusal_args(case, **over):
     return a
 
 
-REFUSALS = {
-    "LK_16385": lambda c: _refusal_args(c, L=16385, S=np.zeros((16385, c["Nv"]), F)),          # K = 1 below
-    "empty_range": lambda c: _refusal_args(c, start1=5, stop1=4),
-    "reversed_range": lambda c: _refusal_args(c, start1=10, stop1=5),
-    "start_0": lambda c: _refusal_args(c, start1=0, stop1=c["Nv"] - 1),
-    "stop_past_N": lambda c: _refusal_args(c, start1=2, stop1=c["N"] + 1),
-    "L_0": lambda c: _refusal_args(c, L=0),
-    "L_negative": lambda c: _refusal_args(c, L=-3),
-    "term_iter_0": lambda c: _refusal_args(c, term_iter=0),
-    "term_iter_negative": lambda c: _refusal_args(c, term_iter=-1),
-    "max_epochs_negative": lambda c: _refusal_args(c, max_epochs=-1),
+REFUSALS = {      # name -> (arguments, a word of the message)
+    "LK_16385": (lambda c: _refusal_args(c, L=16385, S=np.zeros((16385, c["Nv"]), F)), "capacity"),          # K = 1 below
+    "empty_range": (lambda c: _refusal_args(c, start1=5, stop1=4), "col_start1"),
+    "reversed_range": (lambda c: _refusal_args(c, start1=10, stop1=5), "col_start1"),
+    "start_0": (lambda c: _refusal_args(c, start1=0, stop1=c["Nv"] - 1), "col_start1"),
+    "stop_past_N": (lambda c: _refusal_args(c, start1=2, stop1=c["N"] + 1), "col_stop1"),
+    "L_0": (lambda c: _refusal_args(c, L=0), "L must"),
+    "L_negative": (lambda c: _refusal_args(c, L=-3), "L must"),
+    "term_iter_0": (lambda c: _refusal_args(c, term_iter=0), "term_iter"),
+    "term_iter_negative": (lambda c: _refusal_args(c, term_iter=-1), "term_iter"),
+    "max_epochs_negative": (lambda c: _refusal_args(c, max_epochs=-1), "max_epochs"),
 }
 
 
@@ -324,7 +324,8 @@ def test_refusals_name_the_argument_and_leave_the_context_usable(pkg, ctx, name)
     spec = fr.REFUSAL_ROWS["good_after_refusal_K1" if name == "LK_16385" else "good_after_refusal"]
     good = fr.make_case(**spec)
     load(ctx, good)
-    a = REFUSALS[name](good)
+    make, word = REFUSALS[name]
+    a = make(good)
     rows = max(a["L"], good["L"], 1)
     ssq = np.full((rows, good["K"]), 0.25, F)
     A = np.full((rows, good["K"]), -1.0, F)
@@ -333,7 +334,7 @@ def test_refusals_name_the_argument_and_leave_the_context_usable(pkg, ctx, name)
         assert a["L"] * good["K"] == fr.CAPACITY + 1
     rc, best, epochs, msg = raw_update_A(ctx, a["start1"], a["stop1"], a["L"], a["S"], a["alpha"], a["lam"], good["alpha0"],
                                          good["v0"], good["lr"], ssq, A, a["max_epochs"], a["term_iter"], good["atol"], beta)
-    assert rc != 0 and len(msg) > 8, (rc, msg)
+    assert rc != 0 and "pmf_fsard_update_A" in msg and word in msg, (rc, msg)
     assert np.isnan(best) and epochs == -7
     assert np.all(ssq == F(0.25)) and np.all(A == F(-1.0)) and np.all(beta == F(-2.0))
     with pytest.raises(pkg.PMFError):
