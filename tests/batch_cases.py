@@ -31,7 +31,7 @@ import functools
 
 import numpy as np
 
-from problems import make_problem, to_oracle
+from problems import factor_scales, make_problem, to_oracle
 
 GRADS = {"both": dict(update_X=True, update_Y=True), "X": dict(update_X=True), "Y": dict(update_Y=True)}
 BOTH = GRADS["both"]
@@ -339,6 +339,16 @@ def oracle_of(p):
         _, go = to_oracle(p).loss_and_grads(**BOTH)
         _ORACLE[key] = (p, dict(data_loss=go["data_loss"], X=go["X"], Y=go["Y"]))
     return _ORACLE[key][1]
+
+
+_SCALES = {}
+
+
+def scales_of(p):
+    """problems.factor_scales(p), once per problem (cached by identity, like oracle_of)."""
+    if id(p) not in _SCALES:
+        _SCALES[id(p)] = (p, factor_scales(p))
+    return _SCALES[id(p)][1]
 
 
 # ---- mutants for the sensitivity condition ---------------------------------------------------------------------------

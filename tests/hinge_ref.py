@@ -25,7 +25,7 @@ import functools
 import numpy as np
 
 import batch_cases as bc
-from problems import make_problem
+from problems import factor_scales, make_problem
 
 KIND = {"normal": 0, "bernoulli": 1, "poisson": 2, "bernoulli_sq_hinge": 3, "ordinal_sq_hinge3": 3}
 INF = np.inf
@@ -180,11 +180,12 @@ def threshold_gap(p, z):
     return np.where(np.isnan(d), np.inf, d).min(-1)
 
 
-def layer_scales(p):
-    """problems.layer_scales with kind 3: per observed entry sG = w (|a| + |b| + |lo|[a > 0] + |hi|[b > 0] + link' r) with
+def entry_scales(p, c0=0, c1=None):
+    """problems.entry_scales with kind 3: per observed entry sG = w (|a| + |b| + |lo|[a > 0] + |hi|[b > 0] + link' r) with
     link' = [a > 0] + [b > 0] in {0, 1, 2} -- g = w (b - a), a = 1 - z + lo, b = 1 + z - hi: the magnitudes the kernel
     rounds are the two terms, the bounds they are formed from, and z (through r) once per active term -- and the loss
-    magnitude 0.5 w (a^2 + b^2), the loss itself.  Kinds 0..2 as there (tests/test_hinge_cases.py holds the two equal)."""
+    magnitude 0.5 w (a^2 + b^2), the loss itself.  Kinds 0..2 as there (tests/test_hinge_cases.py holds the two equal).
+    The whole matrix is evaluated (these problems are small) and the columns [c0, c1) returned."""
     X, Y = np.asarray(p["X"], np.float64), np.asarray(p["Y"], np.float64)
     sig, mu = np.exp(np.asarray(p["logsigma"], np.float64)), np.asarray(p["mu"], np.float64)
     w, kind, t = np.asarray(p["col_weight"], np.float64), kinds_of(p), thresholds_of(p)
@@ -213,8 +214,17 @@ def layer_scales(p):
     lm = np.where(kind[None, :] == 0, 0.5 * (z - y) ** 2,
                   np.where(kind[None, :] == 3, e["l"],
                            np.where(kind[None, :] == 1, np.logaddexp(0.0, z), np.exp(np.minimum(z, 700.0))) + np.abs(y * z)))
-    out = dict(mu=sG.sum(0), logsigma=sig * (dl * sG).sum(0), theta=[], logdelta=[], g=g,
-               loss=float(np.sum(np.where(obs, w[None, :] * lm, 0.0))))
+    out = dict(g=g, sG=sG, sQ=sQ, sd=sig[None, :] * dl, delta=dl, loss=np.where(obs, w[None, :] * lm, 0.0))
+    return {k: v[:, c0:c1] for k, v in out.items()}
+
+
+def layer_scales(p):
+    """problems.layer_scales from the entry terms above (kind 3 included)."""
+    sig = np.exp(np.asarray(p["logsigma"], np.float64))
+    e = entry_scales(p)
+    sG, sQ = e["sG"], e["sQ"]
+    out = dict(mu=sG.sum(0), logsigma=sig * (e["delta"] * sG).sum(0), theta=[], logdelta=[], g=e["g"],
+               loss=float(np.sum(e["loss"])))
     for v, (c0, c1, bor, onehot) in zip(p["batch_views"], batch_terms(p)[2]):
         out["theta"].append(onehot.T @ sG[:, c0:c1])
         out["logdelta"].append(np.exp(np.asarray(v["logdelta"], np.float64)) * (onehot.T @ sQ[:, c0:c1]))
@@ -286,6 +296,17 @@ def reference_of(p):
     if id(p) not in _REF:
         _REF[id(p)] = (p, reference(p))
     return _REF[id(p)][1]
+
+
+_SCALES = {}
+
+
+def scales_of(p):
+    """problems.factor_scales(p) -- it takes the entry terms of a problem with "noise_thr" from entry_scales above -- once
+    per problem (cached by identity, like reference_of)."""
+    if id(p) not in _SCALES:
+        _SCALES[id(p)] = (p, factor_scales(p))
+    return _SCALES[id(p)][1]
 
 
 def to_context(p, ctx):

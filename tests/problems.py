@@ -217,76 +217,98 @@ def shard_problem(p, lo, hi):
 LAYER_TAU = 2e-5
 
 
-def layer_scales(p, cols=4096):
-    """fp64 error scales of the four layer gradients of problem `p`: the per-(batch, column) sums of the magnitudes a
-    kernel rounds on the way to each gradient.  z comes from the fp64 forward of DESIGN section 4.3 (restated here, per
-    noise kind): z1 = sigma_j a_ij, z = z1 delta_bj + mu_j + theta_bj (delta = 1, theta = 0 for rows with batch -1 and for
-    columns outside every batch view), g = w_j (link(z) - y) on observed entries.  Per observed entry
-
-        sG_ij = w_j (|link(z)| + |y| + link'(z) r_ij),   r_ij = sigma_j delta_bj sum_k |X_ki Y_kj| + |mu_j| + |theta_bj|
-        sQ_ij = |z1_ij| sG_ij + |g_ij| sigma_j sum_k |X_ki Y_kj|
-
-    (r bounds what the forward rounds, link' carries it into g; the second term of sQ is the rounding of z1 itself), and
-
-        grad theta[b, j]    ~ sum_{i in b} sG           grad mu[j]       ~ sum_i sG
-        grad logdelta[b, j] ~ delta_bj sum_{i in b} sQ  grad logsigma[j] ~ sigma_j sum_i delta_bj sG
-
-    The scales only set tolerances; the reference value of every gradient stays the oracle's.  Also returns g (M x N)
-    and, as "loss", the sum of the magnitudes of the loss terms: 0.5 w (z - y)^2 (Gaussian: the loss itself),
-    w (softplus(z) + |y z|) (Bernoulli), w (e^z + |y z|) (Poisson) -- the last two cancel term by term.  Works on blocks
-    of `cols` columns (wide problems)."""
-    X = np.asarray(p["X"], np.float64)
-    Y = np.asarray(p["Y"], np.float64)
-    D = p["D"]
-    M, N = D.shape
-    sig_all = np.exp(np.asarray(p["logsigma"], np.float64))
-    mu_all = np.asarray(p["mu"], np.float64)
-    w_all = np.asarray(p["col_weight"], np.float64)
-    kind = np.zeros(N, np.int8)                                   # 0 normal, 1 bernoulli, 2 poisson
-    for (s, e), kd in zip(p["noise_ranges"], p["noise_kinds"]):
-        kind[s - 1:e] = {"normal": 0, "bernoulli": 1, "poisson": 2}[kd]
+def _batch_views_of(p):
+    """(c0, c1, batch_of_row, has a batch, nb, delta, theta, one-hot M x nb) per batch view, in fp64."""
     bvs = []
     for bv in p["batch_views"]:
         bor = np.asarray(bv["batch_of_row"])
         nb = np.asarray(bv["logdelta"]).shape[0]
         bvs.append((bv["start1"] - 1, bv["stop1"], bor, bor >= 0, nb, np.exp(np.asarray(bv["logdelta"], np.float64)),
                     np.asarray(bv["theta"], np.float64), (bor[:, None] == np.arange(nb)[None, :]).astype(np.float64)))
+    return bvs
+
+
+def entry_scales(p, c0=0, c1=None, bvs=None):
+    """The per-entry part of the error scales, in fp64, on the columns [c0, c1) of problem `p` (all of them by default).
+    z comes from the fp64 forward of DESIGN section 4.3 (restated here, per noise kind): z1 = sigma_j a_ij,
+    z = z1 delta_bj + mu_j + theta_bj (delta = 1, theta = 0 for rows with batch -1 and for columns outside every batch
+    view), g = w_j (link(z) - y) on observed entries.  Per observed entry
+
+        sG_ij = w_j (|link(z)| + |y| + link'(z) r_ij),   r_ij = sigma_j delta_bj sum_k |X_ki Y_kj| + |mu_j| + |theta_bj|
+        sQ_ij = |z1_ij| sG_ij + |g_ij| sigma_j sum_k |X_ki Y_kj|
+
+    (r bounds what the forward rounds, link' carries it into g; the second term of sQ is the rounding of z1 itself).
+    Returns M x (c1 - c0) arrays, 0 on unobserved entries: g, sG, sQ, sd = sigma_j delta_bj (on every entry: the factor
+    that takes dloss/dz to dloss/d(X'Y)), and "loss", the magnitudes of the loss terms: 0.5 w (z - y)^2 (Gaussian: the loss
+    itself), w (softplus(z) + |y z|) (Bernoulli), w (e^z + |y z|) (Poisson) -- the last two cancel term by term.  A problem
+    with squared-hinge columns ("noise_thr") takes the same quantities from hinge_ref.entry_scales."""
+    if p.get("noise_thr"):
+        import hinge_ref
+        return hinge_ref.entry_scales(p, c0, c1)
+    N = p["D"].shape[1]
+    c1 = N if c1 is None else c1
+    bvs = _batch_views_of(p) if bvs is None else bvs
+    X = np.asarray(p["X"], np.float64)
+    Y = np.asarray(p["Y"], np.float64)
+    kind = np.zeros(N, np.int8)                                   # 0 normal, 1 bernoulli, 2 poisson
+    for (s, e), kd in zip(p["noise_ranges"], p["noise_kinds"]):
+        kind[s - 1:e] = {"normal": 0, "bernoulli": 1, "poisson": 2}[kd]
+    sig = np.exp(np.asarray(p["logsigma"], np.float64))[c0:c1]
+    mu = np.asarray(p["mu"], np.float64)[c0:c1]
+    w = np.asarray(p["col_weight"], np.float64)[c0:c1]
+    kd = kind[c0:c1]
+    A = X.T @ Y[:, c0:c1]
+    Aabs = np.abs(X).T @ np.abs(Y[:, c0:c1])
+    dl = np.ones_like(A)
+    th = np.zeros_like(A)
+    for s, e, bor, has, nb, delta, theta, onehot in bvs:
+        a, b = max(s, c0), min(e, c1)
+        if a < b:
+            dl[np.ix_(has, np.arange(a - c0, b - c0))] = delta[bor[has]][:, a - s:b - s]
+            th[np.ix_(has, np.arange(a - c0, b - c0))] = theta[bor[has]][:, a - s:b - s]
+    z1 = A * sig[None, :]
+    z = z1 * dl + mu[None, :] + th
+    link, dlink = z.copy(), np.ones_like(z)
+    bern, pois = kd == 1, kd == 2
+    sg = 0.5 * (1.0 + np.tanh(0.5 * z[:, bern]))
+    link[:, bern], dlink[:, bern] = sg, sg * (1.0 - sg)
+    link[:, pois] = dlink[:, pois] = np.exp(z[:, pois])
+    Dc = np.asarray(p["D"][:, c0:c1], np.float64)
+    obs = np.isfinite(Dc)
+    y = np.where(obs, Dc, 0.0)
+    g = np.where(obs, w[None, :] * (link - y), 0.0)
+    r = sig[None, :] * Aabs * dl + np.abs(mu)[None, :] + np.abs(th)
+    sG = np.where(obs, w[None, :] * (np.abs(link) + np.abs(y) + dlink * r), 0.0)
+    sQ = np.abs(z1) * sG + np.abs(g) * sig[None, :] * Aabs
+    lm = np.where(kd[None, :] == 0, 0.5 * (z - y) ** 2,
+                  np.where(kd[None, :] == 1, np.logaddexp(0.0, z), np.exp(np.minimum(z, 700.0))) + np.abs(y * z))
+    return dict(g=g, sG=sG, sQ=sQ, sd=sig[None, :] * dl, delta=dl, loss=np.where(obs, w[None, :] * lm, 0.0))
+
+
+def layer_scales(p, cols=4096):
+    """fp64 error scales of the four layer gradients of problem `p`: the per-(batch, column) sums of the magnitudes a
+    kernel rounds on the way to each gradient.  With sG, sQ and delta of entry_scales,
+
+        grad theta[b, j]    ~ sum_{i in b} sG           grad mu[j]       ~ sum_i sG
+        grad logdelta[b, j] ~ delta_bj sum_{i in b} sQ  grad logsigma[j] ~ sigma_j sum_i delta_bj sG
+
+    The scales only set tolerances; the reference value of every gradient stays the oracle's.  Also returns g (M x N)
+    and, as "loss", the sum of the magnitudes of the loss terms.  Works on blocks of `cols` columns (wide problems)."""
+    M, N = p["D"].shape
+    bvs = _batch_views_of(p)
+    sig_all = np.exp(np.asarray(p["logsigma"], np.float64))
     out = dict(mu=np.zeros(N), logsigma=np.zeros(N), theta=[np.zeros((b[4], b[1] - b[0])) for b in bvs],
                logdelta=[np.zeros((b[4], b[1] - b[0])) for b in bvs], g=np.zeros((M, N)), loss=0.0)
     for c0 in range(0, N, cols):
         c1 = min(N, c0 + cols)
-        sig, mu, w, kd = sig_all[c0:c1], mu_all[c0:c1], w_all[c0:c1], kind[c0:c1]
-        A = X.T @ Y[:, c0:c1]
-        Aabs = np.abs(X).T @ np.abs(Y[:, c0:c1])
-        dl = np.ones_like(A)
-        th = np.zeros_like(A)
-        for s, e, bor, has, nb, delta, theta, onehot in bvs:
-            a, b = max(s, c0), min(e, c1)
-            if a < b:
-                dl[np.ix_(has, np.arange(a - c0, b - c0))] = delta[bor[has]][:, a - s:b - s]
-                th[np.ix_(has, np.arange(a - c0, b - c0))] = theta[bor[has]][:, a - s:b - s]
-        z1 = A * sig[None, :]
-        z = z1 * dl + mu[None, :] + th
-        link, dlink = z.copy(), np.ones_like(z)
-        bern, pois = kd == 1, kd == 2
-        sg = 0.5 * (1.0 + np.tanh(0.5 * z[:, bern]))
-        link[:, bern], dlink[:, bern] = sg, sg * (1.0 - sg)
-        link[:, pois] = dlink[:, pois] = np.exp(z[:, pois])
-        Dc = np.asarray(D[:, c0:c1], np.float64)
-        obs = np.isfinite(Dc)
-        y = np.where(obs, Dc, 0.0)
-        g = np.where(obs, w[None, :] * (link - y), 0.0)
-        r = sig[None, :] * Aabs * dl + np.abs(mu)[None, :] + np.abs(th)
-        sG = np.where(obs, w[None, :] * (np.abs(link) + np.abs(y) + dlink * r), 0.0)
-        sQ = np.abs(z1) * sG + np.abs(g) * sig[None, :] * Aabs
-        lm = np.where(kd[None, :] == 0, 0.5 * (z - y) ** 2,
-                      np.where(kd[None, :] == 1, np.logaddexp(0.0, z), np.exp(np.minimum(z, 700.0))) + np.abs(y * z))
-        out["loss"] += float(np.sum(np.where(obs, w[None, :] * lm, 0.0)))
-        out["g"][:, c0:c1] = g
+        e = entry_scales(p, c0, c1, bvs)
+        sG, sQ = e["sG"], e["sQ"]
+        out["loss"] += float(np.sum(e["loss"]))
+        out["g"][:, c0:c1] = e["g"]
         out["mu"][c0:c1] = sG.sum(0)
-        out["logsigma"][c0:c1] = sig * (dl * sG).sum(0)
-        for v, (s, e, bor, has, nb, delta, theta, onehot) in enumerate(bvs):   # rows with batch -1: no segment
-            a, b = max(s, c0), min(e, c1)
+        out["logsigma"][c0:c1] = sig_all[c0:c1] * (e["delta"] * sG).sum(0)
+        for v, (s, e_, bor, has, nb, delta, theta, onehot) in enumerate(bvs):   # rows with batch -1: no segment
+            a, b = max(s, c0), min(e_, c1)
             if a < b:
                 out["theta"][v][:, a - s:b - s] = onehot.T @ sG[:, a - c0:b - c0]
                 out["logdelta"][v][:, a - s:b - s] = delta[:, a - s:b - s] * (onehot.T @ sQ[:, a - c0:b - c0])
@@ -321,3 +343,97 @@ def layer_check(p, got, want, tau=LAYER_TAU, tiny=1e-30, scales=None, skip=()):
                 r = max(r, float(np.max(np.abs(a - b) / (tau * c + tiny))))
         worst[k] = r
     return worst
+
+
+# ---- an element-scaled check for the factor gradients ----------------------------------------------------------------
+FACTOR_TAU = LAYER_TAU
+
+
+def factor_scales(p, cols=None):
+    """fp64 error scales of the two factor gradients of problem `p`.  gX_ki = sum_j G_ij Y_kj and gY_kj = sum_i G_ij X_ki
+    with G_ij = sigma_j delta_bj g_ij; what a kernel rounds on the way to G_ij is bounded by sigma_j delta_bj sG_ij (sG of
+    entry_scales: the magnitudes g is formed from, and the forward's through link'), and rounding G_ij itself or the other
+    operand is relative to |G_ij| |Y_kj| <= sigma_j delta_bj sG_ij |Y_kj|.  So every element is held to the sum of the
+    magnitudes of its own terms:
+
+        X (K x M): sGX[k, i] = sum_j sigma_j delta_ij sG_ij |Y_kj|
+        Y (K x N): sGY[k, j] = sum_i sigma_j delta_ij sG_ij |X_ki|
+
+    Works on blocks of `cols` columns (default: about 4M entries per block), so tall problems stay cheap."""
+    M, N = p["D"].shape
+    Xa = np.abs(np.asarray(p["X"], np.float64))
+    Ya = np.abs(np.asarray(p["Y"], np.float64))
+    cols = max(32, min(4096, (1 << 22) // max(M, 1))) if cols is None else cols
+    bvs = None if p.get("noise_thr") else _batch_views_of(p)
+    out = dict(X=np.zeros(Xa.shape), Y=np.zeros(Ya.shape))
+    for c0 in range(0, N, cols):
+        c1 = min(N, c0 + cols)
+        e = entry_scales(p, c0, c1, bvs)
+        W = e["sd"] * e["sG"]
+        out["X"] += Ya[:, c0:c1] @ W.T
+        out["Y"][:, c0:c1] = Xa @ W
+    return out
+
+
+def factor_check(p, got, want, tau=FACTOR_TAU, scales=None):
+    """{"X": worst, "Y": worst} over the factor gradients present in `got`: the worst ratio |got - want| / (tau * scale +
+    1e-30) over the elements of each (<= 1 passes; a non-finite `got` gives inf).  `want` is normally the fp64 oracle's.
+
+    rel_err divides by the largest entry of the whole array; on mixed problems a few Poisson entries set it, and a
+    Gaussian column or a quiet row can be wrong by a third and pass.  Here every element answers for the rounding of its
+    own terms.  tau = FACTOR_TAU = LAYER_TAU = 2e-5, not fitted to any device output: the split kernels' gradient products
+    run on bf16 hi + mid of both operands, 16 significant bits each, so each operand is rounded by at most 2^-17 and the
+    product by 1.5e-5 of sum |G| |X|; the exact kernel's f32 roundings are two orders below
+    (tests/test_host_factor_check.py)."""
+    s = factor_scales(p) if scales is None else scales
+    worst = {}
+    for k in ("X", "Y"):
+        if k not in got:
+            continue
+        a, b = np.asarray(got[k], np.float64), np.asarray(want[k], np.float64)
+        assert a.shape == b.shape == s[k].shape, (k, a.shape, b.shape, s[k].shape)
+        if not np.isfinite(a).all():
+            worst[k] = np.inf
+        else:
+            worst[k] = float(np.max(np.abs(a - b) / (tau * s[k] + 1e-30))) if a.size else 0.0
+    return worst
+
+
+def factor_worst(p, got, want, tau=FACTOR_TAU, scales=None):
+    """One line per gradient present in `got` on its worst element: k, the row (gX) or column (gY), the ratio; for a
+    column its noise kind and feature view; for either the 32 x 32 tile (row block, column block) of D whose removal
+    would explain most of the deviation, and whether that tile is all-finite (the packed epilogue) or not."""
+    s = factor_scales(p) if scales is None else scales
+    D = p["D"]
+    M, N = D.shape
+    X, Y = np.asarray(p["X"], np.float64), np.asarray(p["Y"], np.float64)
+    lines = []
+    for w in ("X", "Y"):
+        if w not in got:
+            continue
+        a, b = np.asarray(got[w], np.float64), np.asarray(want[w], np.float64)
+        ratio = np.where(np.isfinite(a), np.abs(a - b), np.inf) / (tau * s[w] + 1e-30)
+        k, n = np.unravel_index(int(np.argmax(ratio)), ratio.shape)
+        txt = f"g{w}[k={k}, {'row' if w == 'X' else 'column'}={n}]: got {a[k, n]:.6g}, want {b[k, n]:.6g}, " \
+              f"ratio {ratio[k, n]:.3g} of tau * scale = {tau * s[w][k, n]:.3g}"
+        if w == "X":
+            e = entry_scales(p)
+            term = e["sd"][n] * e["g"][n] * Y[k]                               # the N terms of gX[k, n]
+            part = np.add.reduceat(term, np.arange(0, N, 32))
+            tj = int(np.argmin(np.abs(part - (b[k, n] - a[k, n]))))
+            ti = n // 32
+        else:
+            e = entry_scales(p, n, n + 1)
+            term = e["sd"][:, 0] * e["g"][:, 0] * X[k]                         # the M terms of gY[k, n]
+            part = np.add.reduceat(term, np.arange(0, M, 32))
+            ti = int(np.argmin(np.abs(part - (b[k, n] - a[k, n]))))
+            tj = n // 32
+            kind = next((kd for (s0, e0), kd in zip(p["noise_ranges"], p["noise_kinds"]) if s0 - 1 <= n < e0), "?")
+            view = next((v for v, (s0, e0) in enumerate(p.get("view_ranges", [])) if s0 - 1 <= n < e0), None)
+            bview = next((v for v, bv in enumerate(p["batch_views"]) if bv["start1"] - 1 <= n < bv["stop1"]), None)
+            txt += f"; noise {kind}, view {view}, batch view {bview}"
+        tile = D[32 * ti:32 * ti + 32, 32 * tj:32 * tj + 32]
+        txt += f"; tile (row block {ti}, column block {tj}) fits a missing tile best and is " \
+               f"{'all-finite' if np.isfinite(tile).all() else 'masked'}"
+        lines.append(txt)
+    return "\n".join(lines)

@@ -10,7 +10,8 @@ gathers at KB = 3 and 4, 255 and 256 batches, column chunks, workgroups that wal
 set_batch_views on a live context.
 
 Every case asserts the family, bmode, slots and split-launch count that batch_cases.expected_batch_path restates from the
-selection rules, compares the loss and the gradients with the oracle at the tolerances of tests/test_gpu_parity.py, runs
+selection rules, compares the loss and the gradients with the oracle at the tolerances of tests/test_gpu_parity.py (the
+max-norm at GRAD_TOL, and every element at the rounding of its own terms: factor_gate, one FACTOR_CHECK line), runs
 the pass twice for the same bits and prints one BATCH_EDGE line with its relative errors.  tests/test_batch_cases.py
 holds the condition that makes the comparison mean something: on every problem here one row in the wrong batch, one
 unbatched row in batch 0 or one view boundary off by a column moves gX or gY by at least 10 GRAD_TOL.
@@ -20,7 +21,7 @@ import pytest
 
 import batch_cases as bc
 from problems import rel_err, to_context
-from test_gpu_parity import GRAD_TOL, LOSS_RTOL, grads_of
+from test_gpu_parity import GRAD_TOL, LOSS_RTOL, factor_gate, grads_of
 from test_gpu_split_bf16 import bf16_round
 
 pytestmark = pytest.mark.gpu
@@ -53,7 +54,8 @@ def one_pass(ctx, p, path, launches=1):
     return loss, g, exp
 
 
-def check_oracle(name, go, loss, g):
+def check_oracle(ctx, p, name, go, loss, g):
+    """ctx: the context that ran the pass (or its kernel family, where the context is closed)."""
     errs = {}
     for w in ("X", "Y"):
         if w in g:
@@ -63,6 +65,7 @@ def check_oracle(name, go, loss, g):
     assert abs(loss - go["data_loss"]) <= LOSS_RTOL * abs(go["data_loss"]) + 1e-6, (loss, go["data_loss"])
     for w, e in errs.items():
         assert e <= GRAD_TOL, (w, e)
+    factor_gate(ctx, p, g, go, scales=bc.scales_of(p))
 
 
 def run_case(ctx, name, p, path, family=None, BM=None, bmode=None):
@@ -70,7 +73,7 @@ def run_case(ctx, name, p, path, family=None, BM=None, bmode=None):
     loss, g, exp = one_pass(ctx, p, path)
     for got, want in zip(exp, (family, BM, bmode)):
         assert want is None or got == want, (exp, family, BM, bmode)      # what the case was built to reach
-    check_oracle(f"{name}-{bc.path_id(path)}", bc.oracle_of(p), loss, g)
+    check_oracle(ctx, p, f"{name}-{bc.path_id(path)}", bc.oracle_of(p), loss, g)
 
 
 # ---- 1. exactly 15 and exactly 16 batches in a panel ----------------------------------------------------------------
@@ -130,7 +133,7 @@ def test_view_seams_with_bf16_stored_data(ctx, path):
     try:
         loss, g, exp = one_pass(ctx, p, path)
         assert exp[:3] == (fam, BM, 1), exp
-        check_oracle(f"view_seams_bf16-{bc.path_id(path)}", bc.oracle_of(p), loss, g)
+        check_oracle(ctx, p, f"view_seams_bf16-{bc.path_id(path)}", bc.oracle_of(p), loss, g)
     finally:
         ctx.set_data(p["D"])            # back to f32 storage for the tests that follow
 
@@ -165,7 +168,7 @@ def test_view_seams_in_three_column_chunks(ctx, path):
     finally:
         ctx.comm_set_chunks(0)
     assert exp[:3] == (fam, BM, 1), exp
-    check_oracle(f"view_seams161_chunks3-{bc.path_id(path)}", bc.oracle_of(p), loss, g)
+    check_oracle(ctx, p, f"view_seams161_chunks3-{bc.path_id(path)}", bc.oracle_of(p), loss, g)
 
 
 # ---- 6. workgroups that walk pieces of several row panels -----------------------------------------------------------
@@ -196,7 +199,7 @@ def test_multi_piece_walks_restage_the_slot_map(ctx, monkeypatch, path, reserve)
     assert pieces > grid, (pieces, grid)
     loss, g, exp = one_pass(ctx, p, path)
     assert exp == (fam, BM, 1, 64), exp
-    check_oracle(f"walk-{bc.path_id(path)}-reserve{reserve}", bc.oracle_of(p), loss, g)
+    check_oracle(ctx, p, f"walk-{bc.path_id(path)}-reserve{reserve}", bc.oracle_of(p), loss, g)
 
 
 # ---- 7. the three slot caches follow the rows -----------------------------------------------------------------------
@@ -235,4 +238,4 @@ def test_slot_caches_follow_set_batch_views_on_a_live_context(pkg):
         assert loss == loss_f, (gname, loss, loss_f)
         for w in g:
             assert np.array_equal(g[w], g_f[w]), f"g{w} of the {gname} pass differs from a fresh context's"
-    check_oracle("slot_caches-bf16x3-k48-both", bc.oracle_of(C), *got[-1])
+    check_oracle(want_fam["both"][0], C, "slot_caches-bf16x3-k48-both", bc.oracle_of(C), *got[-1])

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 from problems import make_problem, rel_err, shard_problem, to_context, to_oracle
+from test_gpu_parity import factor_gate
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -84,6 +85,7 @@ def test_chunked_data_pass_matches_unchunked_and_oracle(ctx, precision, chunks):
         r0, X0, Y0 = _fit(ctx, p, update_X=True, update_Y=True)
         ctx.comm_set_chunks(chunks)
         l1, gX1, gY1 = _grads(ctx, p)
+        fam1 = ctx.last_kernel()
         r1, X1, Y1 = _fit(ctx, p, update_X=True, update_Y=True)
         assert ctx.comm_info()["n_chunks"] == chunks
         r2, X2, Y2 = _fit(ctx, p, update_X=True, update_Y=True)
@@ -93,6 +95,10 @@ def test_chunked_data_pass_matches_unchunked_and_oracle(ctx, precision, chunks):
     # one data pass: same loss and gradients up to the order the row panels / pieces are summed in
     assert abs(l1 - l0) <= 1e-7 * abs(l0)
     assert rel_err(gX1, gX0) <= 2e-6 and rel_err(gY1, gY0) <= 2e-6, (rel_err(gX1, gX0), rel_err(gY1, gY0))
+    md = to_oracle(p)                       # the chunked pass against the oracle's data gradients, element by element
+    md.m.n_xreg = 0
+    md.m.n_yreg = 0
+    factor_gate(fam1, p, dict(X=gX1, Y=gY1), md.loss_and_grads(update_X=True, update_Y=True)[1])
     np.testing.assert_array_equal(r2["loss"], r1["loss"])       # run to run: bitwise
     np.testing.assert_array_equal(X2, X1)
     np.testing.assert_array_equal(Y2, Y1)

@@ -12,8 +12,8 @@ counter is asserted):
 import numpy as np
 import pytest
 
-from problems import make_problem, rel_err, to_context, to_oracle
-from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, grads_of
+from problems import factor_scales, make_problem, rel_err, to_context, to_oracle
+from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, factor_gate, grads_of
 from test_gpu_split_bf16 import bf16_round
 
 pytestmark = pytest.mark.gpu
@@ -49,6 +49,7 @@ def test_config4_loss_and_gradients_match_oracle(sctx, shape):
         assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]), (loss, gd["data_loss"])
         assert rel_err(g["X"], gd["X"]) <= GRAD_TOL, rel_err(g["X"], gd["X"])
         assert rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, rel_err(g["Y"], gd["Y"])
+        factor_gate(ctx, p, g, gd)
         # with the regularizers kept: total loss, and total gradients recovered from Adam's first moment after one step at lr -> 0
         ctx.set_optimizer("adam", lr=1e-30, beta1=0.9)
         o = ctx.make_opts(update_X=True, update_Y=True)
@@ -188,6 +189,7 @@ def test_sb8_f16_prescale_handles_operand_ranges(sctx, sx, sy):
     _, gd = m.loss_and_grads(update_X=True, update_Y=True)
     assert np.isfinite(loss) and abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]), (loss, gd["data_loss"])
     assert rel_err(g["X"], gd["X"]) <= GRAD_TOL and rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, (rel_err(g["X"], gd["X"]), rel_err(g["Y"], gd["Y"]))
+    factor_gate(ctx, p, g, gd)
 
 
 def test_sb8_column_chunks_and_kernel_selection(sctx):
@@ -237,6 +239,7 @@ def test_k64_both_gradients_run_sb8_and_sb2_agrees(sctx, name):
     m.m.n_xreg = 0
     m.m.n_yreg = 0
     _, gd = m.loss_and_grads(update_X=True, update_Y=True)
+    scales = factor_scales(p)
     for env, family in ((None, 8), ("4", 2)):
         if env is not None:
             os.environ["PMF_SB8"] = env
@@ -247,6 +250,7 @@ def test_k64_both_gradients_run_sb8_and_sb2_agrees(sctx, name):
         assert ctx.last_kernel() == family, (ctx.last_kernel(), family)
         assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]) + 1e-6, (family, loss, gd["data_loss"])
         assert rel_err(g["X"], gd["X"]) <= GRAD_TOL and rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, (family, rel_err(g["X"], gd["X"]), rel_err(g["Y"], gd["Y"]))
+        factor_gate(ctx, p, g, gd, scales=scales, tag=f":family{family}")
     assert ctx.get_precision()[1] == n0 + 2
 
 
@@ -264,6 +268,7 @@ def test_k64_more_batch_views_than_the_tall_panel_holds_fall_back_to_sb2(sctx):
     _, gd = m.loss_and_grads(update_X=True, update_Y=True)
     assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]) + 1e-6
     assert rel_err(g["X"], gd["X"]) <= GRAD_TOL and rel_err(g["Y"], gd["Y"]) <= GRAD_TOL
+    factor_gate(ctx, p, g, gd)
     p5 = make_problem(seed=61, M=1500, N=360, K=64, n_views=5, batch_views=5, n_batches=4, nan_frac=0.05, col_params=True, scale=0.5)
     to_context(p5, ctx)
     grads_of(ctx, p5, update_X=True, update_Y=True)
@@ -304,6 +309,7 @@ def test_noise_tile_weights_change_the_split_not_the_result(sctx):
     m.m.n_xreg = 0
     m.m.n_yreg = 0
     _, gd = m.loss_and_grads(update_X=True, update_Y=True)
+    scales = factor_scales(p)
     res = []
     for wb, we in ((None, None), ("16", "0"), ("48", "20")):
         for k, v in (("PMF_W_BERN", wb), ("PMF_W_BATCH", we)):
@@ -320,6 +326,7 @@ def test_noise_tile_weights_change_the_split_not_the_result(sctx):
         assert ctx.last_kernel() == 8
         assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"])
         assert rel_err(g["X"], gd["X"]) <= GRAD_TOL and rel_err(g["Y"], gd["Y"]) <= GRAD_TOL
+        factor_gate(ctx, p, g, gd, scales=scales, tag=f":w{wb}-{we}")
         res.append((loss, g))
     for loss, g in res[1:]:
         assert abs(loss - res[0][0]) <= 1e-6 * abs(res[0][0])

@@ -13,8 +13,8 @@ Every case runs in f32 and must have taken the exact kernel (family 0).
 import numpy as np
 import pytest
 
-from problems import make_problem, rel_err, to_context, to_oracle
-from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, grads_of
+from problems import factor_scales, make_problem, rel_err, to_context, to_oracle
+from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, factor_gate, grads_of
 
 pytestmark = pytest.mark.gpu
 
@@ -27,11 +27,12 @@ def eval_both(ctx, p):
     return loss, g
 
 
-def check_oracle(go, loss, g):
+def check_oracle(ctx, p, go, loss, g, scales=None):
     assert abs(loss - go["data_loss"]) <= LOSS_RTOL * abs(go["data_loss"]) + 1e-6, (loss, go["data_loss"])
     for w in ("X", "Y"):
         assert np.isfinite(g[w]).all(), f"non-finite g{w}"
         assert rel_err(g[w], go[w]) <= GRAD_TOL, (w, rel_err(g[w], go[w]))
+    factor_gate(ctx, p, g, go, scales=scales)
 
 
 @pytest.mark.parametrize("M,N", [(1, 1), (257, 33), (511, 95), (289, 161)])
@@ -43,7 +44,7 @@ def test_panel_and_tile_edges_match_oracle(ctx, K, M, N):
     to_context(p, ctx)
     loss, g = eval_both(ctx, p)
     _, go = to_oracle(p).loss_and_grads(**BOTH)
-    check_oracle(go, loss, g)
+    check_oracle(ctx, p, go, loss, g)
 
 
 @pytest.fixture(scope="module")
@@ -53,17 +54,17 @@ def walk():
     including the second piece that covers tiles before the first piece's start.  The oracle's answer is computed once."""
     p = make_problem(M=2049, N=2048, K=64, seed=41, col_params=True, weights=True, nan_frac=0.02)
     _, go = to_oracle(p).loss_and_grads(**BOTH)
-    return p, go
+    return p, go, factor_scales(p)
 
 
 @pytest.mark.parametrize("reserve", [None, "128"])
 def test_multi_piece_walks_match_oracle_and_repeat_bitwise(ctx, monkeypatch, walk, reserve):
-    p, go = walk
+    p, go, scales = walk
     if reserve:
         monkeypatch.setenv("PMF_RESERVE_CUS", reserve)
     to_context(p, ctx)
     l1, g1 = eval_both(ctx, p)
-    check_oracle(go, l1, g1)
+    check_oracle(ctx, p, go, l1, g1, scales)
     l2, g2 = eval_both(ctx, p)
     assert l1 == l2
     assert np.array_equal(g1["X"], g2["X"]) and np.array_equal(g1["Y"], g2["Y"])
@@ -77,7 +78,7 @@ def test_general_epilogues_feed_the_cross_wave_gemm(ctx):
     loss, g = eval_both(ctx, p)
     assert ctx.last_path()["bmode"] == 1
     _, go = to_oracle(p).loss_and_grads(**BOTH)
-    check_oracle(go, loss, g)
+    check_oracle(ctx, p, go, loss, g)
 
 
 @pytest.mark.parametrize("reserve", [None, "128"])
@@ -85,7 +86,7 @@ def test_slab_path_and_cross_wave_path_agree(ctx, monkeypatch, walk, reserve):
     """PMF_XGEMM3=0 against the default on one context and one data set.  Nothing on the way to the loss or to gX differs:
     bit-equal.  gY is one 256-term MFMA chain pair per element instead of eight 32-term partials added in wave order:
     f32 re-association, bounded at 1e-5 of the largest entry (an order below GRAD_TOL)."""
-    p, go = walk
+    p, go, scales = walk
     if reserve:
         monkeypatch.setenv("PMF_RESERVE_CUS", reserve)
     to_context(p, ctx)
@@ -99,8 +100,8 @@ def test_slab_path_and_cross_wave_path_agree(ctx, monkeypatch, walk, reserve):
     assert np.array_equal(g_old["X"], g_new["X"])
     assert not np.array_equal(g_old["Y"], g_new["Y"]), "the switch changed nothing: both passes took one path"
     assert rel_err(g_new["Y"], g_old["Y"]) <= 1e-5, rel_err(g_new["Y"], g_old["Y"])
-    check_oracle(go, l_old, g_old)
-    check_oracle(go, l_new, g_new)
+    check_oracle(ctx, p, go, l_old, g_old, scales)
+    check_oracle(ctx, p, go, l_new, g_new, scales)
 
 
 @pytest.mark.parametrize("opt", ["adagrad", "adam"])

@@ -24,7 +24,7 @@ import step_ref as sr
 from impute_ref import BATCH, KEEP, LINK, impute_tol, worst_ratio
 from problems import LAYER_TAU, layer_check, rel_err
 from test_gpu_batch_edges import one_pass
-from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, grads_of
+from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, factor_gate, grads_of
 from test_gpu_split_bf16 import bf16_round
 
 pytestmark = pytest.mark.gpu
@@ -33,7 +33,7 @@ PATH_PARAMS = [pytest.param(path, id=bc.path_id(path)) for path in bc.PATHS]
 INF = np.inf
 
 
-def check_ref(tag, ref, loss, g):
+def check_ref(ctx, p, tag, ref, loss, g):
     errs = {}
     for w in ("X", "Y"):
         if w in g:
@@ -44,6 +44,7 @@ def check_ref(tag, ref, loss, g):
     assert abs(loss - ref["data_loss"]) <= LOSS_RTOL * abs(ref["data_loss"]) + 1e-6, (loss, ref["data_loss"])
     for w, e in errs.items():
         assert e <= GRAD_TOL, (w, e)
+    factor_gate(ctx, p, g, ref, scales=hr.scales_of(p))
 
 
 def data_pass(ctx, p, path):
@@ -78,7 +79,7 @@ def test_every_fused_family_matches_the_reference(ctx, path, name, batch):
     p = hr.layout(name, path[1], batch)
     hr.to_context(p, ctx)
     loss, g = data_pass(ctx, p, path)
-    check_ref(f"{name}-{'batch' if batch else 'plain'}-{bc.path_id(path)}", hr.reference_of(p), loss, g)
+    check_ref(ctx, p, f"{name}-{'batch' if batch else 'plain'}-{bc.path_id(path)}", hr.reference_of(p), loss, g)
 
 
 @pytest.mark.parametrize("path", PATH_PARAMS)
@@ -90,7 +91,7 @@ def test_layout_a_with_bf16_stored_data(ctx, path):
     ctx.set_data(p["D"], store="bf16")
     try:
         loss, g = data_pass(ctx, p, path)
-        check_ref(f"A-batch-bf16-{bc.path_id(path)}", hr.reference(p), loss, g)
+        check_ref(ctx, p, f"A-batch-bf16-{bc.path_id(path)}", hr.reference(p), loss, g)
     finally:
         ctx.set_data(p["D"])            # back to f32 storage for the tests that follow
 
@@ -168,13 +169,13 @@ def test_set_noise_thresholds_on_a_live_context(ctx, pkg):
     hr.to_context(p, ctx)
     assert np.array_equal(ctx.get_noise_thresholds(), hr.thresholds_of(p).astype(np.float32), equal_nan=True)
     loss1, g1 = grads_of(ctx, p, **bc.BOTH)
-    check_ref("live-before", hr.reference_of(p), loss1, g1)
+    check_ref(ctx, p, "live-before", hr.reference_of(p), loss1, g1)
     q = copy.copy(p)
     q["noise_thr"] = [p["noise_thr"][0], (0.3, INF, INF), (-INF, -0.2, 0.9)]
     ctx.set_noise_thresholds(p["noise_ranges"][1:], q["noise_thr"][1:])
     loss2, g2 = grads_of(ctx, p, **bc.BOTH)
     assert loss2 != loss1 and not np.array_equal(g2["Y"], g1["Y"])
-    check_ref("live-after", hr.reference(q), loss2, g2)
+    check_ref(ctx, q, "live-after", hr.reference(q), loss2, g2)
     assert np.array_equal(ctx.get_noise_thresholds(), hr.thresholds_of(q).astype(np.float32), equal_nan=True)
     with pytest.raises(pkg.PMFError, match="t0 <= t1 <= t2"):
         ctx.set_noise_thresholds([(41, 50)], [(1.0, 0.5, INF)])

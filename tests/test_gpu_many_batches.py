@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from problems import make_problem, rel_err, to_context, to_oracle
-from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, grads_of
+from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, factor_gate, grads_of
 
 pytestmark = pytest.mark.gpu
 
@@ -44,6 +44,7 @@ def _check_grads(ctx, p, variant, slots):
     assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]) + 1e-6, (loss, gd["data_loss"])
     assert rel_err(g["X"], gd["X"]) <= GRAD_TOL, rel_err(g["X"], gd["X"])
     assert rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, rel_err(g["Y"], gd["Y"])
+    factor_gate(ctx, p, g, gd)
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -83,6 +84,7 @@ def test_many_batches_single_factor_gradient(ctx, which):
     _, go = m.loss_and_grads(**flags)
     assert abs(loss - go["data_loss"]) <= LOSS_RTOL * abs(go["data_loss"]) + 1e-6
     assert rel_err(g[which], go[which]) <= GRAD_TOL
+    factor_gate(ctx, p, g, go)
 
 
 @pytest.mark.parametrize("name,layer_path", [("sorted40_k16", 1), ("random40_k64", 1), ("sorted40_k128", 1),

@@ -1,19 +1,23 @@
 """GPU parity tests: the HIP path (through the C ABI, include/pmf_hip.h) against the fp64 CPU oracle on the
 same seeded inputs, plus the reference's known-answer vectors and size-independent properties at full size.
 
-Tolerances (north-star: "within a stated fp32 tolerance"): the HIP path computes in fp32 (exact-f32 MFMA,
-f32 elementwise, f32 atomics); against the fp64 oracle we require
+Tolerances (north-star: "within a stated fp32 tolerance"): the HIP path computes in fp32 (exact-f32 MFMA, f32
+elementwise; every sum in a fixed order -- private per-workgroup gY slabs and per-piece gX slots reduced by k_gy_reduce /
+k_gx_reduce, fixed-order loss partials: the library has no float atomics); against the fp64 oracle we require
     loss            : relative 2e-5
     gradients       : max-abs error <= 2e-4 * max|gradient|   (K <= 128 f32 dot products, a few thousand f32 adds)
+                      and, per element of gX and gY, |error| <= FACTOR_TAU * (the sum of the magnitudes of that element's
+                      own terms): problems.factor_check through factor_gate below
     fitted factors  : max-abs error <= 2e-3 * max|param| after 10 epochs (error compounds through AdaGrad)
 """
 import json
+import os
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from problems import make_problem, rel_err, to_context, to_oracle
+from problems import factor_check, factor_scales, factor_worst, make_problem, rel_err, to_context, to_oracle
 
 pytestmark = pytest.mark.gpu
 GOLD = Path(__file__).resolve().parent / "golden"
@@ -38,6 +42,20 @@ def grads_of(ctx, p, **flags):
         g["theta"] = [ctx.get_grad("theta", v) for v in range(len(p["batch_views"]))]
         g["logdelta"] = [ctx.get_grad("logdelta", v) for v in range(len(p["batch_views"]))]
     return loss, g
+
+
+def factor_gate(ctx, p, g, want, scales=None, tag=""):
+    """The per-element check of the factor gradients in `g` (problems.factor_check at FACTOR_TAU) against `want`, the fp64
+    reference of problem `p`: prints one FACTOR_CHECK line with the kernel family of the context's last pass and the worst
+    ratio of each gradient, and fails above 1 naming the worst element.  ctx: the context, or the family itself where the
+    context is gone; scales: factor_scales(p) where a caller shares them between passes."""
+    s = factor_scales(p) if scales is None else scales
+    worst = factor_check(p, g, want, scales=s)
+    tid = os.environ.get("PYTEST_CURRENT_TEST", "-").split(" ")[0] + tag
+    print(f"FACTOR_CHECK {tid} family={ctx if isinstance(ctx, int) else ctx.last_kernel()} " +
+          " ".join(f"{w}={worst[w]:.4f}" if w in worst else f"{w}=-" for w in ("X", "Y")))
+    assert worst and max(worst.values()) <= 1.0, factor_worst(p, g, want, scales=s)
+    return worst
 
 
 def test_batch_array_known_answers_on_device(ctx):
@@ -111,6 +129,7 @@ def test_loss_and_factor_gradients_match_oracle(ctx, name):
     _, gd = m.loss_and_grads(update_X=True, update_Y=True)
     assert rel_err(g["X"], gd["X"]) <= GRAD_TOL, rel_err(g["X"], gd["X"])
     assert rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, rel_err(g["Y"], gd["Y"])
+    factor_gate(ctx, p, g, gd)
 
 
 @pytest.mark.parametrize("which", ["X", "Y"])
@@ -128,6 +147,7 @@ def test_single_factor_gradient_matches_oracle(ctx, name, which):
     _, go = m.loss_and_grads(**flags)
     assert abs(loss - go["data_loss"]) <= LOSS_RTOL * abs(go["data_loss"]) + 1e-6
     assert rel_err(g[which], go[which]) <= GRAD_TOL
+    factor_gate(ctx, p, g, go)
 
 
 @pytest.mark.parametrize("name", ["mixed_batch_nan", "poisson_batch", "ragged_k32"])
@@ -304,6 +324,7 @@ def test_all_finite_tiles_and_masked_tiles_agree_with_oracle(ctx):
     assert abs(loss - go["data_loss"]) <= LOSS_RTOL * abs(go["data_loss"])
     assert rel_err(g["X"], go["X"]) <= GRAD_TOL
     assert rel_err(g["Y"], go["Y"]) <= GRAD_TOL
+    factor_gate(ctx, p, g, go, tag=":masked")
     # changing D must refresh the tile flags: make every entry finite again and compare once more
     p["D"] = np.where(np.isfinite(D), D, 0.25).astype(np.float32)
     to_context(p, ctx)
@@ -314,6 +335,7 @@ def test_all_finite_tiles_and_masked_tiles_agree_with_oracle(ctx):
     _, go2 = m2.loss_and_grads(update_X=True, update_Y=True)
     assert abs(loss2 - go2["data_loss"]) <= LOSS_RTOL * abs(go2["data_loss"])
     assert rel_err(g2["Y"], go2["Y"]) <= GRAD_TOL
+    factor_gate(ctx, p, g2, go2, tag=":all-finite")
 
 
 def test_loss_and_grad_Y_are_bitwise_reproducible(ctx):
@@ -400,6 +422,7 @@ def test_blocks_of_missing_samples_match_oracle(ctx, K):
     assert abs(loss - go["data_loss"]) <= LOSS_RTOL * abs(go["data_loss"])
     assert rel_err(g["X"], go["X"]) <= GRAD_TOL
     assert rel_err(g["Y"], go["Y"]) <= GRAD_TOL
+    factor_gate(ctx, p, g, go)
     assert np.all(g["X"][:, 300:333] == 0.0)                      # unobserved samples get no data gradient
     to_context(p, ctx)
     ctx.set_optimizer("adagrad", lr=0.05)
@@ -431,3 +454,4 @@ def test_multi_rank_grid_with_reserved_cus_matches_oracle(ctx, monkeypatch, prec
     _, gd = m.loss_and_grads(update_X=True, update_Y=True)
     assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]) + 1e-6
     assert rel_err(g["X"], gd["X"]) <= GRAD_TOL and rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, (rel_err(g["X"], gd["X"]), rel_err(g["Y"], gd["Y"]))
+    factor_gate(ctx, p, g, gd)

@@ -12,7 +12,7 @@ import pytest
 
 from problems import make_problem, rel_err, to_context, to_oracle
 import test_gpu_parity as exact_tests
-from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, grads_of
+from test_gpu_parity import FIT_TOL, GRAD_TOL, LOSS_RTOL, factor_gate, grads_of
 
 pytestmark = pytest.mark.gpu
 
@@ -68,6 +68,7 @@ def test_split_bf16_loss_and_gradients_match_oracle(sctx, name):
     assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]) + 1e-6, (loss, gd["data_loss"])
     assert rel_err(g["X"], gd["X"]) <= GRAD_TOL, rel_err(g["X"], gd["X"])
     assert rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, rel_err(g["Y"], gd["Y"])
+    factor_gate(ctx, p, g, gd)
 
 
 @pytest.mark.parametrize("opt", ["adagrad", "adam"])
@@ -134,6 +135,7 @@ def test_split_bf16_falls_back_to_exact_kernel_outside_its_scope(sctx):
         m.m.n_yreg = 0
         _, gd = m.loss_and_grads(update_X=True, update_Y=True)
         assert rel_err(g["Y"], gd["Y"]) <= GRAD_TOL
+        factor_gate(ctx, p, g, gd, tag=f":k{case['K']}")
     assert ctx.get_precision()[1] == n0
 
 
@@ -155,6 +157,7 @@ def test_split_bf16_single_factor_gradient_matches_oracle(sctx, name, which):
     _, go = m.loss_and_grads(**flags)
     assert abs(loss - go["data_loss"]) <= LOSS_RTOL * abs(go["data_loss"]) + 1e-6
     assert rel_err(g[which], go[which]) <= GRAD_TOL, rel_err(g[which], go[which])
+    factor_gate(ctx, p, g, go)
 
 
 def test_split_bf16_headline_size_properties(sctx):
@@ -200,6 +203,7 @@ def test_split_bf16_k128_loss_and_gradients_match_oracle(sctx, name):
     assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]) + 1e-6, (loss, gd["data_loss"])
     assert rel_err(g["X"], gd["X"]) <= GRAD_TOL, rel_err(g["X"], gd["X"])
     assert rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, rel_err(g["Y"], gd["Y"])
+    factor_gate(ctx, p, g, gd)
 
 
 @pytest.mark.parametrize("which", ["X", "Y"])
@@ -217,6 +221,7 @@ def test_split_bf16_k128_single_factor_gradient_matches_oracle(sctx, name, which
     _, go = m.loss_and_grads(**flags)
     assert abs(loss - go["data_loss"]) <= LOSS_RTOL * abs(go["data_loss"]) + 1e-6
     assert rel_err(g[which], go[which]) <= GRAD_TOL, rel_err(g[which], go[which])
+    factor_gate(ctx, p, g, go)
 
 
 @pytest.mark.parametrize("opt", ["adagrad", "adam"])
@@ -269,6 +274,7 @@ def test_bf16_stored_data_matches_oracle_on_the_rounded_matrix(sctx, name):
     assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]) + 1e-6, (loss, gd["data_loss"])
     assert rel_err(g["X"], gd["X"]) <= GRAD_TOL, rel_err(g["X"], gd["X"])
     assert rel_err(g["Y"], gd["Y"]) <= GRAD_TOL, rel_err(g["Y"], gd["Y"])
+    factor_gate(ctx, p, g, gd)
     # the unrounded matrix through the same call gives the same device bytes (the library rounds to nearest even)
     st = ctx.stats(use_factors=True)
     so = m.stats(use_factors=True)
@@ -319,6 +325,7 @@ def test_bf16_stored_data_through_the_exact_kernel(ctx, name):
         _, gd = m.loss_and_grads(update_X=True, update_Y=True)
         assert abs(loss - gd["data_loss"]) <= LOSS_RTOL * abs(gd["data_loss"]) + 1e-6, (loss, gd["data_loss"])
         assert rel_err(g["X"], gd["X"]) <= GRAD_TOL and rel_err(g["Y"], gd["Y"]) <= GRAD_TOL
+        factor_gate(ctx, p, g, gd)
         if p["batch_views"]:
             lossl, gl = grads_of(ctx, p, update_col_layers=True)
             ml = to_oracle(p)
