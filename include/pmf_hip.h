@@ -414,6 +414,48 @@ int pmf_impute_device(pmf_ctx *ctx, int flags, int64_t row_start1, int64_t row_s
 int pmf_impute_entries(pmf_ctx *ctx, int flags, int64_t n, const int64_t *rows1, const int64_t *cols1, float *out_host);
 int pmf_debug_impute_offset(int64_t row, int64_t col, int64_t ld, int64_t *offset);
 
+/* remove_batch_effect(model, Z) (src/remove_batch_effect.jl:3-16): the data with the fitted batch effects taken out, from
+ * the context's CURRENT column parameters and batch views.  SELF-SPECIFIED (Deviation 3): the
+ * reference's body reads fields that no longer exist and inverts an older layer order; this inverts the order the library
+ * implements everywhere (src/layers.jl:240-253: z = (a sigma_j) delta_v[b,j] + mu_j + theta_v[b,j]).  Per entry with input
+ * v, b = the batch of row i in column j's view:
+ *     column in no batch view, or row in no batch (batch_of_row = -1)  ->  v, bit for bit
+ *     kind 3 (squared hinge: class labels, there is no link)           ->  v, bit for bit
+ *     v not finite (missing)                                           ->  NaN
+ *     else  l = link(v) ; l' = ((l - theta_v[b,j]) - mu_j) / delta_v[b,j] + mu_j ; out = invlink(l')      (f32, in that order;
+ *           the division is a multiplication by the hardware reciprocal of delta, 1 ulp, fused with the last addition)
+ *           normal: identity ; bernoulli: log v - log(1 - v) in, 1 / (1 + e^-l') out (0 and 1 come back exactly) ;
+ *           poisson: log v in, e^l' out (0 comes back as 0) ; a value outside a link's domain gives NaN
+ * PMF_DEBATCH_LINK: input and output are both in link space; every column, kind 3 included, uses the identity link.
+ * PMF_DEBATCH_FILL_MISSING: a non-finite input is replaced by the batch-free prediction, exactly pmf_impute with flags 0
+ * (PMF_IMPUTE_LINK when PMF_DEBATCH_LINK is set): the prediction is written first, the observed entries over it.
+ *   pmf_remove_batch_effect         : local rows row_start1..row_stop1 (1-based, inclusive) x all N columns.  Z_host points at
+ *                         the first row of the range, column-major with leading dimension ldz >= rows; Z_host = NULL (ldz
+ *                         ignored): the data matrix resident on the device is the input (bf16-rounded under PMF_STORE_BF16).
+ *                         out_host: column-major, leading dimension ld >= rows; elements between the rows of a column are
+ *                         not written.  Z_host == out_host with ldz == ld (in place) is legal.  Computed in row chunks of
+ *                         whole 32-row blocks through the staging buffer of pmf_impute (at most 256 MiB;
+ *                         PMF_DEBATCH_CHUNK_ROWS=n, read at every call, overrides the chunk height).
+ *   pmf_remove_batch_effect_device  : the same between DEVICE matrices (Z_device = NULL: the resident data), one launch (two with
+ *                         PMF_DEBATCH_FILL_MISSING), no staging.  In place is legal without PMF_DEBATCH_FILL_MISSING; any
+ *                         other overlap of input and output is refused.
+ *   pmf_remove_batch_effect_entries : the corrected values at n listed entries (rows1[e], cols1[e], 1-based; duplicates are
+ *                         legal) of values[e], or of the resident data with values = NULL.  n = 0 succeeds and does nothing.
+ * An entry's value does not depend on the row range, the chunking, ld / ldz, the input's source (for the same f32 value) or
+ * what the context ran before.  The calls change nothing a later pmf_fit reads.  LOCAL ROWS ONLY: no communicator traffic.
+ * Data and factors must have been set, as for pmf_impute.  Refused before anything is launched (the context stays usable):
+ * a null output, unknown flag bits, an empty or out-of-range row range, ld or ldz below the row count,
+ * PMF_DEBATCH_FILL_MISSING passed to pmf_remove_batch_effect_entries, an entry outside 1..M x 1..N, no resident data when
+ * the input is NULL. */
+#define PMF_DEBATCH_LINK 1          /* input and output in link space: the identity link for every column */
+#define PMF_DEBATCH_FILL_MISSING 2  /* missing entries take pmf_impute's batch-free prediction instead of NaN */
+int pmf_remove_batch_effect(pmf_ctx *ctx, int flags, int64_t row_start1, int64_t row_stop1, const float *Z_host, int64_t ldz,
+                            float *out_host, int64_t ld);
+int pmf_remove_batch_effect_device(pmf_ctx *ctx, int flags, int64_t row_start1, int64_t row_stop1, const float *Z_device,
+                                   int64_t ldz, float *out_device, int64_t ld);
+int pmf_remove_batch_effect_entries(pmf_ctx *ctx, int flags, int64_t n, const int64_t *rows1, const int64_t *cols1,
+                                    const float *values, float *out_host);
+
 /* Masked column statistics for the closed-form initialisers that sit between the GD stages (local rows only; a
  * multi-GPU host sums them across ranks).  All outputs are optional (NULL = not wanted).
  *   col_n[N]        MF.column_nonnan                         (src/fit.jl:140, 447; src/regularizers.jl:765)

@@ -21,6 +21,7 @@ OPT = {"adagrad": 0, "adam": 1}
 STORE = {"f32": 0, "bf16": 1}
 TERM = {0: "max_epochs", 1: "loss_increase", 2: "abs_tol", 3: "rel_tol", 4: "nonfinite"}
 IMPUTE_BATCH, IMPUTE_LINK, IMPUTE_KEEP_OBSERVED = 1, 2, 4
+DEBATCH_LINK, DEBATCH_FILL_MISSING = 1, 2
 PARAM = {"X": 0, "Y": 1, "logsigma": 2, "mu": 3, "logdelta": 4, "theta": 5}
 
 
@@ -123,6 +124,7 @@ EXPORTS = [
     "pmf_debug_postprocess_times",
     "pmf_fsard_update_A_csr",
     "pmf_set_noise_thresholds", "pmf_get_noise_thresholds",
+    "pmf_remove_batch_effect", "pmf_remove_batch_effect_device", "pmf_remove_batch_effect_entries",
 ]
 
 COMM_ID_BYTES = 128
@@ -673,6 +675,66 @@ class Context:
             raise PMFError("impute_entries: rows and columns must have the same length")
         out = np.zeros(max(r.size, 1), np.float32)
         self._chk(self.lib.pmf_impute_entries(self._h, int(flags), C.c_int64(r.size), _i64p(r), _i64p(c), _fp(out)))
+        return out[:r.size]
+
+    # ---- batch-corrected data
+    @staticmethod
+    def debatch_flags(link=False, fill_missing=False):
+        return (DEBATCH_LINK if link else 0) | (DEBATCH_FILL_MISSING if fill_missing else 0)
+
+    def remove_batch_effect(self, flags=0, row_start1=1, row_stop1=None, Z=None, out=None, out_row=0):
+        """pmf_remove_batch_effect: rows row_start1..row_stop1 (1-based, inclusive; default all) x all columns with the batch
+        layers taken out.  Z: the values of exactly those rows (rows x N, any layout; copied to a Fortran-ordered float32
+        array unless it is one), or None for the data matrix resident on the device.  `out` as in `impute`; passing the same
+        Fortran-ordered array as Z and out (out_row = 0, its row count = rows) corrects it in place.  Returns the rows x N
+        block."""
+        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
+        rows = max(row_stop1 - int(row_start1) + 1, 0)
+        zp, ldz = None, 0
+        if Z is not None:
+            Zf = _f32(Z)
+            if Zf.shape != (rows, self.N):
+                raise PMFError(f"remove_batch_effect: Z must be rows x N = {rows} x {self.N}")
+            zp, ldz = C.c_void_p(Zf.ctypes.data), max(rows, 1)
+        if out is None:
+            out, out_row = np.zeros((rows, self.N), np.float32, order="F"), 0
+        elif out.dtype != np.float32 or out.ndim != 2 or not out.flags.f_contiguous or out.shape[1] != self.N:
+            raise PMFError("remove_batch_effect: out must be a Fortran-ordered float32 array with N columns")
+        if out_row < 0 or out_row + rows > out.shape[0]:
+            raise PMFError("remove_batch_effect: the block does not fit in out")
+        ptr = C.c_void_p(out.ctypes.data + 4 * int(out_row)) if out.size else None
+        self._chk(self.lib.pmf_remove_batch_effect(self._h, int(flags), C.c_int64(row_start1), C.c_int64(row_stop1), zp,
+                                                   C.c_int64(ldz), ptr, C.c_int64(out.shape[0])))
+        return out[out_row:out_row + rows]
+
+    def remove_batch_effect_device(self, out_ptr, flags=0, row_start1=1, row_stop1=None, z_ptr=None, ldz=None, ld=None):
+        """pmf_remove_batch_effect_device: the same between device matrices (addresses, e.g. a torch tensor's data_ptr());
+        z_ptr = None: the resident data matrix."""
+        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
+        rows = row_stop1 - int(row_start1) + 1
+        ld = rows if ld is None else int(ld)
+        ldz = rows if ldz is None else int(ldz)
+        self._chk(self.lib.pmf_remove_batch_effect_device(self._h, int(flags), C.c_int64(row_start1), C.c_int64(row_stop1),
+                                                          C.c_void_p(z_ptr) if z_ptr else None, C.c_int64(ldz),
+                                                          C.c_void_p(out_ptr), C.c_int64(ld)))
+
+    def remove_batch_effect_entries(self, rows1, cols1, values=None, flags=0):
+        """pmf_remove_batch_effect_entries: the corrected values at the listed (row, column) entries, 1-based; values = None:
+        the entries of the resident data matrix."""
+        r = np.ascontiguousarray(rows1, dtype=np.int64).ravel()
+        c = np.ascontiguousarray(cols1, dtype=np.int64).ravel()
+        if r.shape != c.shape:
+            raise PMFError("remove_batch_effect_entries: rows and columns must have the same length")
+        v = None
+        if values is not None:
+            v = np.ascontiguousarray(values, dtype=np.float32).ravel()
+            if v.shape != r.shape:
+                raise PMFError("remove_batch_effect_entries: one value per entry")
+            if v.size == 0:
+                v = np.zeros(1, np.float32)
+        out = np.zeros(max(r.size, 1), np.float32)
+        self._chk(self.lib.pmf_remove_batch_effect_entries(self._h, int(flags), C.c_int64(r.size), _i64p(r), _i64p(c), _fp(v),
+                                                           _fp(out)))
         return out[:r.size]
 
     def stats(self, use_factors=False):

@@ -6,6 +6,7 @@
 //   pmf_k_sb.hip       pmf_fused_sb_kernel + k_sb_split (pmf_fused_sb.hip.inc), once per K-block count
 //   pmf_k_layers.hip   pmf_layer_kernel + k_layer_map (pmf_layers.hip.inc)
 //   pmf_k_impute.hip   pmf_impute_kernel + k_impute_entries (pmf_impute.hip.inc)
+//   pmf_k_debatch.hip  pmf_debatch_kernel + k_debatch_entries (pmf_debatch.hip.inc)
 #ifndef PMF_COMMON_H
 #define PMF_COMMON_H
 #include <hip/hip_runtime.h>
@@ -459,6 +460,19 @@ struct LayerMapArgs {
 // ld.  m N exceeds 2^31 at the headline size: every operand is 64-bit before the product is formed.
 __host__ __device__ __forceinline__ int64_t pmf_impute_off(int64_t r, int64_t j, int64_t ld) { return j * ld + r; }
 
+// the inverse link of a column's noise model (pmf_impute.hip.inc, pmf_debatch.hip.inc)
+__device__ __forceinline__ float pmf_impute_invlink(int kind, float z, const float4 *tp) {   // tp: read for kind 3 only
+  if (kind == PMF_NOISE_SQ_HINGE) return pmf_hinge_class(z, *tp);
+  if (kind == PMF_NOISE_BERNOULLI) {
+    // 1 / (1 + e^-z) without an infinite intermediate: e = e^-|z| <= 1
+    const float e = __expf(-fabsf(z));
+    const float r = __frcp_rn(1.f + e);
+    return z >= 0.f ? r : e * r;
+  }
+  if (kind == PMF_NOISE_POISSON) return __expf(z);
+  return z;
+}
+
 struct ImputeArgs {
   const float *X, *Y;
   const float4 *colp;
@@ -489,6 +503,38 @@ struct ImputeEntriesArgs {
   const float4 *thr;
 };
 
+// ---- remove_batch_effect (pmf_debatch.hip.inc)
+struct DebatchArgs {
+  const void *Z;           // input: the tile-major D (f32 or bf16), or a column-major f32 matrix of leading dimension ldz
+  int64_t ldz, nRB;        //        whose first row is row0 of the matrix
+  const float4 *colp;
+  const int32_t *bor;      // n_bv x M row -> batch (or -1)
+  const float2 *btab;      // {delta, theta}, view v at views[v].tab_off, nb x Nv column-major
+  const ViewDesc *views;   // device array [n_bv]
+  float *out;              // column-major, rows row0 .. row1 - 1 of the matrix, leading dimension ld (pmf_impute_off)
+  int64_t ld;
+  int64_t M, N;
+  int64_t row0, row1;      // 0-based, [row0, row1)
+  int64_t rb0, n_rb;       // the 32-row blocks (absolute numbering) that meet the row range
+  int64_t n_ct;            // column tiles
+  int32_t n_bv, flags;
+};
+
+struct DebatchEntriesArgs {
+  const float *values;     // [n], or null: the entries of the resident D
+  const void *D;
+  int64_t nRB;
+  int32_t d_bf16, n_bv;
+  const float4 *colp;
+  const int32_t *bor;
+  const float2 *btab;
+  const ViewDesc *views;
+  const int64_t *rows1, *cols1;   // 1-based, validated on the host
+  float *out;
+  int64_t n, M;
+  int32_t flags;
+};
+
 // ---- launchers exported by the kernel files
 // Fused-kernel launchers, one per family, K-block count (exact kernel: and row blocks per wave) and storage type of D, all
 // of one type: the family table in pmf_hip.hip holds them.  The gradient variant follows a.want_gx / a.want_gy.
@@ -511,4 +557,7 @@ int pmf_launch_layer_map(hipStream_t stream, const LayerMapArgs &m);
 int pmf_impute_waves(int KB);   // waves per workgroup of pmf_impute_kernel: 8 up to K = 64, 4 above
 int pmf_launch_impute(PmfDynLds *cache, hipStream_t stream, int KB, bool d_bf16, int grid, const ImputeArgs &a);
 int pmf_launch_impute_entries(hipStream_t stream, const ImputeEntriesArgs &a);
+// src: 0 = the tile-major f32 D, 1 = the tile-major bf16 D, 2 = a column-major f32 matrix; n_cu sizes the persistent grid
+int pmf_launch_debatch(hipStream_t stream, int src, int n_cu, const DebatchArgs &a);
+int pmf_launch_debatch_entries(hipStream_t stream, const DebatchEntriesArgs &a);
 #endif

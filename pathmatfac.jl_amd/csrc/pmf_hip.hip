@@ -2491,6 +2491,127 @@ extern "C" int pmf_debug_impute_offset(int64_t row, int64_t col, int64_t ld, int
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// remove_batch_effect (src/remove_batch_effect.jl): the data with layers 2 and 4 taken out (pmf_debatch.hip.inc)
+// ------------------------------------------------------------------------------------------------
+// what every call checks before it touches the device: impute's readiness, and resident data when that is the input
+static int debatch_check(pmf_ctx *c, const char *fn, int flags, bool resident, const void *out, bool entries) {
+  if (!out) return pmf_fail("%s: null output pointer", fn);
+  if (flags & ~(PMF_DEBATCH_LINK | PMF_DEBATCH_FILL_MISSING)) return pmf_fail("%s: unknown flag bits 0x%x", fn, flags);
+  if (entries && (flags & PMF_DEBATCH_FILL_MISSING)) return pmf_fail("%s: PMF_DEBATCH_FILL_MISSING is not accepted here (predictions at entries: pmf_impute_entries)", fn);
+  if (resident && !c->D) return pmf_fail("%s: a null input means the resident data matrix (data not set)", fn);
+  if (c->K == 0 || c->M <= 0 || c->N <= 0) return pmf_fail("%s: factors not set", fn);
+  for (int v = 0; v < c->n_bv; ++v)
+    if (c->views[v].nb == 0) return pmf_fail("%s: batch view %d declared but not set", fn, v);
+  return 0;
+}
+
+// rows [row0, row1) (0-based) of Z_dev (column-major from row0, leading dimension ldz; null: the resident D) into out_dev;
+// prepare() has run.  FILL_MISSING: pmf_impute_kernel writes the batch-free prediction first, then only observed entries are stored.
+static int debatch_launch(pmf_ctx *c, int flags, int64_t row0, int64_t row1, const float *Z_dev, int64_t ldz, float *out_dev, int64_t ld) {
+  if (flags & PMF_DEBATCH_FILL_MISSING)
+    PMFCHK(impute_launch(c, (flags & PMF_DEBATCH_LINK) ? PMF_IMPUTE_LINK : 0, row0, row1, out_dev, ld));
+  DebatchArgs a;
+  memset(&a, 0, sizeof(a));
+  a.Z = Z_dev ? (const void *)Z_dev : (const void *)c->D.p; a.ldz = ldz; a.nRB = c->nRB;
+  a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
+  a.out = out_dev; a.ld = ld; a.M = c->M; a.N = c->N; a.row0 = row0; a.row1 = row1;
+  a.rb0 = row0 / 32;
+  a.n_rb = (row1 - 1) / 32 + 1 - a.rb0;
+  a.n_ct = (c->N + PMF_BN - 1) / PMF_BN;
+  a.n_bv = c->n_bv; a.flags = flags;
+  if (a.n_rb * a.n_ct >= (1ll << 31)) return pmf_fail("pmf_remove_batch_effect: too many tiles in one call (split the row range)");
+  return pmf_launch_debatch(c->stream, Z_dev ? 2 : (c->store == PMF_STORE_BF16 ? 1 : 0), c->n_cu, a);
+}
+
+extern "C" int pmf_remove_batch_effect_device(pmf_ctx *c, int flags, int64_t row_start1, int64_t row_stop1, const float *Z_device,
+                                              int64_t ldz, float *out_device, int64_t ld) {
+  static const char *fn = "pmf_remove_batch_effect_device";
+  PMFCHK(ctx_bind(c));
+  PMFCHK(debatch_check(c, fn, flags, !Z_device, out_device, false));
+  PMFCHK(impute_check_range(c, fn, row_start1, row_stop1, ld));
+  const int64_t rows = row_stop1 - row_start1 + 1;
+  if (Z_device) {
+    if (ldz < rows) return pmf_fail("%s: ldz=%lld is below the row count %lld", fn, (long long)ldz, (long long)rows);
+    const float *ze = Z_device + pmf_impute_off(rows, c->N - 1, ldz), *oe = out_device + pmf_impute_off(rows, c->N - 1, ld);
+    const bool in_place = Z_device == out_device && ldz == ld && !(flags & PMF_DEBATCH_FILL_MISSING);
+    if (Z_device < oe && out_device < ze && !in_place)
+      return pmf_fail("%s: input and output overlap (in place needs Z == out, ldz == ld and no PMF_DEBATCH_FILL_MISSING)", fn);
+  }
+  PMFCHK(prepare(c));
+  PMFCHK(debatch_launch(c, flags, row_start1 - 1, row_stop1, Z_device, ldz, out_device, ld));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int pmf_remove_batch_effect(pmf_ctx *c, int flags, int64_t row_start1, int64_t row_stop1, const float *Z_host, int64_t ldz,
+                                       float *out_host, int64_t ld) {
+  static const char *fn = "pmf_remove_batch_effect";
+  PMFCHK(ctx_bind(c));
+  PMFCHK(debatch_check(c, fn, flags, !Z_host, out_host, false));
+  PMFCHK(impute_check_range(c, fn, row_start1, row_stop1, ld));
+  const int64_t rows = row_stop1 - row_start1 + 1;
+  if (Z_host && ldz < rows) return pmf_fail("%s: ldz=%lld is below the row count %lld", fn, (long long)ldz, (long long)rows);
+  // the prediction of FILL_MISSING must not land on a host input's chunk: then the staging buffer holds an input and an
+  // output part; otherwise the chunk is corrected in place.  Chunk height as in pmf_impute.
+  const int parts = Z_host && (flags & PMF_DEBATCH_FILL_MISSING) ? 2 : 1;
+  const int64_t cap = std::max<int64_t>(1, (int64_t)(PMF_IMPUTE_STAGE_MAX / sizeof(float)) / c->N / parts);
+  int64_t ch = cap >= 32 ? cap - cap % 32 : cap;
+  if (const char *e = getenv("PMF_DEBATCH_CHUNK_ROWS")) {
+    const long long v = atoll(e);
+    if (v > 0) ch = std::min<int64_t>(v, cap);
+  }
+  ch = std::min(ch, rows);
+  PMFCHK(c->impute_stage.ensure(sizeof(float) * (size_t)(ch * c->N * parts), false));
+  PMFCHK(prepare(c));
+  float *s_out = (float *)c->impute_stage.p, *s_in = s_out + (parts - 1) * ch * c->N;
+  for (int64_t r0 = row_start1 - 1; r0 < row_stop1; r0 += ch) {
+    const int64_t nr = std::min(ch, row_stop1 - r0), rel = r0 - (row_start1 - 1);
+    if (Z_host)
+      HIPCHK(hipMemcpy2DAsync(s_in, sizeof(float) * (size_t)nr, Z_host + rel, sizeof(float) * (size_t)ldz, sizeof(float) * (size_t)nr,
+                              (size_t)c->N, hipMemcpyHostToDevice, c->stream));
+    PMFCHK(debatch_launch(c, flags, r0, r0 + nr, Z_host ? s_in : nullptr, nr, s_out, nr));
+    HIPCHK(hipMemcpy2DAsync(out_host + rel, sizeof(float) * (size_t)ld, s_out, sizeof(float) * (size_t)nr, sizeof(float) * (size_t)nr,
+                            (size_t)c->N, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+
+extern "C" int pmf_remove_batch_effect_entries(pmf_ctx *c, int flags, int64_t n, const int64_t *rows1, const int64_t *cols1,
+                                               const float *values, float *out_host) {
+  static const char *fn = "pmf_remove_batch_effect_entries";
+  PMFCHK(ctx_bind(c));
+  if (n < 0) return pmf_fail("%s: n=%lld", fn, (long long)n);
+  if (n == 0) return 0;
+  PMFCHK(debatch_check(c, fn, flags, !values, out_host, true));
+  if (!rows1 || !cols1) return pmf_fail("%s: null index pointer", fn);
+  for (int64_t e = 0; e < n; ++e)
+    if (rows1[e] < 1 || rows1[e] > c->M || cols1[e] < 1 || cols1[e] > c->N)
+      return pmf_fail("%s: entry %lld = (%lld, %lld) is outside 1..%lld x 1..%lld", fn, (long long)e, (long long)rows1[e],
+                      (long long)cols1[e], (long long)c->M, (long long)c->N);
+  const int64_t ch = std::min<int64_t>(n, 1ll << 22);   // 24 bytes of staging per entry
+  PMFCHK(c->impute_stage.ensure((size_t)ch * (2 * sizeof(int64_t) + 2 * sizeof(float)), false));
+  PMFCHK(prepare(c));
+  int64_t *d_rows = (int64_t *)c->impute_stage.p, *d_cols = d_rows + ch;
+  float *d_val = (float *)(d_cols + ch), *d_out = d_val + ch;
+  for (int64_t e0 = 0; e0 < n; e0 += ch) {
+    const int64_t ne = std::min(ch, n - e0);
+    HIPCHK(hipMemcpyAsync(d_rows, rows1 + e0, sizeof(int64_t) * (size_t)ne, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_cols, cols1 + e0, sizeof(int64_t) * (size_t)ne, hipMemcpyHostToDevice, c->stream));
+    if (values) HIPCHK(hipMemcpyAsync(d_val, values + e0, sizeof(float) * (size_t)ne, hipMemcpyHostToDevice, c->stream));
+    DebatchEntriesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.values = values ? d_val : nullptr; a.D = c->D.p; a.nRB = c->nRB; a.d_bf16 = c->store == PMF_STORE_BF16; a.n_bv = c->n_bv;
+    a.colp = c->colp; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
+    a.rows1 = d_rows; a.cols1 = d_cols; a.out = d_out; a.n = ne; a.M = c->M; a.flags = flags;
+    PMFCHK(pmf_launch_debatch_entries(c->stream, a));
+    HIPCHK(hipMemcpyAsync(out_host + e0, d_out, sizeof(float) * (size_t)ne, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return 0;
+}
+
 extern "C" int pmf_synth_data(pmf_ctx *c, uint64_t seed, float noise, float frac_nan) {
   PMFCHK(ctx_bind(c));
   if (!c->D) return pmf_fail("data buffer not allocated (pmf_set_data_device(ctx, NULL, M, N, store))");

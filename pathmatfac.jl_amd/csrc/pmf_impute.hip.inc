@@ -19,19 +19,8 @@
 // row range is asked for: an entry is always computed by the same lane of the same block in the same order, and the range
 // only masks the stores.  The three flags are run-time, wave-uniform branches (one instance per (KB, NW, DB)).
 
-// the two rules the MFMA kernel and the per-entry kernel share
+// the two rules the MFMA kernel and the per-entry kernel share (pmf_impute_invlink: pmf_common.h, shared with pmf_debatch.hip.inc)
 __device__ __forceinline__ float pmf_impute_batch(float z1, float mu, float2 dt) { return fmaf(z1, dt.x, mu + dt.y); }
-__device__ __forceinline__ float pmf_impute_invlink(int kind, float z, const float4 *tp) {   // tp: read for kind 3 only
-  if (kind == PMF_NOISE_SQ_HINGE) return pmf_hinge_class(z, *tp);
-  if (kind == PMF_NOISE_BERNOULLI) {
-    // 1 / (1 + e^-z) without an infinite intermediate: e = e^-|z| <= 1
-    const float e = __expf(-fabsf(z));
-    const float r = __frcp_rn(1.f + e);
-    return z >= 0.f ? r : e * r;
-  }
-  if (kind == PMF_NOISE_POISSON) return __expf(z);
-  return z;
-}
 
 template <int KB, int NW>
 struct ImputeCfg {

@@ -737,6 +737,24 @@ function impute(model::PM.PathMatFacModel; include_batch_effects=false, link=fal
     return out
 end
 
+"""remove_batch_effect(model, Z) (src/remove_batch_effect.jl:3-16) on the device: pmf_remove_batch_effect with the model's
+current column and batch parameters, against the layer order of src/layers.jl:240-253 (the reference's body inverts an
+older one).  Z holds the values of `rows` (M x N by default); `link=true`: Z and the result are in link space;
+`fill_missing=true`: missing entries take the batch-free prediction instead of NaN.  Returns length(rows) x N Float32."""
+function remove_batch_effect(model::PM.PathMatFacModel, Z::AbstractMatrix; link=false, fill_missing=false,
+                             rows::UnitRange=1:size(model.data, 1))
+    size(Z) == (length(rows), size(model.data, 2)) || error("remove_batch_effect: Z must be length(rows) x N")
+    ctx = context!(model)
+    marshal!(ctx, model.matfac)
+    flags = Cint((link ? 1 : 0) | (fill_missing ? 2 : 0))
+    Z32 = f32(Z)
+    out = zeros(Float32, length(rows), size(model.data, 2))
+    GC.@preserve Z32 out chk(ccall((:pmf_remove_batch_effect, LIB[]), Cint,
+                                   (Ptr{Cvoid}, Cint, Int64, Int64, Ptr{Cfloat}, Int64, Ptr{Cfloat}, Int64),
+                                   ctx, flags, rows.start, rows.stop, Z32, length(rows), out, length(rows)))
+    return out
+end
+
 """Point PathMatFac's drop-in boundary at the HIP library."""
 function install!(libpath::AbstractString="libpmf_hip.so")
     LIB[] = libpath
@@ -753,6 +771,7 @@ function install!(libpath::AbstractString="libpmf_hip.so")
     @eval PathMatFac reorder_by_importance!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.reorder_by_importance!(model; kwargs...)
     @eval PathMatFac reweight_eb!(reg::L2Regularizer, X::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.reweight_eb!(reg, X; kwargs...)
     @eval PathMatFac reweight_eb!(reg::GroupRegularizer, X::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.reweight_eb!(reg, X; kwargs...)
+    @eval PathMatFac remove_batch_effect(model::PathMatFacModel, Z::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.remove_batch_effect(model, Z; kwargs...)
     return nothing
 end
 
