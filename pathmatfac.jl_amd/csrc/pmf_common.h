@@ -1,7 +1,7 @@
 // pmf_common.h -- what the translation units of libpmf_hip.so share: the kernels' argument structs, the device layout of
 // the data matrix, small device helpers, and the host-side launchers each kernel file exports.  The library is built
 // from several translation units so that they compile in parallel (csrc/Makefile):
-//   pmf_hip.hip        C ABI, small kernels, work split, epoch loop, communicator
+//   pmf_hip.hip        C ABI (marshalling, step-level API, statistics), small kernels (pmf_ctx.h lists the other host units)
 //   pmf_k_fused.hip    pmf_fused_kernel (pmf_fused.hip.inc), once per (K blocks, row blocks per wave)
 //   pmf_k_sb.hip       pmf_fused_sb_kernel + k_sb_split (pmf_fused_sb.hip.inc), once per K-block count
 //   pmf_k_layers.hip   pmf_layer_kernel + k_layer_map (pmf_layers.hip.inc)
@@ -81,7 +81,7 @@ struct FusedArgs {
   const int32_t *bor;   // n_bv x M
   const float2 *btab;
   const float2 *btd;    // dense per-column batch table [N padded to 32][1 << nbs_shift] {delta, theta} (last slot = identity); null = not available
-  // panel-local batch slots (PanelSlots, pmf_hip.hip): slot s of (row panel rp, view v) holds batch pm[(rp*n_bv + v)*16 + s]
+  // panel-local batch slots (PanelSlots, pmf_ctx.h): slot s of (row panel rp, view v) holds batch pm[(rp*n_bv + v)*16 + s]
   // (255 = unused); row_slot[v*M + i] = the slot of row i (15 = no batch); colview[j] = view of column j (255 = none)
   const uint8_t *pm, *row_slot, *colview;
   int32_t nbs_shift;
@@ -537,7 +537,7 @@ struct DebatchEntriesArgs {
 
 // ---- launchers exported by the kernel files
 // Fused-kernel launchers, one per family, K-block count (exact kernel: and row blocks per wave) and storage type of D, all
-// of one type: the family table in pmf_hip.hip holds them.  The gradient variant follows a.want_gx / a.want_gy.
+// of one type: the family table in pmf_pass.hip holds them.  The gradient variant follows a.want_gx / a.want_gy.
 typedef int PmfFusedLaunch(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
 PmfFusedLaunch pmf_launch_fused_exact_11, pmf_launch_fused_exact_12, pmf_launch_fused_exact_21, pmf_launch_fused_exact_31,
     pmf_launch_fused_exact_41, pmf_launch_fused_exact_11_bf16, pmf_launch_fused_exact_12_bf16, pmf_launch_fused_exact_21_bf16,

@@ -1,7 +1,9 @@
 // pmf_ctx.h -- internal to libpmf_hip.so: the context behind the opaque `pmf_ctx` of include/pmf_hip.h and the host
 // helpers its translation units share; DevBuf / PinnedBuf, the one type that allocates and frees device and pinned memory
 // (every buffer below is a member of that type, or a local of one call: no capacity fields, no free lists).
-//   pmf_hip.hip       C ABI (marshalling, step-level API, statistics), small kernels, work split, data-pass launches
+//   pmf_hip.hip       C ABI (marshalling, step-level API, statistics), small kernels, the scalar column walk, layer-pass launches
+//   pmf_pass.hip      host driver of the fused data pass: work split, family table, geometry, buffers, extents, launches
+//   pmf_outputs.hip   pmf_forward, pmf_synth_data, pmf_impute*, pmf_remove_batch_effect* and the staging path they share
 //   pmf_comm_fit.hip  cross-rank exchange (RCCL via dlopen / host-staged transport) and the epoch loop pmf_fit
 //   pmf_fsard.hip     the FeatureSetARD update_A! solver (ISTA on the device; dense S, A in LDS, L x K <= 16384)
 //   pmf_fsard_csr.hip the same solver on a sparse S with A in device memory (no bound on L x K)
@@ -272,7 +274,7 @@ struct pmf_ctx {
 #define PMF_MAX_CHUNKS 16
 
 // Geometry of one fused data pass: kernel family, row panels, column chunks.
-struct FusedFamily;   // a row of the family table (pmf_hip.hip): kernel, panel height, operand images, launchers
+struct FusedFamily;   // a row of the family table (pmf_pass.hip): kernel, panel height, operand images, launchers
 struct FusedGeom {
   const FusedFamily *fam = nullptr;
   int grid_max = 256, S = 1;
@@ -336,25 +338,44 @@ __device__ __forceinline__ void pmf_reg_ard(float p, float be, float al, float s
   g += scale * ((al + 0.5f) * p / (b * be));
 }
 
+// ---- small host helpers
+inline int nblocks(int64_t n, int bs) { return (int)((n + bs - 1) / bs); }
+// the by-value copy of the batch views (and of their offsets into logdelta / theta) a kernel's argument struct carries
+inline void fill_views(const pmf_ctx *c, ViewDesc *views, int64_t *val_off = nullptr) {
+  for (int v = 0; v < c->n_bv; ++v) {
+    views[v] = c->views[v];
+    if (val_off) val_off[v] = c->val_off[v];
+  }
+}
+// room for the n loss partials of the pass about to be launched, which k_loss_reduce will then sum
+inline int ensure_loss_partials(pmf_ctx *c, int64_t n) {
+  PMFCHK(c->loss_partial.ensure((size_t)n, true));
+  c->n_macro = n;
+  return 0;
+}
+// a call's temporary: n elements (not zeroed) holding a copy of src
+template <typename T>
+int upload_new(DevBuf<T> &b, const T *src, size_t n) {
+  PMFCHK(b.alloc(n, false));
+  return b.upload(src, n);
+}
+template <typename T>
+int upload_vec(pmf_ctx *c, std::common_type_t<T> *dst, const T *src, size_t n) {   // (T is deduced from src alone: dst may be a DevBuf)
+  if (n == 0) return 0;
+  HIPCHK(hipMemcpyAsync(dst, src, sizeof(T) * n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // ---- defined in pmf_hip.hip
 int ctx_bind(pmf_ctx *c);
 int ensure_dyn_lds(pmf_ctx *c, const void *kern, size_t lds);
 int check_ready(pmf_ctx *c);
-int harvest_events(pmf_ctx *c);
+int prepare(pmf_ctx *c);   // the column / batch tables (colp, btab, the dense table) from the current layer parameters
+int upload_padded(pmf_ctx *c, float *dst, const float *src, int64_t n, float padval);   // host K x n -> device Kp x n
+int download_padded(pmf_ctx *c, float *dst_host, const float *src_dev, int64_t n);      // and back
 int epoch_open(pmf_ctx *c, const pmf_fit_opts *o);
 int epoch_layer_pass(pmf_ctx *c, const pmf_fit_opts *o, bool with_loss);
-FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chunks);
-int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);
-int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool want_gy);
-// What the kernels of a prepared data pass address in every grow-only buffer against what is allocated, in bytes
-// (DESIGN.md section 3, "Extents").  fused_pass_extents fills out[PMF_PASS_EXTENTS] and returns the count;
-// check_pass_extents fails on the first need > cap, naming the buffer; guard_fused_pass is both, between
-// prepare_fused_pass and the first launch of the pass: a few integer compares, no device work.
-struct PassExtent { const char *name; int64_t need, cap; };
-constexpr int PMF_PASS_EXTENTS = 10;
-int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy, PassExtent *out);
-int check_pass_extents(const PassExtent *e, int n);
-int guard_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);
 int step_param_range(pmf_ctx *c, int which, int64_t e0, int64_t n, bool do_step, bool use_reg, int reg_slot, int *reg_count,
                      int max_blocks, bool advance);
 int step_param(pmf_ctx *c, int which, bool do_step, bool use_reg, int reg_slot, int *reg_count);
@@ -376,6 +397,21 @@ int eval_data_grads(pmf_ctx *c);
 // nothing else, ahead of a caller that must not launch anything before it knows the pass will run.
 int stats_pass_check(pmf_ctx *c);
 int stats_pass(pmf_ctx *c, int use_factors, bool want_cols, bool want_batch, const float **cols, const float **batch);
+// ---- defined in pmf_pass.hip
+int harvest_events(pmf_ctx *c);
+int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy);   // the whole data pass in one go (chunks only on request)
+FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chunks);
+int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);
+int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool want_gy);
+// What the kernels of a prepared data pass address in every grow-only buffer against what is allocated, in bytes
+// (DESIGN.md section 3, "Extents").  fused_pass_extents fills out[PMF_PASS_EXTENTS] and returns the count;
+// check_pass_extents fails on the first need > cap, naming the buffer; guard_fused_pass is both, between
+// prepare_fused_pass and the first launch of the pass: a few integer compares, no device work.
+struct PassExtent { const char *name; int64_t need, cap; };
+constexpr int PMF_PASS_EXTENTS = 10;
+int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy, PassExtent *out);
+int check_pass_extents(const PassExtent *e, int n);
+int guard_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);
 // ---- defined in pmf_lbfgs.hip
 void lbfgs_free(pmf_ctx *c);
 // ---- defined in pmf_netreg.hip

@@ -1,4 +1,4 @@
-// pmf_fused.hip.inc -- the fused data-pass kernel (included by pmf_hip.hip).
+// pmf_fused.hip.inc -- the fused data-pass kernel (included by pmf_k_fused.hip).
 //
 // One launch per epoch computes, for the local rows of D, everything the reference does in ~10 full
 // M x N round trips (SURVEY 3.2): A = X'Y (MatFac forward; layers.jl:283), the four column layers
@@ -21,7 +21,7 @@
 //   The per-wave gY partials of a tile are written to per-wave LDS slabs with plain stores; after barrier B1 all
 //   waves sum the NW slabs (16-B LDS reads, interleaved with the next tile's forward MFMAs) and add the result to
 //   the workgroup's PRIVATE copy of gY in HBM with a plain read-modify-write (the old values are prefetched half a
-//   tile earlier); barrier B2 frees the slabs.  k_gy_reduce (pmf_hip.hip) then sums the private copies of the
+//   tile earlier); barrier B2 frees the slabs.  k_gy_reduce (pmf_pass.hip) then sums the private copies of the
 //   workgroups that visited each column segment, in fixed order: no float atomics on the gY path and a bitwise
 //   reproducible gY.  (Measured alternatives: LDS float atomics, ds_add_f32, 3.5x slower than the whole rest of
 //   the kernel; global atomics per tile, 10.6 % of the wave time in issue stalls -- the CU retires one 256-B

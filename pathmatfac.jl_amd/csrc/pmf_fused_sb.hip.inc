@@ -1,4 +1,4 @@
-// pmf_fused_sb.hip.inc -- the fused data pass on split-bf16 ("bf16x3") matrix products (included by pmf_hip.hip).
+// pmf_fused_sb.hip.inc -- the fused data pass on split-bf16 ("bf16x3") matrix products (included by pmf_k_sb.hip).
 //
 // Same computation, work split, private gY slabs and outputs as pmf_fused_kernel (pmf_fused.hip.inc); what changes is
 // how the three products are evaluated.  v_mfma_f32_32x32x2_f32 is exact but runs at 1/16 of the bf16 rate and blocks

@@ -1,4 +1,4 @@
-// pmf_layers.hip.inc -- the layer-parameter pass (included by pmf_hip.hip after pmf_fused.hip.inc).
+// pmf_layers.hip.inc -- the layer-parameter pass (included by pmf_k_layers.hip).
 //
 // Epochs that train only the column layers (init_mu!, init_theta!, the batch-effect fits: src/fit.jl:82-122, 378-496)
 // need, per column j and row batch b of j's view, S_G[b,j] = sum_{i in b} g_ij and S_Q[b,j] = sum_{i in b} g_ij z1_ij

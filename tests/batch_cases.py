@@ -1,7 +1,7 @@
 """Problems at the batch-table edges of the fused data pass, and the selection rules restated (no GPU needed).
 
 With batch layers a fused kernel family keeps a 32-column x 16-slot {delta, theta} table in LDS.  Slots are local to a
-(row panel of the family's height BM, view): ensure_panel_slots (csrc/pmf_hip.hip) gives every distinct batch of the panel
+(row panel of the family's height BM, view): ensure_panel_slots (csrc/pmf_pass.hip) gives every distinct batch of the panel
 one of the slots 0..14 and every row in no batch the identity slot 15.  A family therefore fits when no (panel, view) meets
 more than 15 batches and its LDS has room for the views (max_bv); fused_geometry walks
 

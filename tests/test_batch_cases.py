@@ -1,6 +1,6 @@
 """The batch-edge problems of tests/test_gpu_batch_edges.py are what they claim to be (no GPU).
 
-* the restated selection rules give the families of the table in csrc/pmf_hip.hip (fused_geometry) on spot values;
+* the restated selection rules give the families of the table in csrc/pmf_pass.hip (fused_geometry) on spot values;
 * every builder has the per-panel batch counts its case is about, ascending disjoint views and batch ids below nb;
 * sensitivity: on every problem the GPU file runs, one batched row moved to another batch of its panel, one unbatched row
   given batch 0, or one view boundary moved by a column changes the fp64 oracle's gX or gY by at least 10 GRAD_TOL in

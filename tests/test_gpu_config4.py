@@ -298,7 +298,7 @@ def test_k64_fit_trajectory_through_sb8(sctx, opt):
 
 
 def test_noise_tile_weights_change_the_split_not_the_result(sctx):
-    """The work split weighs Bernoulli / Poisson tiles by measured per-kernel costs (noise_tile_weights, pmf_hip.hip).  Whatever
+    """The work split weighs Bernoulli / Poisson tiles by measured per-kernel costs (noise_tile_weights, pmf_pass.hip).  Whatever
     the weights (PMF_W_BERN / PMF_W_BATCH override them), loss and gradients are those of the oracle: a weight only moves the
     boundaries between workgroups."""
     import os

@@ -1,7 +1,7 @@
 """Every fused kernel family at its K edges and its panel edges, against the fp64 oracle.
 
 The data pass picks a kernel family and a row-panel height from K, the precision, the gradients wanted and the batch
-layers (fused_geometry, csrc/pmf_hip.hip).  Ragged shapes go wrong at the edges of that table: K one above or below a
+layers (fused_geometry, csrc/pmf_pass.hip).  Ragged shapes go wrong at the edges of that table: K one above or below a
 multiple of 32 (the k-block count KB = ceil(K/32) and its zero padding), a last row panel holding one row or missing most
 of its 32-row blocks, and a last column tile that is ragged at 32 or at the 64-column pad of the tiled D.  Each case here
 picks M from the panel height BM of the family it must run, pairs it with one N, asserts that family ran, and compares the

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import debatch_ref as dref
 from impute_ref import (BATCH, CASES, FLAG_SETS, KEEP, LINK, case_problem, impute_ref, impute_tol, kinds_of, scale_of,
                         worst_ratio)
 from problems import rel_err, to_context
@@ -230,6 +231,39 @@ def test_entries(ctx):
         assert one.shape == (1,) and bits(one)[0] == bits(got)[0]
         assert ctx.impute_entries(np.zeros(0, np.int64), np.zeros(0, np.int64), flags).shape == (0,)
     assert ctx.lib.pmf_impute_entries(ctx._h, 0, C.c_int64(0), None, None, None) == 0
+
+
+def test_entry_chunk_seam(ctx):
+    """pmf_impute_entries and pmf_remove_batch_effect_entries stage 1 << 22 entries at a time: three entries more than one
+    chunk, so that a second round runs with the staging buffer carved for the first.  Every entry against the full matrix of
+    the fp64 restatements under their own bounds, and bit for bit the two calls that stop and start at the seam: an entry's
+    bits do not depend on the chunk it falls in."""
+    CH, M, N = 1 << 22, 70, 100
+    rng = np.random.default_rng(2207)
+    bor = rows(M, 3, "sorted", rng)
+    bor[[0, 3, 41, M - 1]] = -1                                  # rows in no batch
+    p = layer_problem(M, N, 8, 2208, [(10, 77, bor, 3)])         # columns outside the view on both sides, mixed noise kinds
+    assert {0, 1, 2} <= set(kinds_of(p).tolist())
+    to_context(p, ctx)
+    D = np.asarray(p["D"], np.float32)
+    n = CH + 3
+    r, c = rng.integers(0, M, n), rng.integers(0, N, n)
+    r[[CH - 1, CH, CH + 2]], c[[CH - 1, CH, CH + 2]] = (5, 69, 41), (11, 76, 99)
+    r1, c1, v = r + 1, c + 1, D[r, c]
+    want, z = impute_ref(p, BATCH)
+    wd, _, _ = dref.debatch_ref(p, D, 0)
+    calls = [("impute", lambda s: ctx.impute_entries(r1[s], c1[s], BATCH), worst_ratio, want, impute_tol(p, BATCH, z)),
+             ("debatch, given values", lambda s: ctx.remove_batch_effect_entries(r1[s], c1[s], v[s]), dref.worst_ratio, wd,
+              dref.debatch_tol(p, D, 0)),
+             ("debatch, resident", lambda s: ctx.remove_batch_effect_entries(r1[s], c1[s]), dref.worst_ratio, wd,
+              dref.debatch_tol(p, D, 0))]
+    for what, call, ratio, ref, tol in calls:
+        got = call(slice(None))
+        assert got.shape == (n,) and got.dtype == np.float32
+        q = ratio(got, ref[r, c], tol[r, c])
+        print(f"{what}: worst |error| / bound = {q:.3f}")
+        assert q <= 1.0, (what, q)
+        assert same_bits(got, np.concatenate([call(slice(0, CH)), call(slice(CH, n))])), what
 
 
 # ---- 6. saturation ----------------------------------------------------------------------------------------------------
