@@ -414,6 +414,46 @@ int pmf_impute_device(pmf_ctx *ctx, int flags, int64_t row_start1, int64_t row_s
 int pmf_impute_entries(pmf_ctx *ctx, int flags, int64_t n, const int64_t *rows1, const int64_t *cols1, float *out_host);
 int pmf_debug_impute_offset(int64_t row, int64_t col, int64_t ld, int64_t *offset);
 
+/* simulate_data!(model) (src/simulate_params.jl:219-251): a data matrix drawn from the context's CURRENT X, Y, column
+ * parameters, batch views, noise ranges and thresholds.  SELF-SPECIFIED where the reference is silent (DESIGN.md section 2,
+ * Deviation 4).  Per entry (i = GLOBAL 0-based row = local row + row_offset, j = 0-based column):
+ *     z = the value of pmf_impute with PMF_IMPUTE_BATCH | PMF_IMPUTE_LINK, bit for bit (MF.forward(matfac), :247)
+ *     Philox4x32-10 (Salmon et al., SC'11) with counter (i_lo, i_hi, j_lo, j_hi) and key (seed_lo, seed_hi) gives r0..r3;
+ *     u1 = ((r0 >> 8) + 1) 2^-24, u2 = (r1 >> 8) 2^-24, n = sqrtf(-2 logf(u1)) cosf(6.28318530718f u2),
+ *     u3 = (r2 >> 8) 2^-24 (missingness), u4 = (r3 >> 8) 2^-24 (Bernoulli)
+ *     normal            -> fmaf(noise, n, z)  (:240-242; noise = 0 gives z itself)
+ *     kind 3 (sq hinge) -> the number of the column's thresholds strictly below z: the class of the noise-free z (:224-238),
+ *                          pmf_impute with PMF_IMPUTE_BATCH bit for bit
+ *     bernoulli (logit) -> u4 < 1 / (1 + e^-z) ? 1 : 0   (no reference method)
+ *     poisson           -> the call is refused (no reference method, no sampler)
+ *     then u3 < frac_missing -> NaN  (frac_missing = 0: never; 1: always)
+ * An entry's value depends on (parameters, seed, i, j, noise, frac_missing) alone: not on the row range, the chunking, ld,
+ * the kind of output, pmf_set_precision or what the context ran before; a row shard with its row_offset reproduces its
+ * rows of the whole matrix.
+ *   pmf_simulate_data          : local rows row_start1..row_stop1 (1-based, inclusive) x all N columns into a HOST matrix,
+ *                                column-major with leading dimension ld >= rows, as pmf_impute: through the context's staging
+ *                                buffer of at most 256 MiB (PMF_SIMULATE_CHUNK_ROWS=n, read at every call, overrides the chunk
+ *                                height); elements between the rows of a column are not written.
+ *   pmf_simulate_data_device   : the same into DEVICE memory, one launch, no staging.
+ *   pmf_simulate_data_resident : overwrites the whole data matrix resident on the device (bf16-rounded under PMF_STORE_BF16
+ *                                exactly as pmf_set_data rounds): a later pmf_fit / pmf_loss / pmf_stats sees what
+ *                                pmf_set_data of pmf_simulate_data's host matrix would give.  Needs the buffer that
+ *                                pmf_set_data_device(ctx, NULL, M, N, store) or an earlier pmf_set_data allocated.
+ * The calls change no parameter, gradient or optimizer state.  LOCAL ROWS ONLY: no communicator traffic.
+ * Refused before anything is launched (the context stays usable): null options or output, noise negative or not finite,
+ * frac_missing outside [0, 1] or NaN, row_offset < 0, an empty or out-of-range row range, ld below the row count, factors
+ * or batch views not set, a noise range of kind poisson, pmf_simulate_data_resident without a data buffer. */
+typedef struct pmf_sim_opts {
+  uint64_t seed;
+  int64_t row_offset;     /* global index of local row 1 (0 on one GPU; the shard's first row otherwise) */
+  float noise;            /* standard deviation of the normal columns' noise (simulate_data!'s `noise`) */
+  float frac_missing;     /* probability that an entry is NaN */
+} pmf_sim_opts;
+int pmf_simulate_data(pmf_ctx *ctx, const pmf_sim_opts *opts, int64_t row_start1, int64_t row_stop1, float *out_host, int64_t ld);
+int pmf_simulate_data_device(pmf_ctx *ctx, const pmf_sim_opts *opts, int64_t row_start1, int64_t row_stop1, float *out_device,
+                             int64_t ld);
+int pmf_simulate_data_resident(pmf_ctx *ctx, const pmf_sim_opts *opts);
+
 /* remove_batch_effect(model, Z) (src/remove_batch_effect.jl:3-16): the data with the fitted batch effects taken out, from
  * the context's CURRENT column parameters and batch views.  SELF-SPECIFIED (Deviation 3): the
  * reference's body reads fields that no longer exist and inverts an older layer order; this inverts the order the library

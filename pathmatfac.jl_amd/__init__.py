@@ -22,6 +22,8 @@ from . import impute as _impute  # noqa: F401
 from .impute import impute, impute_entries  # noqa: F401
 from . import remove_batch_effect as _remove_batch_effect  # noqa: F401
 from .remove_batch_effect import remove_batch_effect, remove_batch_effect_entries  # noqa: F401
+from . import simulate as _simulate  # noqa: F401
+from .simulate import simulate_params_, simulate_data_, average_precision, Y_average_precs  # noqa: F401
 from . import model_io  # noqa: F401
 from .model_io import save_params_npz, load_params_npz  # noqa: F401
 from . import data_io  # noqa: F401

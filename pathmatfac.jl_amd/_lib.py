@@ -68,6 +68,11 @@ class EmResult(C.Structure):
                 ("diffs", C.POINTER(C.c_double)), ("seconds", C.c_double)]
 
 
+class SimOpts(C.Structure):
+    """pmf_sim_opts"""
+    _fields_ = [("seed", C.c_uint64), ("row_offset", C.c_int64), ("noise", C.c_float), ("frac_missing", C.c_float)]
+
+
 class Csr(C.Structure):
     """pmf_csr: one sparse block in 0-based CSR with sorted rows."""
     _fields_ = [("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rowptr", C.POINTER(C.c_int64)),
@@ -125,6 +130,7 @@ EXPORTS = [
     "pmf_fsard_update_A_csr",
     "pmf_set_noise_thresholds", "pmf_get_noise_thresholds",
     "pmf_remove_batch_effect", "pmf_remove_batch_effect_device", "pmf_remove_batch_effect_entries",
+    "pmf_simulate_data", "pmf_simulate_data_device", "pmf_simulate_data_resident",
 ]
 
 COMM_ID_BYTES = 128
@@ -676,6 +682,43 @@ class Context:
         out = np.zeros(max(r.size, 1), np.float32)
         self._chk(self.lib.pmf_impute_entries(self._h, int(flags), C.c_int64(r.size), _i64p(r), _i64p(c), _fp(out)))
         return out[:r.size]
+
+    # ---- simulated data
+    @staticmethod
+    def sim_opts(seed=0, noise=0.1, frac_missing=0.0, row_offset=0):
+        return SimOpts(int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_offset), float(noise), float(frac_missing))
+
+    def simulate_data(self, seed=0, noise=0.1, frac_missing=0.0, row_offset=0, row_start1=1, row_stop1=None, out=None,
+                      out_row=0):
+        """pmf_simulate_data: rows row_start1..row_stop1 (1-based, inclusive; default all) x all columns drawn from the
+        current parameters; `out` and `out_row` as in `impute`.  row_offset: the global index of local row 1."""
+        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
+        rows = max(row_stop1 - int(row_start1) + 1, 0)
+        if out is None:
+            out, out_row = np.zeros((rows, self.N), np.float32, order="F"), 0
+        elif out.dtype != np.float32 or out.ndim != 2 or not out.flags.f_contiguous or out.shape[1] != self.N:
+            raise PMFError("simulate_data: out must be a Fortran-ordered float32 array with N columns")
+        if out_row < 0 or out_row + rows > out.shape[0]:
+            raise PMFError("simulate_data: the block does not fit in out")
+        ptr = C.c_void_p(out.ctypes.data + 4 * int(out_row)) if out.size else None
+        o = self.sim_opts(seed, noise, frac_missing, row_offset)
+        self._chk(self.lib.pmf_simulate_data(self._h, C.byref(o), C.c_int64(row_start1), C.c_int64(row_stop1), ptr,
+                                             C.c_int64(out.shape[0])))
+        return out[out_row:out_row + rows]
+
+    def simulate_data_device(self, ptr, seed=0, noise=0.1, frac_missing=0.0, row_offset=0, row_start1=1, row_stop1=None,
+                             ld=None):
+        """pmf_simulate_data_device: the same into device memory at address `ptr`."""
+        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
+        ld = row_stop1 - int(row_start1) + 1 if ld is None else int(ld)
+        o = self.sim_opts(seed, noise, frac_missing, row_offset)
+        self._chk(self.lib.pmf_simulate_data_device(self._h, C.byref(o), C.c_int64(row_start1), C.c_int64(row_stop1),
+                                                    C.c_void_p(ptr), C.c_int64(ld)))
+
+    def simulate_data_resident(self, seed=0, noise=0.1, frac_missing=0.0, row_offset=0):
+        """pmf_simulate_data_resident: overwrites the data matrix resident on the device."""
+        o = self.sim_opts(seed, noise, frac_missing, row_offset)
+        self._chk(self.lib.pmf_simulate_data_resident(self._h, C.byref(o)))
 
     # ---- batch-corrected data
     @staticmethod

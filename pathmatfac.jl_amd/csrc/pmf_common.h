@@ -490,6 +490,52 @@ struct ImputeArgs {
   const float4 *thr;       // per column thresholds of the kind-3 columns
 };
 
+// ---- simulate_data (pmf_simulate.hip.inc): the seeded draws of one entry
+// Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11): ten rounds of two 32 x 32 -> 64 multiplies, the key bumped by the Weyl
+// constants between rounds.  Plain C++ for host and device: the known answers are checked on both.
+__host__ __device__ __forceinline__ void pmf_philox4x32(const uint32_t c[4], uint32_t k0, uint32_t k1, uint32_t r[4]) {
+  uint32_t c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+// The draws of entry (global 0-based row i, 0-based column j) under `seed`: counter (i_lo, i_hi, j_lo, j_hi), key (seed_lo,
+// seed_hi).  Every uniform is a 24-bit integer times 2^-24, exact in f32:
+//   n  = sqrtf(-2 logf(u1)) cosf(6.28318530718f u2), u1 = ((r0 >> 8) + 1) 2^-24 in (0, 1], u2 = (r1 >> 8) 2^-24   (want_n only)
+//   u3 = (r2 >> 8) 2^-24  the missingness draw ;  u4 = (r3 >> 8) 2^-24  the Bernoulli draw
+// logf / cosf / sqrtf are the precise library functions (the test bound on n rests on them).
+struct PmfSimDraws { float n, u3, u4; };
+__host__ __device__ __forceinline__ PmfSimDraws pmf_sim_draws(uint64_t seed, uint64_t i, uint64_t j, bool want_n) {
+  const uint32_t c[4] = {(uint32_t)i, (uint32_t)(i >> 32), (uint32_t)j, (uint32_t)(j >> 32)};
+  uint32_t r[4];
+  pmf_philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+  PmfSimDraws d;
+  d.n = 0.f;
+  if (want_n) {
+    const float u1 = (float)((r[0] >> 8) + 1u) * 5.9604644775390625e-8f, u2 = (float)(r[1] >> 8) * 5.9604644775390625e-8f;
+    d.n = sqrtf(-2.f * logf(u1)) * cosf(6.28318530718f * u2);
+  }
+  d.u3 = (float)(r[2] >> 8) * 5.9604644775390625e-8f;
+  d.u4 = (float)(r[3] >> 8) * 5.9604644775390625e-8f;
+  return d;
+}
+
+// what pmf_simulate_kernel takes beside ImputeArgs (whose flags are PMF_IMPUTE_BATCH; `out` is the resident D for the
+// tile-major store forms)
+struct SimArgs {
+  uint64_t seed;
+  int64_t row_offset;      // global row of local row 0
+  float noise, frac_missing;
+};
+#define PMF_SIM_COLMAJOR 0   // store forms: impute's column-major streaming store,
+#define PMF_SIM_TILE_F32 1   // the tile-major data layout (pmf_d_off), whole tiles with NaN pads,
+#define PMF_SIM_TILE_BF16 2  // the same as packed bf16 (pmf_d_off16)
+
 struct ImputeEntriesArgs {
   const float *X, *Y;
   const float4 *colp;
@@ -557,6 +603,8 @@ int pmf_launch_layer_map(hipStream_t stream, const LayerMapArgs &m);
 int pmf_impute_waves(int KB);   // waves per workgroup of pmf_impute_kernel: 8 up to K = 64, 4 above
 int pmf_launch_impute(PmfDynLds *cache, hipStream_t stream, int KB, bool d_bf16, int grid, const ImputeArgs &a);
 int pmf_launch_impute_entries(hipStream_t stream, const ImputeEntriesArgs &a);
+// form: PMF_SIM_COLMAJOR | PMF_SIM_TILE_F32 | PMF_SIM_TILE_BF16; grid and a.R / a.n_seg as for pmf_launch_impute
+int pmf_launch_simulate(PmfDynLds *cache, hipStream_t stream, int KB, int form, int grid, const ImputeArgs &a, const SimArgs &s);
 // src: 0 = the tile-major f32 D, 1 = the tile-major bf16 D, 2 = a column-major f32 matrix; n_cu sizes the persistent grid
 int pmf_launch_debatch(hipStream_t stream, int src, int n_cu, const DebatchArgs &a);
 int pmf_launch_debatch_entries(hipStream_t stream, const DebatchEntriesArgs &a);

@@ -32,8 +32,62 @@ struct ImputeCfg {
   }
 };
 
-template <int KB, int NW, bool DB>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(const ImputeArgs a) {
+// impute's epilogue: the inverse link of the tile's noise kind, the observed entries of D with KEEP_OBSERVED, and one
+// streaming 4-byte store per register.  An epilogue policy Epi of pmf_impute_kernel (the other one: pmf_simulate.hip.inc) has
+//   KEEP           whether PMF_IMPUTE_KEEP_OBSERVED is honoured (the D tile is loaded before the forward),
+//   finish(...)    everything after the forward and the batch step, the stores included.
+// finish sees: the accumulators (register r of lane (l31, h) = row irow, column 32 ct + pmf_rowmap(r, h)), the tile's noise
+// kind tkt (3: per column), the tile's 32 metas in LDS, the column tile ct, the row block rb, and the D tile d when keep.
+struct ImputeEpi {
+  static constexpr bool KEEP = true;
+  template <bool DB>
+  __device__ __forceinline__ void finish(f32x16 acc, const ImputeArgs &a, int tkt, const int *Cmt_t, int64_t ct, int64_t rb, int lane,
+                                         int64_t irow, bool row_ok, const PmfDTile<DB> &d, bool keep) const {
+    constexpr int BN = PMF_BN;
+    const int h = lane >> 5;
+    const int64_t N = a.N;
+    if (tkt == PMF_NOISE_BERNOULLI) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = pmf_impute_invlink(PMF_NOISE_BERNOULLI, acc[r], nullptr);
+    } else if (tkt == PMF_NOISE_POISSON) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = pmf_impute_invlink(PMF_NOISE_POISSON, acc[r], nullptr);
+    } else if (tkt == 3) {
+#pragma unroll
+      for (int c4 = 0; c4 < 4; ++c4) {
+        const int4 mt4 = *reinterpret_cast<const int4 *>(Cmt_t + 8 * c4 + 4 * h);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int meta = u == 0 ? mt4.x : (u == 1 ? mt4.y : (u == 2 ? mt4.z : mt4.w));
+          acc[4 * c4 + u] = pmf_impute_invlink(pmf_meta_kind(meta), acc[4 * c4 + u], a.thr + ct * BN + 4 * h + (8 * c4 + u));
+        }
+      }
+    }
+    if (keep) {
+      // pad rows and columns of D are NaN: they take the prediction, which the store masks
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float y = d.get(r);
+        acc[r] = pmf_finite(y) ? y : acc[r];
+      }
+    }
+    // ---- store: one streaming 4-byte store per register; a half-wave covers 128 contiguous bytes of one column
+    const int64_t rrel = irow - a.row0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int64_t j = ct * BN + pmf_rowmap(r, h);
+      if (row_ok && j < N) __builtin_nontemporal_store(acc[r], a.out + pmf_impute_off(rrel, j, a.ld));
+    }
+  }
+};
+
+// One kernel template for impute (Epi = ImputeEpi) and simulate_data (Epi = SimEpi<FORM>, pmf_simulate.hip.inc): staging, the
+// forward and the batch step are this one piece of code, so both issue the same FMAs in the same order for an entry; only
+// Epi::finish differs.  The epilogue is a kernel ARGUMENT (an empty one for impute) and the body stays in the __global__
+// function: moved into a __device__ function that both kernels call, the same text compiled to 16 to 75 more VGPRs and, at
+// K = 64, to scratch.
+template <int KB, int NW, bool DB, class Epi = ImputeEpi>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(const ImputeArgs a, const Epi epi) {
   using Cfg = ImputeCfg<KB, NW>;
   constexpr int NT = 64 * NW;
   constexpr int Kp = Cfg::Kp, KpS = Cfg::KpS, KS = Kp / 2, BN = PMF_BN, LS = PMF_LS;
@@ -48,7 +102,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(co
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, l31 = lane & 31, h = lane >> 5;
   const int64_t M = a.M, N = a.N;
-  const bool batch = (a.flags & PMF_IMPUTE_BATCH) != 0 && a.n_bv > 0, keep = (a.flags & PMF_IMPUTE_KEEP_OBSERVED) != 0;
+  const bool batch = (a.flags & PMF_IMPUTE_BATCH) != 0 && a.n_bv > 0, keep = Epi::KEEP && (a.flags & PMF_IMPUTE_KEEP_OBSERVED) != 0;
   const bool link = (a.flags & PMF_IMPUTE_LINK) != 0;
   float *Xw = Xs + w * Cfg::XP;
 
@@ -172,43 +226,13 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void pmf_impute_kernel(co
             }
           }
         }
-        if (tk[t] == PMF_NOISE_BERNOULLI) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = pmf_impute_invlink(PMF_NOISE_BERNOULLI, acc[r], nullptr);
-        } else if (tk[t] == PMF_NOISE_POISSON) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[r] = pmf_impute_invlink(PMF_NOISE_POISSON, acc[r], nullptr);
-        } else if (tk[t] == 3) {
-#pragma unroll
-          for (int c4 = 0; c4 < 4; ++c4) {
-            const int4 mt4 = *reinterpret_cast<const int4 *>(Cmt + t * 32 + 8 * c4 + 4 * h);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int meta = u == 0 ? mt4.x : (u == 1 ? mt4.y : (u == 2 ? mt4.z : mt4.w));
-              acc[4 * c4 + u] = pmf_impute_invlink(pmf_meta_kind(meta), acc[4 * c4 + u], a.thr + (int64_t)(ct0 + t) * BN + 4 * h + (8 * c4 + u));
-            }
-          }
-        }
-        if (keep) {
-          // pad rows and columns of D are NaN: they take the prediction, which the store masks
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float y = d.get(r);
-            acc[r] = pmf_finite(y) ? y : acc[r];
-          }
-        }
-        // ---- store: one streaming 4-byte store per register; a half-wave covers 128 contiguous bytes of one column
-        const int64_t rrel = irow - a.row0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int64_t j = (int64_t)(ct0 + t) * BN + pmf_rowmap(r, h);
-          if (row_ok && j < N) __builtin_nontemporal_store(acc[r], a.out + pmf_impute_off(rrel, j, a.ld));
-        }
+        epi.finish(acc, a, tk[t], Cmt + t * 32, (int64_t)(ct0 + t), rb, lane, irow, row_ok, d, keep);
       }
     }
   }
 }
 
+#ifndef PMF_IMPUTE_KERNEL_ONLY   // (pmf_k_simulate.hip takes pmf_impute_kernel alone)
 // The predictions at listed entries: one entry per lane, the dot product over K in index order, the same two rules.
 __global__ __launch_bounds__(256) void k_impute_entries(const ImputeEntriesArgs a) {
   const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -230,3 +254,4 @@ __global__ __launch_bounds__(256) void k_impute_entries(const ImputeEntriesArgs 
   }
   a.out[e] = pmf_impute_invlink((a.flags & PMF_IMPUTE_LINK) != 0 ? PMF_NOISE_NORMAL : pmf_meta_kind(meta), z, a.thr + j);
 }
+#endif

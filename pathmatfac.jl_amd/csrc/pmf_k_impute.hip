@@ -5,7 +5,7 @@
 int pmf_impute_waves(int KB) { return KB <= 2 ? 8 : 4; }
 
 int pmf_launch_impute(PmfDynLds *cache, hipStream_t stream, int KB, bool d_bf16, int grid, const ImputeArgs &a) {
-  void (*kern)(const ImputeArgs) = nullptr;
+  void (*kern)(const ImputeArgs, const ImputeEpi) = nullptr;
   size_t lds = 0;
   const bool batch = (a.flags & PMF_IMPUTE_BATCH) != 0 && a.n_bv > 0;
   // the storage type of D matters to PMF_IMPUTE_KEEP_OBSERVED alone
@@ -20,7 +20,7 @@ int pmf_launch_impute(PmfDynLds *cache, hipStream_t stream, int KB, bool d_bf16,
   }
 #undef PMF_IK
   PMFCHK(pmf_ensure_dyn_lds(cache, (const void *)kern, lds));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * pmf_impute_waves(KB)), lds, stream, a);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * pmf_impute_waves(KB)), lds, stream, a, ImputeEpi{});
   HIPCHK(hipGetLastError());
   return 0;
 }

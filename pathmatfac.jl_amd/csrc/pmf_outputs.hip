@@ -1,5 +1,5 @@
-// pmf_outputs.hip -- what a fitted model gives back: pmf_forward / pmf_synth_data (k_forward), pmf_impute* (pmf_impute.hip.inc)
-// and pmf_remove_batch_effect* (pmf_debatch.hip.inc) with the one host path their staged calls share.
+// pmf_outputs.hip -- what a fitted model gives back: pmf_forward / pmf_synth_data (k_forward), pmf_impute* (pmf_impute.hip.inc),
+// pmf_simulate_data* (pmf_simulate.hip.inc) and pmf_remove_batch_effect* (pmf_debatch.hip.inc) with the one host path their staged calls share.
 #include "pmf_ctx.h"
 
 // Z = layers(X'Y) materialised (MF.forward, simulate_params.jl:247); also used by pmf_synth_data.
@@ -191,24 +191,33 @@ static int impute_check_range(pmf_ctx *c, const char *fn, int64_t s1, int64_t e1
   return 0;
 }
 
-// rows [row0, row1) (0-based) into out_dev (leading dimension ld); prepare() has run
-static int impute_launch(pmf_ctx *c, int flags, int64_t row0, int64_t row1, float *out_dev, int64_t ld) {
+// The arguments and the grid of a sweep (pmf_impute_kernel, pmf_simulate_kernel) over rows [row0, row1) (0-based) and n_ct
+// column tiles; prepare() has run.
+static int impute_args(pmf_ctx *c, const char *fn, int flags, int64_t row0, int64_t row1, int64_t n_ct, float *out_dev, int64_t ld,
+                       ImputeArgs &a, int &grid) {
   const int nw = pmf_impute_waves(c->KB);
   const int64_t BM = 32 * nw;
-  ImputeArgs a;
   memset(&a, 0, sizeof(a));
   a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.thr = c->thr; a.bor = c->bor; a.btab = c->btab; a.views = c->d_views;
   a.D = c->D; a.nRB = c->nRB; a.out = out_dev; a.ld = ld; a.M = c->M; a.N = c->N; a.row0 = row0; a.row1 = row1;
   a.rp0 = row0 / BM;
   a.n_rp = (row1 - 1) / BM + 1 - a.rp0;
   a.n_bv = c->n_bv; a.flags = flags;
-  const int64_t n_ct = (c->N + PMF_BN - 1) / PMF_BN, n_seg = (n_ct + PMF_LS - 1) / PMF_LS;
-  if (n_ct >= (1ll << 31)) return pmf_fail("pmf_impute: N too large");
+  const int64_t n_seg = (n_ct + PMF_LS - 1) / PMF_LS;
+  if (n_ct >= (1ll << 31)) return pmf_fail("%s: N too large", fn);
   // a unit = (column segment, 1/R of the panels); R as in the layer pass: a few units per CU, consecutive units share a segment
   const int64_t R = std::max<int64_t>(1, std::min<int64_t>(a.n_rp, (4ll * c->n_cu + n_seg - 1) / n_seg));
   a.n_ct = (int)n_ct; a.n_seg = (int)n_seg; a.R = (int)R;
-  if (n_seg * R >= (1ll << 31)) return pmf_fail("pmf_impute: too many units");
-  const int grid = (int)std::min<int64_t>(n_seg * R, c->n_cu);
+  if (n_seg * R >= (1ll << 31)) return pmf_fail("%s: too many units", fn);
+  grid = (int)std::min<int64_t>(n_seg * R, c->n_cu);
+  return 0;
+}
+
+// rows [row0, row1) (0-based) into out_dev (leading dimension ld); prepare() has run
+static int impute_launch(pmf_ctx *c, int flags, int64_t row0, int64_t row1, float *out_dev, int64_t ld) {
+  ImputeArgs a;
+  int grid = 0;
+  PMFCHK(impute_args(c, "pmf_impute", flags, row0, row1, (c->N + PMF_BN - 1) / PMF_BN, out_dev, ld, a, grid));
   return pmf_launch_impute(&c->dyn_lds, c->stream, c->KB, c->store == PMF_STORE_BF16, grid, a);
 }
 
@@ -240,6 +249,71 @@ extern "C" int pmf_impute_entries(pmf_ctx *c, int flags, int64_t n, const int64_
                           a.rows1 = d_rows; a.cols1 = d_cols; a.out = d_out; a.n = ne; a.M = c->M; a.Kp = c->Kp; a.K = c->K; a.flags = flags;
                           return pmf_launch_impute_entries(c->stream, a);
                         });
+}
+
+// ------------------------------------------------------------------------------------------------
+// simulate_data! (src/simulate_params.jl:219-251): seeded draws from the current parameters (pmf_simulate.hip.inc)
+// ------------------------------------------------------------------------------------------------
+// what every call checks before it touches the device
+static int simulate_check(pmf_ctx *c, const char *fn, const pmf_sim_opts *o) {
+  if (!o) return pmf_fail("%s: null options", fn);
+  if (!(o->noise >= 0.f) || !std::isfinite(o->noise)) return pmf_fail("%s: noise=%g must be finite and >= 0", fn, (double)o->noise);
+  if (!(o->frac_missing >= 0.f && o->frac_missing <= 1.f)) return pmf_fail("%s: frac_missing=%g is outside [0, 1]", fn, (double)o->frac_missing);
+  if (o->row_offset < 0) return pmf_fail("%s: row_offset=%lld is negative", fn, (long long)o->row_offset);
+  PMFCHK(outputs_ready(c, fn));
+  for (size_t j = 0; j < c->h_kind.size(); ++j)
+    if ((c->h_kind[j] & 3) == PMF_NOISE_POISSON)
+      return pmf_fail("%s: column %lld has Poisson noise, for which there is no sampler", fn, (long long)(j + 1));
+  return 0;
+}
+
+// rows [row0, row1) (0-based) in store form `form`: into out_dev (column-major, leading dimension ld) or the resident D
+static int simulate_launch(pmf_ctx *c, const pmf_sim_opts *o, int form, int64_t row0, int64_t row1, float *out_dev, int64_t ld) {
+  ImputeArgs a;
+  int grid = 0;
+  // the tile-major forms write every column tile of D, the all-pad one of an odd tile count included
+  const int64_t n_ct = form == PMF_SIM_COLMAJOR ? (c->N + PMF_BN - 1) / PMF_BN : c->D_Npad / PMF_BN;
+  PMFCHK(impute_args(c, "pmf_simulate_data", PMF_IMPUTE_BATCH, row0, row1, n_ct, out_dev, ld, a, grid));
+  SimArgs s;
+  s.seed = o->seed; s.row_offset = o->row_offset; s.noise = o->noise; s.frac_missing = o->frac_missing;
+  return pmf_launch_simulate(&c->dyn_lds, c->stream, c->KB, form, grid, a, s);
+}
+
+extern "C" int pmf_simulate_data_device(pmf_ctx *c, const pmf_sim_opts *opts, int64_t row_start1, int64_t row_stop1, float *out_device,
+                                        int64_t ld) {
+  static const char *fn = "pmf_simulate_data_device";
+  PMFCHK(ctx_bind(c));
+  if (!out_device) return pmf_fail("%s: null output pointer", fn);
+  PMFCHK(simulate_check(c, fn, opts));
+  PMFCHK(impute_check_range(c, fn, row_start1, row_stop1, ld));
+  PMFCHK(prepare(c));
+  PMFCHK(simulate_launch(c, opts, PMF_SIM_COLMAJOR, row_start1 - 1, row_stop1, out_device, ld));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+extern "C" int pmf_simulate_data(pmf_ctx *c, const pmf_sim_opts *opts, int64_t row_start1, int64_t row_stop1, float *out_host, int64_t ld) {
+  static const char *fn = "pmf_simulate_data";
+  PMFCHK(ctx_bind(c));
+  if (!out_host) return pmf_fail("%s: null output pointer", fn);
+  PMFCHK(simulate_check(c, fn, opts));
+  PMFCHK(impute_check_range(c, fn, row_start1, row_stop1, ld));
+  return staged_rows(c, row_start1 - 1, row_stop1, 1, "PMF_SIMULATE_CHUNK_ROWS", nullptr, 0, out_host, ld,
+                     [&](int64_t r0, int64_t r1, const float *, float *s_out, int64_t nr) {
+                       return simulate_launch(c, opts, PMF_SIM_COLMAJOR, r0, r1, s_out, nr);
+                     });
+}
+
+extern "C" int pmf_simulate_data_resident(pmf_ctx *c, const pmf_sim_opts *opts) {
+  static const char *fn = "pmf_simulate_data_resident";
+  PMFCHK(ctx_bind(c));
+  PMFCHK(simulate_check(c, fn, opts));
+  if (!c->D) return pmf_fail("%s: data buffer not allocated (pmf_set_data_device(ctx, NULL, M, N, store) or pmf_set_data)", fn);
+  PMFCHK(prepare(c));
+  c->tflags_valid = false;   // what pmf_set_data invalidates: the per-tile all-finite flags of the old values
+  PMFCHK(simulate_launch(c, opts, c->store == PMF_STORE_BF16 ? PMF_SIM_TILE_BF16 : PMF_SIM_TILE_F32, 0, c->M, (float *)c->D.p, c->M));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
 }
 
 extern "C" int pmf_debug_impute_offset(int64_t row, int64_t col, int64_t ld, int64_t *offset) {

@@ -68,6 +68,10 @@ mutable struct EmResult   # pmf_em_result
     iters::Cint; n_diffs::Cint; diffs_cap::Cint; reserved::Cint; diffs::Ptr{Cdouble}; seconds::Cdouble
 end
 
+struct SimOpts            # pmf_sim_opts
+    seed::UInt64; row_offset::Int64; noise::Cfloat; frac_missing::Cfloat
+end
+
 lasterr() = unsafe_string(ccall((:pmf_last_error, LIB[]), Cstring, ()))
 chk(rc::Integer) = rc == 0 ? nothing : error("libpmf_hip: " * lasterr())
 f32(a) = convert(Array{Float32}, a)
@@ -755,6 +759,30 @@ function remove_batch_effect(model::PM.PathMatFacModel, Z::AbstractMatrix; link=
     return out
 end
 
+"""simulate_data!(model; noise=0.1) (src/simulate_params.jl:244-255) on the device: model.data is overwritten by a draw from
+the model's current parameters (pmf_simulate_data: the forward of all four layers, normal noise on the normal columns, the
+class of the noise-free value on the squared-hinge columns, a 0 / 1 draw on logit-Bernoulli columns; a Poisson range is
+refused).  `seed` fixes the Philox4x32-10 stream, `frac_missing` of the entries become NaN, `row_offset` is the global
+index of the first local row of a row shard.  `resident=true` draws into the device's copy instead (pmf_simulate_data_resident)
+and leaves model.data alone.  Returns model.data."""
+function simulate_data!(model::PM.PathMatFacModel; noise=0.1, seed::Integer=0, frac_missing=0.0, row_offset::Integer=0,
+                        resident::Bool=false, kwargs...)
+    ctx = context!(model)
+    marshal!(ctx, model.matfac)
+    opts = Ref(SimOpts(UInt64(seed), Int64(row_offset), Cfloat(noise), Cfloat(frac_missing)))
+    if resident
+        chk(ccall((:pmf_simulate_data_resident, LIB[]), Cint, (Ptr{Cvoid}, Ref{SimOpts}), ctx, opts))
+        return model.data
+    end
+    M, N = size(model.data)
+    out = zeros(Float32, M, N)
+    GC.@preserve out chk(ccall((:pmf_simulate_data, LIB[]), Cint, (Ptr{Cvoid}, Ref{SimOpts}, Int64, Int64, Ptr{Cfloat}, Int64),
+                               ctx, opts, 1, M, out, M))
+    model.data .= out
+    delete!(DATA_KEY, model)      # the device copy is of the old values: the next context!(model) uploads the new ones
+    return model.data
+end
+
 """Point PathMatFac's drop-in boundary at the HIP library."""
 function install!(libpath::AbstractString="libpmf_hip.so")
     LIB[] = libpath
@@ -772,6 +800,7 @@ function install!(libpath::AbstractString="libpmf_hip.so")
     @eval PathMatFac reweight_eb!(reg::L2Regularizer, X::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.reweight_eb!(reg, X; kwargs...)
     @eval PathMatFac reweight_eb!(reg::GroupRegularizer, X::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.reweight_eb!(reg, X; kwargs...)
     @eval PathMatFac remove_batch_effect(model::PathMatFacModel, Z::AbstractMatrix; kwargs...) = Main.PathMatFacHIP.remove_batch_effect(model, Z; kwargs...)
+    @eval PathMatFac simulate_data!(model::PathMatFacModel; kwargs...) = Main.PathMatFacHIP.simulate_data!(model; kwargs...)
     return nothing
 end
 
