@@ -3,7 +3,8 @@
 output, repeated calls, history of the context, precision mode, and a fit before or after.
 
 pmf_impute_kernel<KB, NW, DB> works on absolute 32-row blocks in panels of 32 NW rows (NW = 8 up to K = 64, 4 above) and
-units of two 32-column tiles; the shapes below sit on those edges."""
+units of two 32-column tiles; the shapes below sit on those edges.  They all leave the persistent grid at one unit per
+workgroup and one panel per unit: the unit and grid edges live in tests/test_gpu_output_grid.py."""
 import ctypes as C
 
 import numpy as np

@@ -3,7 +3,9 @@ pmf_impute's bit for bit, the uniforms (missing mask, Bernoulli draws) are the t
 bound, and an entry depends on (parameters, seed, global row, column, noise, frac_missing) alone.
 
 The kernel is pmf_impute_kernel with a sampling epilogue: absolute 32-row blocks in panels of 32 NW rows (NW = 8 up to
-K = 64, 4 above), units of two 32-column tiles; the shapes are impute_ref.CASES, which sit on those edges."""
+K = 64, 4 above), units of two 32-column tiles; the shapes are impute_ref.CASES, which sit on those edges.  The unit and grid
+edges (several units per workgroup, several panels per unit), rows past 2^32 and a seed with both words set live in
+tests/test_gpu_output_grid.py."""
 import ctypes as C
 
 import numpy as np
