@@ -348,8 +348,11 @@ int pmf_comm_info(pmf_ctx *ctx, int *rank, int *nranks, int *transport, int *n_c
  * gathers), the last layer pass (1 MFMA layer pass, 2 VALU kernel) and the columns of the dense batch table as of the
  * last prepared epoch (16 without batch views, 0 when a view has more than 255 batches and no table is built).  Views with
  * more than 15 batches stay on variant 1 as long as no 256-row (128-row for K > 64) panel holds more than 15 distinct
- * batches of one view (src/batch_array.jl:78-147 places no bound on the batch count). */
-int pmf_debug_last_path(pmf_ctx *ctx, int *bmode, int *layer_path, int *slots);
+ * batches of one view (src/batch_array.jl:78-147 places no bound on the batch count).
+ * xreg: 1 when the last fused launch ran an instance of the exact kernel that holds a piece's X operands in registers
+ * (32 < K <= 64, both gradients, PMF_XREG unset or non-zero), 0 when it read them from LDS per tile; the two are
+ * bit-identical in every result, so this field is the only way to tell which one ran.  Any out-pointer may be null. */
+int pmf_debug_last_path(pmf_ctx *ctx, int *bmode, int *layer_path, int *slots, int *xreg);
 /* the kernel family the last fused data pass ran on: 0 exact f32 (pmf_fused_kernel), 1 pmf_fused_sb_kernel, 2 pmf_fused_sb2_kernel,
  * 4 pmf_fused_sb4_kernel, 8 pmf_fused_sb8_kernel (split modes; tests assert that the intended variant really ran) */
 int pmf_debug_last_kernel(pmf_ctx *ctx, int *kernel);

@@ -932,10 +932,10 @@ class Context:
                     reserved_cus=cu.value, n_collectives=nc.value)
 
     def last_path(self):
-        """Batch-layer variants of the last launches: dict(bmode=0|1|2, layer_path=0|1|2, slots=...), see pmf_hip.h."""
-        b, l, s = C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(self.lib.pmf_debug_last_path(self._h, C.byref(b), C.byref(l), C.byref(s)))
-        return dict(bmode=b.value, layer_path=l.value, slots=s.value)
+        """Variants of the last launches: dict(bmode=0|1|2, layer_path=0|1|2, slots=..., xreg=0|1), see pmf_hip.h."""
+        b, l, s, x = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        self._chk(self.lib.pmf_debug_last_path(self._h, C.byref(b), C.byref(l), C.byref(s), C.byref(x)))
+        return dict(bmode=b.value, layer_path=l.value, slots=s.value, xreg=x.value)
 
     def last_kernel(self):
         """Kernel family of the last fused data pass: 0 exact, 1 / 2 / 4 / 8 the split kernels sb / sb2 / sb4 / sb8."""

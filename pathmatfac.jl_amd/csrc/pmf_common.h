@@ -588,6 +588,9 @@ typedef int PmfFusedLaunch(PmfDynLds *cache, hipStream_t stream, const FusedArgs
 PmfFusedLaunch pmf_launch_fused_exact_11, pmf_launch_fused_exact_12, pmf_launch_fused_exact_21, pmf_launch_fused_exact_31,
     pmf_launch_fused_exact_41, pmf_launch_fused_exact_11_bf16, pmf_launch_fused_exact_12_bf16, pmf_launch_fused_exact_21_bf16,
     pmf_launch_fused_exact_31_bf16, pmf_launch_fused_exact_41_bf16;
+// Set to 1 by an exact launcher that picked a register-resident-X instance (launch_fused_chunk clears it before the launch
+// and copies it to the context afterwards: pmf_debug_last_path).
+extern thread_local int pmf_last_xreg;
 PmfFusedLaunch pmf_launch_fused_sb_1, pmf_launch_fused_sb_2, pmf_launch_fused_sb_1_bf16, pmf_launch_fused_sb_2_bf16;
 PmfFusedLaunch pmf_launch_fused_sb2, pmf_launch_fused_sb2_bf16;
 PmfFusedLaunch pmf_launch_fused_sb4_3, pmf_launch_fused_sb4_4, pmf_launch_fused_sb4_3_bf16, pmf_launch_fused_sb4_4_bf16;

@@ -206,7 +206,7 @@ struct pmf_ctx {
   PanelSlots pslots[3];           // panel-local batch slots for row panels of 128 / 256 / 512 rows (ensure_panel_slots)
   int64_t views_serial = 0;       // bumped whenever a view's rows / shape change
   int last_kernel = 0;            // fused kernel family of the last data pass (pmf_debug_last_kernel)
-  int last_bmode = 0, last_layer_path = 0;   // diagnostics (pmf_debug_last_path)
+  int last_bmode = 0, last_layer_path = 0, last_xreg = 0;   // diagnostics (pmf_debug_last_path)
   DevBuf<int32_t> d_val_view;     // per flat value element: view id
   // noise model / prepared column parameters
   DevBuf<int32_t> colmeta;     // kind | (view+1)<<2

@@ -27,7 +27,8 @@
 //   the kernel; global atomics per tile, 10.6 % of the wave time in issue stalls -- the CU retires one 256-B
 //   atomic instruction per ~120 cycles.)
 //   The X fragments live in a wave-private LDS panel rather than in VGPRs: with them in registers hipcc ran out
-//   of VGPRs and serialised every LDS read behind s_waitcnt 0 (profiles/, DESIGN.md).
+//   of VGPRs and serialised every LDS read behind s_waitcnt 0 (profiles/, DESIGN.md).  That was the slab path at 254
+//   VGPRs; the cross-wave instances below that have the room hold them in registers (XR).
 //   Both outputs have lane = factor index k, so every global access is a full 128-B row segment.
 //   What bounds the kernel (profiles/r1_micro_mfma_valu.txt): v_mfma_f32_32x32x2_f32 runs at exactly the packed-f32
 //   VALU rate and does NOT co-execute with VALU instructions -- every VALU instruction issued by either wave of a
@@ -39,6 +40,15 @@
 // one 16 k x 16 j block of gY over all 256 rows of the panel with v_mfma_f32_16x16x4_f32 (A = the X panels, B = the G
 // tiles, both b32 LDS reads), scales it by sigma_j and adds it straight to the private gY slab in HBM.  No per-wave
 // slabs, no 8-way reduction between the forward's MFMAs and no second barrier (DESIGN.md section 4.1).
+//
+// XR (on XW instances that stay within 256 VGPRs without scratch: pmf_k_fused.hip, pmf_xreg_instance) holds a piece's X
+// operands in registers.  They do not change within a piece, yet the XW loop read them from LDS for every tile: 8
+// ds_read_b128 for the forward's B operand and 32 ds_read2st64_b32 for GEMM3's A operand, 40 of its 105 LDS reads and
+// 24 KiB of the ~64 KiB a wave reads per tile.  With XR each wave reads both fragments once, after the piece prologue's
+// barrier (the panels are still staged through LDS: that is how a wave gets the other waves' rows), and every MFMA takes
+// the same values in the same order from registers: loss, gX and gY are bit-identical, 96 more VGPRs (144 -> 239 in the
+// headline instance), 65 LDS reads per tile and wave.  PMF_XREG=0 (read at every pass) selects the LDS-read instance;
+// pmf_debug_last_path's xreg tells which one ran.
 
 // RBW = 32-row blocks per wave.  RBW = 2 amortises everything that is per (wave, tile) but not per row -- the slab
 // write, the cross-wave reduction, the Y staging, the barriers -- over twice the MFMA work; it is used where that
@@ -71,10 +81,14 @@ struct FusedCfg {
 // steady-state loop is branch-free apart from the loop itself, which lets hipcc emit exact counted s_waitcnt vmcnt(N)
 // instead of draining the queue at every join (the run-time variant measured 2x slower on grad(Y)-only epochs).
 // BMODE: 0 = no batch layers, 1 = batch tables staged through LDS (<= 15 batches per view), 2 = global gathers
-template <int KB, int NW, int RBW, int BMODE, bool MIXED, int GM, bool DB, bool XW = false>
+template <int KB, int NW, int RBW, int BMODE, bool MIXED, int GM, bool DB, bool XW = false, bool XR = false>
 __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fused_kernel(const FusedArgs a) {
   using Cfg = FusedCfg<KB, NW, RBW>;
   constexpr bool FULL = GM != 3;   // no run-time flags
+  // (XW) The two instances that would otherwise need scratch (D stored as bf16, mixed noise models and batch layers: 1 and 7
+  // spilled registers at the 256 of two waves per SIMD): they give up the launch-long pinned addressing -- HOIST below
+  // and the GEMM3 read bases, which they recompute per tile (~30 VALU) -- for 16 registers.  Same addresses, same results.
+  constexpr bool TIGHT = XW && DB && MIXED && BMODE != 0;
   constexpr bool BATCH = BMODE != 0;
   constexpr bool bt_lds = BMODE == 1;
   constexpr int Kp = Cfg::Kp;
@@ -90,6 +104,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
   constexpr int NBT = (BN * 16 + NT - 1) / NT;     // float2 of the dense batch table per thread and tile
   static_assert(!XW || (KB == 2 && NW == 8 && RBW == 1 && GM == 0 && NYB == 2 && RV4 == 1 && 2 * NW * 1024 <= NW * SLAB),
                 "cross-wave GEMM3: 8 waves x one row block, Kp = 64, both gradients");
+  static_assert(!XR || XW, "register-resident X fragments: the cross-wave GEMM3 instances only");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float *Ys = reinterpret_cast<float *>(smem);        // [NYB][BN*KpS]      sigma_j * Y[k,j]
@@ -143,7 +158,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     const int i = 4 * (lane >> 4) + u;
     xw_g[u] = i * 32 + 4 * ((xw_j >> 2) ^ (i & 7)) + (xw_j & 3);
     xw_xa[u] = (unsigned)(uintptr_t)(lds_cptr)(Xs + xw_x + u * KpS);
-    if (XW) asm volatile("" : "+v"(xw_xa[u]));
+    if (XW && !TIGHT) asm volatile("" : "+v"(xw_xa[u]));
   }
 
   // (HOIST: the KB = 2 instances) Tile-invariant addressing.  The lane-dependent part of the Y, column-parameter and
@@ -151,9 +166,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
   // (the clamps that keep dead columns' loads in bounds).  Both sets are byte offsets computed once per launch and
   // pinned in registers; a tile selects one by a wave-uniform condition and adds it to a scalar base, so that a load
   // costs one VALU instruction instead of the clamp, the shifts and a 64-bit add.
-  // (Not where the eight registers would only add to an instance's spills: the run-time-flag builds and the per-wave-slab
-  // builds with batch layers, which already exceed the 256-register budget.)
-  constexpr bool HOIST = KB == 2 && NW == 8 && RBW == 1 && GM != 3 && (XW || GM != 0 || BMODE == 0);
+  // (Not where the eight registers would only add to an instance's spills: the run-time-flag builds, the per-wave-slab
+  // builds with batch layers, which already exceed the 256-register budget, and the TIGHT cross-wave builds.)
+  constexpr bool HOIST = KB == 2 && NW == 8 && RBW == 1 && GM != 3 && !TIGHT && (XW || GM != 0 || BMODE == 0);
   unsigned ho_y[2][YV], ho_s[2][YV], ho_c[2], ho_g[2][RV4];
   if (HOIST) {
 #pragma unroll
@@ -254,6 +269,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) gx[rb][kb][r] = 0.f;
+    // (XR) the X values this wave multiplies by do not change within a piece: both fragments are read from the panels
+    // once, after the prologue's barrier, and stay in registers for all of its tiles (every index a compile-time constant)
+    //   xf[q]: the forward's B operand of k-steps 4 q .. 4 q + 3 (this lane's row, its half of k)
+    //   xg[q]: the cross-wave GEMM3's A operand of step q = 8 p + 2 u + hi
+    float4 xf[XR ? KS / 4 : 1];
+    float xg[XR ? 8 * NW : 1];
 
     // Y tile staging: global -> registers -> (scaled by sigma_j) -> LDS.  The scaling is applied at store time so
     // that nothing waits on the loads when they are issued.
@@ -384,7 +405,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
 #pragma unroll
       for (int rb = 0; rb < RBW; ++rb) {
         xr[rb] = reinterpret_cast<const float4 *>(Xw[rb] + l31 * KpS + h * (Kp / 2));
-        xv[rb] = xr[rb][0];
+        xv[rb] = XR ? xf[0] : xr[rb][0];
       }
       constexpr int NIT = KS / 4, RTOT = NW * RV4, RPI = (RTOT + NIT - 1) / NIT;
       float4 racc[RV4];
@@ -403,7 +424,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
         if (q + 1 < NIT) {
           yn = yr[q + 1];
 #pragma unroll
-          for (int rb = 0; rb < RBW; ++rb) xn[rb] = xr[rb][q + 1];
+          for (int rb = 0; rb < RBW; ++rb) xn[rb] = XR ? xf[XR ? q + 1 : 0] : xr[rb][q + 1];
         }
         if (do_red) {
 #pragma unroll
@@ -492,6 +513,16 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       }
     }
     __syncthreads();
+    if (XR) {
+      const float4 *xr0 = reinterpret_cast<const float4 *>(Xw[0] + l31 * KpS + h * (Kp / 2));
+#pragma unroll
+      for (int q = 0; q < KS / 4; ++q) xf[XR ? q : 0] = xr0[q];
+#pragma unroll
+      for (int q = 0; q < 8 * NW; ++q) {
+        const int p = q >> 3, u = (q >> 1) & 3, hi = q & 1;
+        xg[XR ? q : 0] = *(lds_cptr)(uintptr_t)(xw_xa[u] + 4 * (p * Cfg::XP + 16 * hi * KpS));
+      }
+    }
 
     f32x16 acc[RBW];
     forward_reduce(acc, 0, 0, false, 0);
@@ -780,15 +811,27 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
         typedef float f32x4 __attribute__((ext_vector_type(4)));
         constexpr int XW_RING = 8, XW_AHEAD = 6;
         const float *Gp = Sl + par * (NW * 1024);
-        float xa[XW_RING], xb[XW_RING];
+        int xt_g[4];        // (TIGHT) xw_g / xw_xa again, from a lane id the compiler cannot hoist out of the tile loop
+        unsigned xt_xa[4];
+        if (TIGHT) {
+          int lo = lane;
+          asm volatile("" : "+v"(lo));
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const int i = 4 * (lo >> 4) + u, j = 16 * (w & 1) + (lo & 15);
+            xt_g[u] = i * 32 + 4 * ((j >> 2) ^ (i & 7)) + (j & 3);
+            xt_xa[u] = (unsigned)(uintptr_t)(lds_cptr)(Xs + 4 * (lo >> 4) * KpS + 16 * (w >> 1) + (lo & 15) + u * KpS);
+          }
+        }
+        float xa[XW_RING], xb[XW_RING];   // (XR: xa is unused, the A operand of step q is xg[q])
         // steps q = 8 p + 2 u + hi: rows i and i + 16 of one block are read together -- both strides (16 rows of X or G, one
         // block of either) are multiples of 256 B, so every read is one half of a ds_read2st64_b32 off four bases per operand
         auto xw_read = [&](int q) __attribute__((always_inline)) {
           const int p = q >> 3, u = (q >> 1) & 3;
 #pragma unroll
           for (int hi = 0; hi < 2; ++hi) {
-            xa[(q + hi) % XW_RING] = *(lds_cptr)(uintptr_t)(xw_xa[u] + 4 * (p * Cfg::XP + 16 * hi * KpS));
-            xb[(q + hi) % XW_RING] = Gp[p * 1024 + xw_g[u] + 512 * hi];
+            if (!XR) xa[(q + hi) % XW_RING] = *(lds_cptr)(uintptr_t)((TIGHT ? xt_xa[u] : xw_xa[u]) + 4 * (p * Cfg::XP + 16 * hi * KpS));
+            xb[(q + hi) % XW_RING] = Gp[p * 1024 + (TIGHT ? xt_g[u] : xw_g[u]) + 512 * hi];
           }
         };
 #pragma unroll
@@ -798,8 +841,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
 #pragma unroll
         for (int q = 0; q < 8 * NW; q += 2) {
           if (q + XW_AHEAD < 8 * NW) xw_read(q + XW_AHEAD);
-          gy0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q % XW_RING], xb[q % XW_RING], gy0, 0, 0, 0);
-          gy1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[(q + 1) % XW_RING], xb[(q + 1) % XW_RING], gy1, 0, 0, 0);
+          gy0 = __builtin_amdgcn_mfma_f32_16x16x4f32(XR ? xg[XR ? q : 0] : xa[q % XW_RING], xb[q % XW_RING], gy0, 0, 0, 0);
+          gy1 = __builtin_amdgcn_mfma_f32_16x16x4f32(XR ? xg[XR ? q + 1 : 0] : xa[(q + 1) % XW_RING], xb[(q + 1) % XW_RING], gy1, 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
         }
         // make the (long finished) D loads count as consumed BEFORE the store below is issued: otherwise the next
@@ -828,7 +871,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
         PMF_STAMP(9);   // B2 wait
       }
     }
-    // (XW) the next piece's prologue overwrites this wave's X panel, which the other waves read in the last GEMM3
+    // (XW) the next piece's prologue overwrites this wave's X panel, which the other waves read in the last GEMM3.
+    // (XR) The panels are read only right after the prologue's barrier, but this barrier protects more than them: the
+    // next piece's first epilogue writes G tile parity 0 and its stage_store writes Y buffer 0, both of which slower
+    // waves may still be reading in their last GEMM3 and forward.
     if (XW && !bt_lds) __syncthreads();
 
     PMF_STAMP(10);

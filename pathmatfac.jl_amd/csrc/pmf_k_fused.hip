@@ -8,6 +8,11 @@
 #endif
 #include "pmf_common.h"
 #include "pmf_fused.hip.inc"
+// Which cross-wave-GEMM3 instances (batch mode, mixed noise, bf16 D storage) keep their X fragments in registers: those
+// whose build has no scratch and at most 256 VGPRs with the 96 extra registers; the others keep the LDS reads.
+// Measured on the builds: single-model Gaussian columns without batch layers hold them at 239
+// (f32 D) / 241 (bf16 D) VGPRs; every other instance starts from 175 .. 256 and would spill 5 .. 92 registers.
+static constexpr bool pmf_xreg_instance(int bmode, bool mixed, bool db) { return bmode == 0 && !mixed; }
 template <int KB, int NW, int RBW>
 static int launch_fused_t(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed) {
   using Cfg = FusedCfg<KB, NW, RBW>;
@@ -29,9 +34,17 @@ static int launch_fused_t(PmfDynLds *cache, hipStream_t stream, const FusedArgs 
   if constexpr (KB == 2 && NW == 8 && RBW == 1) {
     const char *xe = getenv("PMF_XGEMM3");
     if (gm == 0 && !(xe && atoi(xe) == 0)) {
-#define PMF_PICK_XW(BM) (mixed ? pmf_fused_kernel<KB, NW, RBW, BM, true, 0, PMF_DB != 0, true> : pmf_fused_kernel<KB, NW, RBW, BM, false, 0, PMF_DB != 0, true>)
+      // register-resident X fragments (XR): the instances that hold them without scratch inside the 256 registers of two
+      // waves per SIMD (pmf_xreg_instance; DESIGN.md section 4.1 has the counts).  PMF_XREG=0 (read at every pass) keeps
+      // the per-tile LDS reads: same MFMAs on the same values, bit-identical results.
+      const char *re = getenv("PMF_XREG");
+      const bool xr = !(re && atoi(re) == 0);
+#define PMF_PICK_XR(BM, MX) (xr && pmf_xreg_instance(BM, MX, PMF_DB != 0) ? (pmf_last_xreg = 1, pmf_fused_kernel<KB, NW, RBW, BM, MX, 0, PMF_DB != 0, true, pmf_xreg_instance(BM, MX, PMF_DB != 0)>) \
+                                                                          : pmf_fused_kernel<KB, NW, RBW, BM, MX, 0, PMF_DB != 0, true>)
+#define PMF_PICK_XW(BM) (mixed ? PMF_PICK_XR(BM, true) : PMF_PICK_XR(BM, false))
       kern = bmode == 0 ? PMF_PICK_XW(0) : (bmode == 1 ? PMF_PICK_XW(1) : PMF_PICK_XW(2));
 #undef PMF_PICK_XW
+#undef PMF_PICK_XR
     }
   }
   PMFCHK(pmf_ensure_dyn_lds(cache, (const void *)kern, lds));

@@ -664,7 +664,9 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   auto &ev = c->ev_pool[c->ev_used++];
   HIPCHK(hipEventRecord(ev.first, c->stream));
   c->last_kernel = f.kernel;
+  pmf_last_xreg = 0;
   const int rc = f.launch[c->store == PMF_STORE_BF16](&c->dyn_lds, c->stream, a, grid, batch, c->mixed);
+  c->last_xreg = pmf_last_xreg;
   if (f.kernel != 0) c->sb_launches += 1;
   PMFCHK(rc);
   HIPCHK(hipEventRecord(ev.second, c->stream));   // the events bracket pmf_fused_kernel alone (= rocprofv3's kernel duration)
@@ -694,15 +696,18 @@ int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy) {
 
 // Which batch-layer variants the last launches took (tests and benchmarks: a silent fall-back to the slow paths is a
 // performance bug).  bmode: 0 none, 1 LDS table with panel-local slots, 2 per-entry gathers; layer_path: 1 MFMA layer
-// pass, 2 VALU layer kernel; slots: columns of the dense batch table.
+// pass, 2 VALU layer kernel; slots: columns of the dense batch table; xreg: 1 = the last fused launch held its X
+// fragments in registers (the only way to tell: its results are bit-identical to the LDS-read instance's).
+thread_local int pmf_last_xreg = 0;
 extern "C" int pmf_debug_last_kernel(pmf_ctx *c, int *kernel) {
   if (!c) return pmf_fail("null context");
   if (kernel) *kernel = c->last_kernel;
   return 0;
 }
 
-extern "C" int pmf_debug_last_path(pmf_ctx *c, int *bmode, int *layer_path, int *slots) {
+extern "C" int pmf_debug_last_path(pmf_ctx *c, int *bmode, int *layer_path, int *slots, int *xreg) {
   if (!c) return pmf_fail("null context");
+  if (xreg) *xreg = c->last_xreg;
   if (bmode) *bmode = c->last_bmode;
   if (layer_path) *layer_path = c->last_layer_path;
   if (slots) *slots = c->nbs;
