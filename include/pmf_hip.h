@@ -351,14 +351,21 @@ int pmf_comm_info(pmf_ctx *ctx, int *rank, int *nranks, int *transport, int *n_c
  * batches of one view (src/batch_array.jl:78-147 places no bound on the batch count).
  * xreg: 1 when the last fused launch ran an instance of the exact kernel that holds a piece's X operands in registers
  * (32 < K <= 64, both gradients, PMF_XREG unset or non-zero), 0 when it read them from LDS per tile; the two are
- * bit-identical in every result, so this field is the only way to tell which one ran.  Any out-pointer may be null. */
-int pmf_debug_last_path(pmf_ctx *ctx, int *bmode, int *layer_path, int *slots, int *xreg);
+ * bit-identical in every result, so this field is the only way to tell which one ran.
+ * plain_tiles: the (row panel, column tile) pairs the last data pass ran in the plain tile loop of those instances (runs of
+ * all-finite, full, already visited tiles; 0 under PMF_PLAIN=0, read at every pass, and for every other kernel); again
+ * bit-identical, and counted by the kernel itself.  Asking for it waits for the pass.  Any out-pointer may be null. */
+int pmf_debug_last_path(pmf_ctx *ctx, int *bmode, int *layer_path, int *slots, int *xreg, int64_t *plain_tiles);
+/* Diagnostics: the table the plain loop is chosen from, built for the context's data as a pass of 256-row panels would
+ * build it: int32 [n_rp][n_ct + 1], entry (rp, c) = the number of column tiles < c whose 32 x 32 tiles in row panel rp are
+ * not all finite (row blocks beyond the matrix count as not finite).  out may be NULL (shape only); cap = its entries. */
+int pmf_debug_plain_table(pmf_ctx *ctx, int32_t *out, int64_t cap, int64_t *n_rp, int64_t *n_ct);
 /* the kernel family the last fused data pass ran on: 0 exact f32 (pmf_fused_kernel), 1 pmf_fused_sb_kernel, 2 pmf_fused_sb2_kernel,
  * 4 pmf_fused_sb4_kernel, 8 pmf_fused_sb8_kernel (split modes; tests assert that the intended variant really ran) */
 int pmf_debug_last_kernel(pmf_ctx *ctx, int *kernel);
 
 /* Diagnostics: per grow-only device buffer of the fused data pass (gx_part, gy_slabs, xsb, ysb, btd, colview, tflags,
- * loss_partial, pm, row_slot), the bytes the kernels of the pass pmf_epoch_begin would run with these gradient flags address
+ * loss_partial, pm, row_slot; ptab and plain_count besides when the pass runs a kernel with the plain tile loop), the bytes the kernels of the pass pmf_epoch_begin would run with these gradient flags address
  * ("need", from the kernels' index expressions) and the bytes allocated ("capacity"); 0 / 0 for a buffer the pass does not
  * use.  The call chooses the kernel family and prepares the buffers exactly as the pass would and launches no data pass.
  * Every data pass makes the same comparison before its first launch and refuses to run when a need exceeds its capacity.

@@ -119,7 +119,7 @@ EXPORTS = [
     "pmf_set_precision", "pmf_get_precision",
     "pmf_comm_get_unique_id", "pmf_comm_init", "pmf_comm_init_host", "pmf_comm_destroy", "pmf_comm_set_chunks",
     "pmf_comm_info", "pmf_comm_allreduce", "pmf_get_opt_state", "pmf_fsard_update_A", "pmf_debug_last_path", "pmf_debug_last_kernel",
-    "pmf_debug_pass_extents", "pmf_debug_live_bytes",
+    "pmf_debug_pass_extents", "pmf_debug_live_bytes", "pmf_debug_plain_table",
     "pmf_add_xreg_network", "pmf_add_yreg_network", "pmf_get_reg_network_state", "pmf_add_xreg_l1", "pmf_add_yreg_l1",
     "pmf_impute", "pmf_impute_device", "pmf_impute_entries", "pmf_debug_impute_offset",
     "pmf_loss", "pmf_fit_lbfgs", "pmf_debug_lbfgs_direction",
@@ -932,10 +932,21 @@ class Context:
                     reserved_cus=cu.value, n_collectives=nc.value)
 
     def last_path(self):
-        """Variants of the last launches: dict(bmode=0|1|2, layer_path=0|1|2, slots=..., xreg=0|1), see pmf_hip.h."""
+        """Variants of the last launches: dict(bmode=0|1|2, layer_path=0|1|2, slots=..., xreg=0|1, plain_tiles=...), see
+        pmf_hip.h."""
         b, l, s, x = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
-        self._chk(self.lib.pmf_debug_last_path(self._h, C.byref(b), C.byref(l), C.byref(s), C.byref(x)))
-        return dict(bmode=b.value, layer_path=l.value, slots=s.value, xreg=x.value)
+        pt = C.c_int64(0)
+        self._chk(self.lib.pmf_debug_last_path(self._h, C.byref(b), C.byref(l), C.byref(s), C.byref(x), C.byref(pt)))
+        return dict(bmode=b.value, layer_path=l.value, slots=s.value, xreg=x.value, plain_tiles=pt.value)
+
+    def plain_table(self):
+        """pmf_debug_plain_table: int32 [row panels of 256 rows][column tiles + 1], the running counts of not-all-finite
+        tiles that the exact kernel chooses its plain tile loop from."""
+        n_rp, n_ct = C.c_int64(0), C.c_int64(0)
+        self._chk(self.lib.pmf_debug_plain_table(self._h, None, C.c_int64(0), C.byref(n_rp), C.byref(n_ct)))
+        out = np.zeros((n_rp.value, n_ct.value + 1), np.int32)
+        self._chk(self.lib.pmf_debug_plain_table(self._h, out.ctypes.data_as(C.c_void_p), C.c_int64(out.size), None, None))
+        return out
 
     def last_kernel(self):
         """Kernel family of the last fused data pass: 0 exact, 1 / 2 / 4 / 8 the split kernels sb / sb2 / sb4 / sb8."""

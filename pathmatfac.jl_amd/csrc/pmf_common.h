@@ -110,6 +110,14 @@ struct FusedArgs {
   // multiple of PMF_DPAD columns; read in that branch of pmf_noise only.  LAST: appended so that no other explicit kernarg
   // offset moved.
   const float *htab;
+  // (the exact kernel's XW && XR instances, pmf_fused.hip.inc "plain runs") per row panel of 256 rows the running count,
+  // along its column tiles, of tiles with a row block that is not flagged all-finite: [n_rp][ptab_stride], entry c = the
+  // count over the absolute column tiles < c (k_plain_table).  Null, or plain == 0 (PMF_PLAIN=0): every run takes the
+  // general tile loop.  plain_count[wg] = tiles the workgroup ran in the plain loop (pmf_debug_last_path).
+  const int32_t *ptab;
+  int32_t ptab_stride;  // n_ct_all + 1
+  int32_t plain;
+  int32_t *plain_count;
 };
 
 __device__ __forceinline__ int pmf_rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }

@@ -185,6 +185,12 @@ struct pmf_ctx {
   int64_t D_M = 0, D_Npad = 0, nRB = 0;
   DevBuf<uint32_t> tflags;        // per 32x32 tile of D: 1 = all 1024 entries finite (fast epilogue path of the fused kernel)
   bool tflags_valid = false;
+  // plain-run table of the exact kernel's 256-row panels (k_plain_table): [ptab_n_rp][ptab_n_ct + 1] running counts along a
+  // panel's column tiles of the tiles with a row block that is not all-finite.  Follows tflags: D changes, both are rebuilt.
+  DevBuf<int32_t> ptab;
+  int64_t ptab_bm = 0, ptab_n_rp = 0, ptab_n_ct = 0;   // panel height and shape it was built for (ptab_bm 0: not built)
+  DevBuf<int32_t> plain_count;    // per workgroup and chunk: tiles the last pass ran in the plain loop (beside loss_partial)
+  int64_t last_plain_n = -1;      // live entries of plain_count written by the last pass (-1: it had no plain loop)
   int store = PMF_STORE_F32;
   ParamBuf P[6];  // X, Y, logsigma, mu, logdelta, theta
   // batch views
@@ -408,7 +414,7 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
 // check_pass_extents fails on the first need > cap, naming the buffer; guard_fused_pass is both, between
 // prepare_fused_pass and the first launch of the pass: a few integer compares, no device work.
 struct PassExtent { const char *name; int64_t need, cap; };
-constexpr int PMF_PASS_EXTENTS = 10;
+constexpr int PMF_PASS_EXTENTS = 12;   // ten rows of every pass + ptab and plain_count of a pass whose kernel has the plain loop
 int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy, PassExtent *out);
 int check_pass_extents(const PassExtent *e, int n);
 int guard_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);

@@ -49,6 +49,11 @@
 // the same values in the same order from registers: loss, gX and gY are bit-identical, 96 more VGPRs (144 -> 239 in the
 // headline instance), 65 LDS reads per tile and wave.  PMF_XREG=0 (read at every pass) selects the LDS-read instance;
 // pmf_debug_last_path's xreg tells which one ran.
+//
+// The XR instances (PLAINB) have a second instantiation of the tile loop for plain runs -- consecutive tiles of a piece
+// that are all-finite, full and already visited -- which no longer asks those three questions per tile (at the loop,
+// "Plain runs"), and read GEMM2's Y operand off one pinned base (Y1BASE).  Bit-identical again; PMF_PLAIN=0 (read at
+// every pass) runs everything in the general loop, pmf_debug_last_path's plain_tiles counts the tiles that ran plain.
 
 // RBW = 32-row blocks per wave.  RBW = 2 amortises everything that is per (wave, tile) but not per row -- the slab
 // write, the cross-wave reduction, the Y staging, the barriers -- over twice the MFMA work; it is used where that
@@ -76,6 +81,11 @@ struct FusedCfg {
 #ifndef PMF_NW4_WAVES
 #define PMF_NW4_WAVES 1
 #endif
+// -DPMF_Y1BASE=0: GEMM2's Y operand through the compiler's own addressing in every instance (the A/B of Y1BASE below)
+#ifndef PMF_Y1BASE
+#define PMF_Y1BASE 1
+#endif
+template <bool B> struct PmfFlag { static constexpr bool value = B; };
 // GM = which gradients the launch produces, as a compile-time constant: 0 both (fit!), 1 grad(X) only (transform: Y
 // fixed), 2 grad(Y) only, 3 decided at run time by FusedArgs (ablation flags, loss-only evaluations).  With GM < 3 the
 // steady-state loop is branch-free apart from the loop itself, which lets hipcc emit exact counted s_waitcnt vmcnt(N)
@@ -158,7 +168,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     const int i = 4 * (lane >> 4) + u;
     xw_g[u] = i * 32 + 4 * ((xw_j >> 2) ^ (i & 7)) + (xw_j & 3);
     xw_xa[u] = (unsigned)(uintptr_t)(lds_cptr)(Xs + xw_x + u * KpS);
-    if (XW && !TIGHT) asm volatile("" : "+v"(xw_xa[u]));
+    if (XW && !TIGHT && !XR) asm volatile("" : "+v"(xw_xa[u]));   // (XR reads the panels once per piece: nothing to pin)
   }
 
   // (HOIST: the KB = 2 instances) Tile-invariant addressing.  The lane-dependent part of the Y, column-parameter and
@@ -169,10 +179,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
   // (Not where the eight registers would only add to an instance's spills: the run-time-flag builds, the per-wave-slab
   // builds with batch layers, which already exceed the 256-register budget, and the TIGHT cross-wave builds.)
   constexpr bool HOIST = KB == 2 && NW == 8 && RBW == 1 && GM != 3 && !TIGHT && (XW || GM != 0 || BMODE == 0);
-  unsigned ho_y[2][YV], ho_s[2][YV], ho_c[2], ho_g[2][RV4];
+  // (PLAINB) the instances with a second tile loop for plain runs (below, at the loop)
+  constexpr bool PLAINB = XW && XR && HOIST && !MIXED && !BATCH;
+  // (PLAINB pins set 0 only, for the registers of the second loop: its general loop meets the ragged tile once per row
+  // panel and computes that tile's clamps where it loads, behind a scalar branch)
+  constexpr int HOZ = PLAINB ? 1 : 2;
+  unsigned ho_y[HOZ][YV], ho_s[HOZ][YV], ho_c[HOZ], ho_g[HOZ][RV4];
   if (HOIST) {
 #pragma unroll
-    for (int z = 0; z < 2; ++z) {
+    for (int z = 0; z < HOZ; ++z) {
       const int ncol = z == 0 || N % BN == 0 ? BN : (int)(N % BN);   // z = 1: the live columns of the ragged tile
 #pragma unroll
       for (int q = 0; q < YV; ++q) {
@@ -198,7 +213,20 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       }
     }
   }
-  auto ho_at = [](const void *base, unsigned off) { return reinterpret_cast<const char *>(base) + off; };
+  // (PLAINB) The offset is made opaque again where it is used: its zero extension then stays next to the add, which lets
+  // the load take the base from scalar registers and the offset from ONE vector register.  Hoisted out of the loops, every
+  // offset was a 64-bit pair with a register of zeros, every load a 64-bit vector add, and launch-invariant bases (the
+  // private slab) were pre-added into further pairs: the registers the second tile loop needs.
+  // (Y1BASE) GEMM2's B operand, Ys[tile parity][rowmap(s, h)][l31 + 32 kb]: the lane's part of the LDS byte address, pinned
+  // for the launch.  A tile adds its buffer once and reads all 32 values at compile-time offsets from that ONE register;
+  // left to itself the compiler pairs the reads (ds_read2_b32) off eight bases that it recomputes for every tile.
+  constexpr bool Y1BASE = PLAINB && PMF_Y1BASE != 0;
+  unsigned g2_lane = (unsigned)(uintptr_t)(lds_cptr)(Ys + 4 * h * KpS + l31);
+  if (Y1BASE) asm volatile("" : "+v"(g2_lane));
+  auto ho_at = [](const void *base, unsigned &off) {
+    if (PLAINB) asm volatile("" : "+v"(off));
+    return reinterpret_cast<const char *>(base) + off;
+  };
 #ifdef PMF_STAMPS
   unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long st_prev = __builtin_amdgcn_s_memtime();
@@ -219,6 +247,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
   float *myslab = a.gy_slabs + (int64_t)wg * a.slab_stride;
   const int64_t seg_block = a.n_rp * a.tps;        // tiles of one full segment
   double lossacc = 0.0;
+  int n_plain = 0;                                 // (PLAINB) tiles this workgroup runs in the plain loop (scalar)
   int seg_cur = -1, pidx = 0, t0_first = 0;        // slab bookkeeping: piece index within the current segment visit
   int gx_slot = (GM == 2) ? 0 : a.piece_base[wg];  // slot of this workgroup's next piece in the gX partial buffer
   for (int64_t widx = w_begin; widx < w_end;) {
@@ -234,6 +263,23 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     // a column tile's slab entry is STORED on the workgroup's first visit and accumulated afterwards: the first
     // piece of a segment visit covers tiles >= ti0 only, so tiles < t0_first are first seen by the second piece
     bool slab_first = true;
+    // (PLAINB) the piece's plain run [t_plain, t_pend), see the tile loop below.  The two table entries are loaded here and
+    // compared there, behind the prologue's loads and barrier.
+    int pl_b = ntiles, pl_e = ntiles;
+    int32_t pl_c0 = 0, pl_c1 = 0;
+    if (PLAINB && a.plain) {
+      const int64_t c_abs = (int64_t)a.ct0 + (int64_t)cs * a.tps + ti0;   // absolute column tile of the piece's tile 0
+      const bool rag = (c_abs + ntiles) * PMF_BN > N;                      // the piece ends with the matrix's ragged tile
+      pl_b = pidx == 0 ? ntiles : (pidx == 1 ? (t0_first - ti0 < 0 ? 0 : (t0_first - ti0 < ntiles ? t0_first - ti0 : ntiles)) : 0);
+      pl_e = rag ? ntiles - 2 : ntiles;
+      if (pl_b < pl_e) {
+        const int32_t *pt = a.ptab + rp * a.ptab_stride;
+        pl_c0 = pt[c_abs + pl_b];
+        pl_c1 = pt[c_abs + (rag ? ntiles - 1 : ntiles)];
+      } else {
+        pl_b = pl_e = ntiles;
+      }
+    }
     const int64_t col_begin = ((int64_t)a.ct0 + (int64_t)cs * a.tps + ti0) * BN;
     int64_t row0[RBW], irow_c[RBW];
     bool row_ok[RBW];
@@ -281,14 +327,15 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     // The loads are issued unconditionally from clamped in-bounds addresses and their results are NOT touched until
     // stage_store (dead columns are zeroed there): nothing waits on a load where it is issued, and the compiler
     // knows how many VMEM operations are in flight (counted s_waitcnt vmcnt(N)).
-    auto stage_load_y = [&](int64_t jt, int q, float4 (&yv)[YV], float (&sgv)[YV]) {
+    // (plain: a constant at every call; true = the tile is known to be a full one, PLAIN below)
+    auto stage_load_y = [&](int64_t jt, int q, float4 (&yv)[YV], float (&sgv)[YV], bool plain = false) {
       const float *yb = a.Y + jt * Kp;       // the BN x Kp tile is contiguous in Y
       const float4 *cb = a.colp + jt;
       const int64_t rem = N - jt;
-      if (HOIST) {
-        const bool rag = rem < BN;
-        yv[q] = *reinterpret_cast<const float4 *>(ho_at(yb, rag ? ho_y[1][q] : ho_y[0][q]));
-        sgv[q] = *reinterpret_cast<const float *>(ho_at(cb, rag ? ho_s[1][q] : ho_s[0][q]));
+      if (HOIST && !(PLAINB && !plain && rem < BN)) {
+        const bool rag = HOZ == 2 && rem < BN;
+        yv[q] = *reinterpret_cast<const float4 *>(ho_at(yb, rag ? ho_y[HOZ - 1][q] : ho_y[0][q]));
+        sgv[q] = *reinterpret_cast<const float *>(ho_at(cb, rag ? ho_s[HOZ - 1][q] : ho_s[0][q]));
         return;
       }
       const int ncol = rem > BN ? BN : (int)rem;  // live columns of this tile (>= 1)
@@ -299,11 +346,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       yv[q] = *reinterpret_cast<const float4 *>(yb + e4 * 4);
       sgv[q] = cb[jl].x;
     };
-    auto stage_load_c = [&](int64_t jt, float4 &cv) {
+    auto stage_load_c = [&](int64_t jt, float4 &cv, bool plain = false) {
       const float4 *cb = a.colp + jt;
       const int64_t rem = N - jt;
-      if (HOIST) {
-        cv = *reinterpret_cast<const float4 *>(ho_at(cb, rem < BN ? ho_c[1] : ho_c[0]));
+      if (HOIST && !(PLAINB && !plain && rem < BN)) {
+        cv = *reinterpret_cast<const float4 *>(ho_at(cb, HOZ == 2 && rem < BN ? ho_c[HOZ - 1] : ho_c[0]));
         return;
       }
       const int ncol = rem > BN ? BN : (int)rem;
@@ -315,22 +362,22 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       stage_load_c(jt, cv);
     };
     // jt = first column of the staged tile (decides which columns are dead)
-    auto stage_store = [&](int ybuf, int cbuf, int64_t jt, const float4 (&yv)[YV], const float (&sgv)[YV], const float4 &cv) {
+    auto stage_store = [&](int ybuf, int cbuf, int64_t jt, const float4 (&yv)[YV], const float (&sgv)[YV], const float4 &cv, bool plain = false) {
       float *Yn = Ys + ybuf * Cfg::YT;
       const int64_t rem = N - jt;
-      const int ncol = rem > BN ? BN : (int)rem;
+      const int ncol = plain || rem > BN ? BN : (int)rem;
 #pragma unroll
       for (int q = 0; q < YV; ++q) {
         const int e4 = tid + NT * q;
         if (e4 < BN * Kp / 4) {
           const int jl = (e4 * 4) / Kp, kf = (e4 * 4) % Kp;
-          const float sg = jl < ncol ? sgv[q] : 0.f;
+          const float sg = plain || jl < ncol ? sgv[q] : 0.f;
           *reinterpret_cast<float4 *>(Yn + jl * KpS + kf) = make_float4(yv[q].x * sg, yv[q].y * sg, yv[q].z * sg, yv[q].w * sg);
         }
       }
       asm volatile("" ::"v"(cv.x), "v"(cv.y), "v"(cv.z), "v"(cv.w));   // counted wait here, not vmcnt(0) inside the branch
       if (tid < BN) {
-        const bool livec = tid < ncol;
+        const bool livec = plain || tid < ncol;
         Csg[cbuf * BN + tid] = livec ? cv.x : 0.f;
         Cmu[cbuf * BN + tid] = livec ? cv.y : 0.f;
         Cw[cbuf * BN + tid] = livec ? cv.z : 0.f;
@@ -375,11 +422,11 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       e = ((ff % (BN * 8)) / 8) * Kp + 32 * (ff / (BN * 8)) + 4 * (ff % 8);
       return in;
     };
-    auto slab_prefetch_one = [&](int64_t jt, int q) {
+    auto slab_prefetch_one = [&](int64_t jt, int q, bool plain = false) {
       const float *sb = myslab + jt * Kp;
       const int64_t rem = N - jt;
-      if (HOIST) {
-        gold[q] = pmf_load_stream(reinterpret_cast<const float4 *>(ho_at(sb, rem < BN ? ho_g[1][q] : ho_g[0][q])));
+      if (HOIST && !(PLAINB && !plain && rem < BN)) {
+        gold[q] = pmf_load_stream(reinterpret_cast<const float4 *>(ho_at(sb, HOZ == 2 && rem < BN ? ho_g[HOZ - 1][q] : ho_g[0][q])));
         return;
       }
       const int nel = (rem > BN ? BN : (int)rem) * Kp;   // live elements of this gY tile (>= Kp)
@@ -535,7 +582,31 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     // XW:  epilogue(t) -> G tile [t & 1] | issue loads of tile t+1 | GEMM2(t) | publish Y(t+1)
     //   -- the tile's barrier: the eight G tiles complete, Y(t+1) visible --
     //   cross-wave GEMM3(t) -> private gY slab (plain RMW) | forward(t+1)
-    for (int t = 0; t < ntiles; ++t) {
+    //
+    // (PLAINB) Plain runs.  Three questions of the loop have the same answer for every tile of a run of consecutive
+    // tiles of a piece, for all eight waves: is the tile all-finite (the packed epilogue), is it the matrix's ragged last
+    // column tile (load offsets, dead columns, store predicate), is this the workgroup's first visit of the slab entry
+    // (store or accumulate).  The loop body is one routine with a compile-time flag; a piece runs its first t_plain tiles
+    // in the general instantiation and the rest in the PLAIN one, which answers "finite, full, not first" without asking:
+    // no tile-flag load and test, offset set 0 only, gold always added, unpredicated store, no dead-column selects, the
+    // packed epilogue only.  Same MFMAs on the same operands in the same order: bit-identical results.  The loop-carried
+    // state (acc, dcur, gx, the loss sums) passes straight from one instantiation to the other; have_next still refers to
+    // the piece's end.  The run starts at the first tile that is not a first visit and ends with the piece, if the tiles
+    // in between are all-finite in all eight row blocks (two loads from the running counts of k_plain_table, by absolute
+    // column tile); there is none in a segment visit's first piece and under PMF_PLAIN=0.
+    // The ragged tile ends a piece of the last segment in every row panel (three tiles in ten at the headline size sit
+    // in such pieces): there the run stops two tiles short, so that a general iteration issues the ragged tile's clamped
+    // loads and its flag; the table answers for the tile in between (its flag was never loaded: set below).
+    int t_plain = ntiles, t_pend = ntiles;
+    if (PLAINB && a.plain) {
+      const bool run = pl_b < pl_e && pl_c0 == pl_c1;
+      t_plain = __builtin_amdgcn_readfirstlane(run ? pl_b : ntiles);
+      t_pend = __builtin_amdgcn_readfirstlane(run ? pl_e : ntiles);
+      n_plain += t_pend - t_plain;
+    }
+    auto tile_loop = [&](auto plain_flag, const int t_begin, const int t_end) __attribute__((always_inline)) {
+    constexpr bool PLAIN = decltype(plain_flag)::value;
+    for (int t = t_begin; t < t_end; ++t) {
       const int par = t & 1;
       const int cur = NYB == 2 ? par : 0, nxt = NYB == 2 ? (par ^ 1) : 0;
       const int64_t j0 = col_begin + (int64_t)t * BN;
@@ -632,24 +703,25 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       // piece re-loads itself: unconditional loads keep the loop branch-free.)
       const int64_t jn = have_next ? j0 + BN : j0;
       constexpr int NOTH = YV + 1 + RV4 + (BATCH ? NBT : 0);     // the non-D loads, in the order they are needed
-      constexpr int NVM = NOTH + (DCH + 1) * RBW;                  // + per row block: the D chunks and the tile flag
+      constexpr int DPR = DCH + (PLAIN ? 0 : 1);
+      constexpr int NVM = NOTH + DPR * RBW;                        // + per row block: the D chunks and (not PLAIN) the tile flag
       bool tile_fast[RBW];
 #pragma unroll
-      for (int rb = 0; rb < RBW; ++rb) tile_fast[rb] = rows_in[rb] && tflag[rb] != 0;
+      for (int rb = 0; rb < RBW; ++rb) tile_fast[rb] = PLAIN || (rows_in[rb] && tflag[rb] != 0);
       auto vmem_op = [&](int i) {
         if (i == 0 && bt_lds) {   // the views of the table entries this thread fetches below (address of those loads)
 #pragma unroll
           for (int q = 0; q < NBT; ++q) btv[q] = pmf_bt_view(a, jn, bt_e(q));
         }
-        if (i < YV) stage_load_y(jn, i, ynext, sgnext);
-        else if (i == YV) stage_load_c(jn, cnext);
-        else if (i < YV + 1 + RV4) { if (want_gy) slab_prefetch_one(j0, i - YV - 1); }
+        if (i < YV) stage_load_y(jn, i, ynext, sgnext, PLAIN);
+        else if (i == YV) stage_load_c(jn, cnext, PLAIN);
+        else if (i < YV + 1 + RV4) { if (want_gy) slab_prefetch_one(j0, i - YV - 1, PLAIN); }
         else if (i < NOTH) {
           const int q = i - YV - 1 - RV4;
           if (bt_lds) { btn[q] = pmf_bt_entry(a, Pm, jn, bt_e(q), btv[q]); btm[q] = bt_mu(jn, bt_e(q)); }
         }
         else if (i < NVM) {
-          const int rb = (i - NOTH) / (DCH + 1), q = (i - NOTH) % (DCH + 1);
+          const int rb = (i - NOTH) / DPR, q = (i - NOTH) % DPR;
           if (q < DCH) {
             if (FULL || !(dbg & 2)) dcur[rb].load(a.D, (jn >> 5) * a.nRB + rb_u[rb], lane, q);
           } else {
@@ -717,19 +789,24 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       //      the B operands of step s+2 are read, one global load is issued, then the MFMAs of step s.
       if (want_gx) {
         float bq[3][KB];
+        unsigned g2_y = g2_lane + (unsigned)(cur * Cfg::YT * 4);   // (Y1BASE) this tile's base, opaque: nothing to re-derive
+        if (Y1BASE) asm volatile("" : "+v"(g2_y));
+        auto g2_read = [&](int s, int kb) -> float {
+          // (volatile: keeps each read a ds_read_b32 at its own offset; merged into pairs they need the eight bases again)
+          if (Y1BASE) return *(const volatile __attribute__((address_space(3))) float *)(uintptr_t)(g2_y + 4 * (pmf_rowmap(s, 0) * KpS + 32 * kb));
+          return (Yc + pmf_rowmap(s, h) * KpS + l31)[32 * kb];
+        };
 #pragma unroll
         for (int s0 = 0; s0 < 2; ++s0) {
-          const float *yp = Yc + pmf_rowmap(s0, h) * KpS + l31;
 #pragma unroll
-          for (int kb = 0; kb < KB; ++kb) bq[s0][kb] = yp[32 * kb];
+          for (int kb = 0; kb < KB; ++kb) bq[s0][kb] = g2_read(s0, kb);
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int s = 0; s < 16; ++s) {
           if (s + 2 < 16) {
-            const float *yp = Yc + pmf_rowmap(s + 2, h) * KpS + l31;
 #pragma unroll
-            for (int kb = 0; kb < KB; ++kb) bq[(s + 2) % 3][kb] = yp[32 * kb];
+            for (int kb = 0; kb < KB; ++kb) bq[(s + 2) % 3][kb] = g2_read(s + 2, kb);
           }
           if (s < NVM) vmem_op(s);
 #pragma unroll
@@ -793,7 +870,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
       PMF_STAMP(4);   // GEMM3 + slab writes
       // ---- publish Y(t+1); B1 also completes this tile's slabs
       if (NYB == 1) __syncthreads();   // single Y buffer: every wave is done reading Y(t)
-      stage_store(nxt, par ^ 1, jn, ynext, sgnext, cnext);
+      stage_store(nxt, par ^ 1, jn, ynext, sgnext, cnext, PLAIN);
       PMF_STAMP(5);   // stage_store (waits for the Y loads)
       __syncthreads();                 // B1
       PMF_STAMP(6);   // B1 wait
@@ -803,7 +880,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
         for (int q = 0; q < NBT; ++q) bt_store(bt_e(q), btn[q], btm[q]);
       }
       // ---- forward of tile t+1 with the reduction of tile t's slabs into the private gY slab inside it
-      slab_first = pidx == 0 || (pidx == 1 && ti0 + t < t0_first);
+      slab_first = !PLAIN && (pidx == 0 || (pidx == 1 && ti0 + t < t0_first));
       if (XW) {
         // ---- cross-wave GEMM3: gY[xw_j, xw_k..+3] = sum over the panel's 256 rows of X[k, i] G[i, j].  64 MFMAs in two
         //      independent accumulator chains (32-cycle issue, 40-cycle dependent latency), operands read XW_AHEAD steps
@@ -852,7 +929,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
         const int nel = (rem > BN ? BN : (int)rem) * Kp;
         float4 v = make_float4((gy0[0] + gy1[0]) * xw_sg, (gy0[1] + gy1[1]) * xw_sg, (gy0[2] + gy1[2]) * xw_sg, (gy0[3] + gy1[3]) * xw_sg);
         if (!slab_first) { v.x += gold[0].x; v.y += gold[0].y; v.z += gold[0].z; v.w += gold[0].w; }
-        if (xw_e < nel) pmf_store_stream(reinterpret_cast<float4 *>(myslab + j0 * Kp + xw_e), v);
+        // (PLAIN: through the pinned offset the old values were loaded from -- one address for both, not two induction pointers)
+        if (PLAIN) pmf_store_stream(reinterpret_cast<float4 *>(const_cast<char *>(ho_at(myslab + j0 * Kp, ho_g[0][0]))), v);
+        else if (xw_e < nel) pmf_store_stream(reinterpret_cast<float4 *>(myslab + j0 * Kp + xw_e), v);
         PMF_STAMP(4);   // GEMM3 + gY store
         // forward of tile t+1 (unconditional, as everything in this loop: a piece's last tile repeats its own, and a
         // branch would cost the sixteen register copies of a conditional acc per tile).  G(t+2) and Y(t+2) overwrite
@@ -870,6 +949,19 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
         if ((GM != 1 || bt_lds) && !(dbg & 16)) __syncthreads();
         PMF_STAMP(9);   // B2 wait
       }
+    }
+    };
+    if constexpr (PLAINB) {
+      // at most three runs: general, plain, general (the two tiles up to the ragged one)
+      tile_loop(PmfFlag<false>{}, 0, t_plain);
+      tile_loop(PmfFlag<PLAINB>{}, t_plain, t_pend);
+      if (t_pend < ntiles) {
+#pragma unroll
+        for (int rb = 0; rb < RBW; ++rb) tflag[rb] = 1;   // of tile t_pend: all-finite by the table, its flag was not loaded
+        tile_loop(PmfFlag<false>{}, t_pend, ntiles);
+      }
+    } else {
+      tile_loop(PmfFlag<false>{}, 0, ntiles);
     }
     // (XW) the next piece's prologue overwrites this wave's X panel, which the other waves read in the last GEMM3.
     // (XR) The panels are read only right after the prologue's barrier, but this barrier protects more than them: the
@@ -901,6 +993,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 8 ? 2 : PMF_NW4_WAVES)) void pmf_fu
     double s = 0.0;
     for (int q = 0; q < NW; ++q) s += red[q];
     a.loss_partial[wg] = s;
+    if (PLAINB && a.plain_count) a.plain_count[wg] = n_plain;
   }
 #ifdef PMF_STAMPS
   st_acc[14] = __builtin_amdgcn_s_memtime() - st_t0;          // shader clocks over the whole kernel

@@ -27,6 +27,53 @@ static int ensure_tile_flags(pmf_ctx *c) {
   k_tile_flags<<<(unsigned)ntiles, 256, 0, c->stream>>>(c->D, ntiles, c->tflags, c->store == PMF_STORE_BF16);
   HIPCHK(hipGetLastError());
   c->tflags_valid = true;
+  c->ptab_bm = 0;   // the plain-run table was made from the old flags
+  return 0;
+}
+
+// The plain-run table of the exact kernel (pmf_fused.hip.inc, "Plain runs"): one workgroup per row panel of nblk row
+// blocks walks the panel's column tiles in strips of 256 and writes, for every column tile c, the number of tiles < c
+// with a row block that is absent or not flagged all-finite: out[rp][0 .. n_ct].  A run of tiles [c0, c1) of the panel
+// is all-finite iff out[rp][c1] == out[rp][c0].  Like the flags it is made once per data matrix, not per pass.
+__global__ __launch_bounds__(256) void k_plain_table(const uint32_t *__restrict__ flags, int64_t nRB, int nblk, int64_t n_ct,
+                                                     int32_t *__restrict__ out) {
+  __shared__ int sc[256];
+  const int64_t rp = blockIdx.x;
+  int32_t *o = out + rp * (n_ct + 1);
+  int carry = 0;
+  if (threadIdx.x == 0) o[0] = 0;
+  for (int64_t c0 = 0; c0 < n_ct; c0 += 256) {
+    const int64_t ct = c0 + threadIdx.x;
+    int bad = 0;
+    if (ct < n_ct)
+      for (int r = 0; r < nblk; ++r) {
+        const int64_t rb = rp * nblk + r;
+        if (rb >= nRB || flags[ct * nRB + rb] == 0) bad = 1;
+      }
+    sc[threadIdx.x] = bad;
+    __syncthreads();
+    for (int d = 1; d < 256; d <<= 1) {   // inclusive scan of the strip
+      const int v = threadIdx.x >= d ? sc[threadIdx.x - d] : 0;
+      __syncthreads();
+      sc[threadIdx.x] += v;
+      __syncthreads();
+    }
+    if (ct < n_ct) o[ct + 1] = carry + sc[threadIdx.x];
+    carry += sc[255];
+    __syncthreads();
+  }
+}
+
+// (after ensure_tile_flags) the table for panels of bm rows over n_ct column tiles; rebuilt when D, and with it the flags,
+// changed, or when it was made for another panel height or shape
+static int ensure_plain_table(pmf_ctx *c, int64_t bm, int64_t n_ct) {
+  const int64_t n_rp = (c->M + bm - 1) / bm;
+  if (c->ptab_bm == bm && c->ptab_n_rp == n_rp && c->ptab_n_ct == n_ct) return 0;
+  if (n_ct + 1 > 0x7fffffff || n_rp > 0x7fffffff) return pmf_fail("too many tiles");
+  PMFCHK(c->ptab.ensure((size_t)n_rp * (size_t)(n_ct + 1), false));
+  k_plain_table<<<(unsigned)n_rp, 256, 0, c->stream>>>(c->tflags, c->nRB, (int)(bm / 32), n_ct, c->ptab);
+  HIPCHK(hipGetLastError());
+  c->ptab_bm = bm; c->ptab_n_rp = n_rp; c->ptab_n_ct = n_ct;
   return 0;
 }
 
@@ -328,6 +375,14 @@ static const FusedFamily *find_family(int kernel, int KB, int RBW = 0) {
   return nullptr;
 }
 
+// Does the pass run an instance of the exact kernel that has the plain tile loop (pmf_fused.hip.inc, PLAINB: cross-wave
+// GEMM3 with register-resident X, i.e. 32 < K <= 64, both gradients, one noise model, no batch layers)?  Then it reads the
+// plain-run table and writes the per-workgroup counts.  (PMF_XGEMM3=0 / PMF_XREG=0 select instances that ignore both.)
+static bool pass_has_plain_loop(const pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy) {
+  const FusedFamily &f = *g.fam;
+  return f.kernel == 0 && f.KB == 2 && f.NW == 8 && f.RBW == 1 && want_gx && want_gy && g.bmode == 0 && !c->mixed;
+}
+
 // Family and chunking of a fused data pass.
 //   family (a row of fused_families): split-bf16 products (pmf_set_precision), at least one gradient, no PMF_DEBUG_FLAGS:
 //     K <= 32 sb;  32 < K <= 64 sb8 with both gradients unless PMF_SB8=0 or 4, else sb2 (sb under PMF_SB2=0);
@@ -494,6 +549,10 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     PMFCHK(c->gx_part.ensure(pieces * (size_t)f.BM() * (size_t)c->Kp, false));   // every slot is written whole by its piece before it is read
   }
   PMFCHK(ensure_tile_flags(c));
+  if (pass_has_plain_loop(c, g, want_gx, want_gy)) {
+    PMFCHK(ensure_plain_table(c, f.BM(), g.n_ct_all));
+    PMFCHK(c->plain_count.ensure((size_t)grid_sum, false));   // one per workgroup and chunk, like the loss partials
+  }
   if (f.img != IMG_NONE) {
     // the image buffers are sized for the largest block of every family whose image rows are as wide as f's
     size_t xblk = 0, yblk = 0;
@@ -546,7 +605,13 @@ int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
   out[n++] = {"loss_partial", grid_sum * 8, (int64_t)c->loss_partial.bytes()};
   out[n++] = {"pm", bt ? g.n_rp * c->n_bv * 16 : 0, bt ? (int64_t)g.ps->pm.bytes() : 0};
   out[n++] = {"row_slot", bt ? (int64_t)c->n_bv * c->M : 0, bt ? (int64_t)g.ps->row_slot.bytes() : 0};
-  static_assert(PMF_PASS_EXTENTS == 10, "fused_pass_extents");
+  if (pass_has_plain_loop(c, g, want_gx, want_gy)) {
+    // rows of a pass whose kernel has the plain loop only: row panel rp < n_rp reads entries [0, n_ct_all] of its line (the
+    // absolute column tile of a run's end is at most n_ct_all); one count per workgroup and chunk
+    out[n++] = {"ptab", g.n_rp * (g.n_ct_all + 1) * 4, c->ptab_bm == f.BM() ? (int64_t)c->ptab.bytes() : 0};
+    out[n++] = {"plain_count", grid_sum * 4, (int64_t)c->plain_count.bytes()};
+  }
+  static_assert(PMF_PASS_EXTENTS == 12, "fused_pass_extents");
   return n;
 }
 int check_pass_extents(const PassExtent *e, int n) {
@@ -627,6 +692,13 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   a.M = c->M; a.N = c->N; a.n_tiles = n_rp * n_ct; a.tps = (int)tiles_per_seg; a.n_ct = (int)n_ct; a.n_cseg = (int)n_cseg;
   a.want_gx = want_gx; a.want_gy = want_gy;
   a.ct0 = (int32_t)g.ct0[s];
+  const bool has_plain = pass_has_plain_loop(c, g, want_gx, want_gy);
+  if (has_plain) {
+    // PMF_PLAIN=0 (read at every pass, like PMF_XREG): every run takes the general tile loop; bit-identical results
+    const char *pe = getenv("PMF_PLAIN");
+    a.ptab = c->ptab; a.ptab_stride = (int32_t)(g.n_ct_all + 1); a.plain = !(pe && atoi(pe) == 0);
+    a.plain_count = c->plain_count + loss_off;
+  }
   a.gx_part = c->gx_part; a.piece_base = ws.d_piece_base_abs; a.gx_slot_stride = (int64_t)f.BM() * c->Kp;
   {
     const char *dbg = getenv("PMF_DEBUG_FLAGS");
@@ -667,6 +739,8 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   pmf_last_xreg = 0;
   const int rc = f.launch[c->store == PMF_STORE_BF16](&c->dyn_lds, c->stream, a, grid, batch, c->mixed);
   c->last_xreg = pmf_last_xreg;
+  // the counts the pass leaves in plain_count: those of its chunks so far, if the instance that writes them ran
+  c->last_plain_n = has_plain && pmf_last_xreg ? loss_off + grid : -1;
   if (f.kernel != 0) c->sb_launches += 1;
   PMFCHK(rc);
   HIPCHK(hipEventRecord(ev.second, c->stream));   // the events bracket pmf_fused_kernel alone (= rocprofv3's kernel duration)
@@ -705,12 +779,40 @@ extern "C" int pmf_debug_last_kernel(pmf_ctx *c, int *kernel) {
   return 0;
 }
 
-extern "C" int pmf_debug_last_path(pmf_ctx *c, int *bmode, int *layer_path, int *slots, int *xreg) {
+extern "C" int pmf_debug_last_path(pmf_ctx *c, int *bmode, int *layer_path, int *slots, int *xreg, int64_t *plain_tiles) {
   if (!c) return pmf_fail("null context");
+  if (plain_tiles) {
+    *plain_tiles = 0;
+    if (c->last_plain_n > 0) {
+      PMFCHK(ctx_bind(c));
+      std::vector<int32_t> h((size_t)c->last_plain_n);
+      HIPCHK(hipMemcpyAsync(h.data(), c->plain_count, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+      for (int32_t v : h) *plain_tiles += v;
+    }
+  }
   if (xreg) *xreg = c->last_xreg;
   if (bmode) *bmode = c->last_bmode;
   if (layer_path) *layer_path = c->last_layer_path;
   if (slots) *slots = c->nbs;
+  return 0;
+}
+
+// The plain-run table of the context's data for 256-row panels, built as a pass builds it (ensure_plain_table).
+extern "C" int pmf_debug_plain_table(pmf_ctx *c, int32_t *out, int64_t cap, int64_t *n_rp, int64_t *n_ct) {
+  PMFCHK(ctx_bind(c));
+  if (!c->D) return pmf_fail("data not set");
+  PMFCHK(ensure_tile_flags(c));
+  const int64_t nct = (c->N + PMF_BN - 1) / PMF_BN;
+  PMFCHK(ensure_plain_table(c, 256, nct));
+  if (n_rp) *n_rp = c->ptab_n_rp;
+  if (n_ct) *n_ct = nct;
+  if (out) {
+    const int64_t n = c->ptab_n_rp * (nct + 1);
+    if (cap < n) return pmf_fail("pmf_debug_plain_table: room for %lld entries, %lld needed", (long long)cap, (long long)n);
+    HIPCHK(hipMemcpyAsync(out, c->ptab, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
   return 0;
 }
 
