@@ -325,7 +325,7 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
   // chunk s of an epoch's data pass, with the exchange of what it completes
   auto pass_chunk = [&](int s) -> int {
     if (fused) {
-      PMFCHK(launch_fused_chunk(c, g, s, ux, uy));
+      PMFCHK(launch_fused_chunk(c, g, s));
       if (cm && uy) {
         const int64_t col0 = g.ct0[s] * 32, col1 = std::min<int64_t>(c->N, (g.ct0[s] + g.nct[s]) * 32);
         PMFCHK(comm_after_compute(c, m.ev_ready[(size_t)s]));
@@ -349,8 +349,8 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
   bool in_flight = false;   // a data pass whose epoch has not been finished is enqueued
   if (o->epoch <= o->max_epochs) {
     if (fused) {
-      PMFCHK(prepare_fused_pass(c, g, ux, uy));
-      PMFCHK(guard_fused_pass(c, g, ux, uy));
+      PMFCHK(prepare_fused_pass(c, g));
+      PMFCHK(guard_fused_pass(c, g));
     }
     for (int s = 0; s < S; ++s) PMFCHK(pass_chunk(s));
     in_flight = true;

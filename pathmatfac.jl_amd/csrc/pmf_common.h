@@ -4,6 +4,7 @@
 //   pmf_hip.hip        C ABI (marshalling, step-level API, statistics), small kernels (pmf_ctx.h lists the other host units)
 //   pmf_k_fused.hip    pmf_fused_kernel (pmf_fused.hip.inc), once per (K blocks, row blocks per wave)
 //   pmf_k_sb.hip       pmf_fused_sb_kernel + k_sb_split (pmf_fused_sb.hip.inc), once per K-block count
+//                      (pmf_split_launch.h: the instance selection it shares with pmf_k_sb2.hip and pmf_k_sb4.hip)
 //   pmf_k_layers.hip   pmf_layer_kernel + k_layer_map (pmf_layers.hip.inc)
 //   pmf_k_impute.hip   pmf_impute_kernel + k_impute_entries (pmf_impute.hip.inc)
 //   pmf_k_debatch.hip  pmf_debatch_kernel + k_debatch_entries (pmf_debatch.hip.inc)
@@ -589,25 +590,50 @@ struct DebatchEntriesArgs {
   int32_t flags;
 };
 
+// ---- which instance of a fused kernel a data pass runs
+// Decided once per pass on the host (fused_geometry, pmf_pass.hip) and handed to the family's launcher, which selects by
+// it and by nothing else; a launcher asked for an instance that is not built fails (pmf_fail), it never runs another one.
+struct FusedInstance {
+  int bmode = 0;        // batch layers: 0 none, 1 LDS table with panel-local slots, 2 per-entry gathers (exact kernel only)
+  bool mixed = false;   // per-column noise models
+  int gm = 0;           // gradient mode (compile-time in the kernel): 0 both, 1 grad(X) only, 2 grad(Y) only, 3 run-time flags
+  bool xw = false;      // exact kernel: cross-wave GEMM3
+  bool xr = false;      // exact kernel, on an xw instance: a piece's X fragments stay in registers; these have the plain tile loop
+};
+// The rules of the exact kernel's instances (pmf_fused_kernel<KB, NW, RBW, BMODE, MIXED, GM, DB, XW, XR>), the same
+// functions for the host, which fills FusedInstance by them, and for pmf_k_fused.hip, which instantiates by them.
+// The gather fallback (> 15 batches of a view in a row panel) has no single-gradient variants.
+constexpr bool pmf_exact_gm_built(int bmode, int gm) { return bmode != 2 || gm == 0 || gm == 3; }
+// PMF_DEBUG_FLAGS (dbg != 0) and a pass without gradients take the run-time flags, and so does what is not built.
+constexpr int pmf_exact_gm(int bmode, bool want_gx, bool want_gy, int dbg) {
+  const int gm = dbg != 0 ? 3 : (want_gx && want_gy ? 0 : (want_gx ? 1 : (want_gy ? 2 : 3)));
+  return pmf_exact_gm_built(bmode, gm) ? gm : 3;
+}
+// Cross-wave GEMM3 (pmf_fused.hip.inc, XW): eight waves of one row block at 32 < K <= 64 with both gradients, whatever
+// the epilogue.
+constexpr bool pmf_exact_has_xw(int KB, int NW, int RBW, int bmode, bool mixed, int gm, bool db) {
+  return KB == 2 && NW == 8 && RBW == 1 && gm == 0;
+}
+// Which cross-wave-GEMM3 instances keep their X fragments in registers (XR): those whose build has no scratch and at most
+// 256 VGPRs with the 96 extra registers; the others keep the LDS reads.  Measured on the builds:
+// single-model Gaussian columns without batch layers hold them at 239 (f32 D) / 241 (bf16 D) VGPRs; every other instance
+// starts from 175 .. 256 and would spill 5 .. 92 registers.  These instances, and no others, have the plain tile loop.
+constexpr bool pmf_exact_has_xr(int KB, int NW, int RBW, int bmode, bool mixed, int gm, bool db) {
+  return pmf_exact_has_xw(KB, NW, RBW, bmode, mixed, gm, db) && bmode == 0 && !mixed;
+}
+
 // ---- launchers exported by the kernel files
-// Fused-kernel launchers, one per family, K-block count (exact kernel: and row blocks per wave) and storage type of D, all
-// of one type: the family table in pmf_pass.hip holds them.  The gradient variant follows a.want_gx / a.want_gy.
-typedef int PmfFusedLaunch(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed);
-PmfFusedLaunch pmf_launch_fused_exact_11, pmf_launch_fused_exact_12, pmf_launch_fused_exact_21, pmf_launch_fused_exact_31,
-    pmf_launch_fused_exact_41, pmf_launch_fused_exact_11_bf16, pmf_launch_fused_exact_12_bf16, pmf_launch_fused_exact_21_bf16,
-    pmf_launch_fused_exact_31_bf16, pmf_launch_fused_exact_41_bf16;
-// Set to 1 by an exact launcher that picked a register-resident-X instance (launch_fused_chunk clears it before the launch
-// and copies it to the context afterwards: pmf_debug_last_path).
-extern thread_local int pmf_last_xreg;
-PmfFusedLaunch pmf_launch_fused_sb_1, pmf_launch_fused_sb_2, pmf_launch_fused_sb_1_bf16, pmf_launch_fused_sb_2_bf16;
-PmfFusedLaunch pmf_launch_fused_sb2, pmf_launch_fused_sb2_bf16;
-PmfFusedLaunch pmf_launch_fused_sb4_3, pmf_launch_fused_sb4_4, pmf_launch_fused_sb4_3_bf16, pmf_launch_fused_sb4_4_bf16;
-PmfFusedLaunch pmf_launch_fused_sb8_2, pmf_launch_fused_sb8_4, pmf_launch_fused_sb8_2_bf16, pmf_launch_fused_sb8_4_bf16;
+// Fused-kernel launchers: one explicit specialisation per family (0 exact, 1 sb, 2 sb2, 4 sb4, 8 sb8), K-block count, row
+// blocks per wave and storage type of D (bf16: DB), each defined by the pmf_k_*.hip unit compiled with those values; the
+// family table in pmf_pass.hip names them.
+template <int FAMILY, int KB, int RBW, bool DB>
+int pmf_launch_fused(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, const FusedInstance &inst);
+typedef int PmfFusedLaunch(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, const FusedInstance &inst);
+typedef void (*FusedKernel)(const FusedArgs);   // any instance of the five families
 int pmf_launch_sb4_split(hipStream_t stream, const Sb4SplitArgs &a);
 int pmf_launch_sb8_split(hipStream_t stream, const Sb8SplitArgs &a, int KB);
 int pmf_launch_sb8_scale(hipStream_t stream, const Sb8ScaleArgs &a);
-int pmf_launch_sb_split_1(hipStream_t stream, const SbSplitArgs &a);
-int pmf_launch_sb_split_2(hipStream_t stream, const SbSplitArgs &a);
+template <int KB> int pmf_launch_sb_split(hipStream_t stream, const SbSplitArgs &a);   // (pmf_k_sb.hip, KB = 1, 2)
 size_t pmf_layer_pass_lds(int KB, int lnw, int nbs);   // dynamic LDS of the layer pass (<= 160 KiB: eligible)
 int pmf_launch_layer_pass(PmfDynLds *cache, hipStream_t stream, int KB, int lnw, bool mixed, int grid, const LayerPassArgs &a);   // (a.d_bf16 picks the storage variant)
 int pmf_launch_layer_map(hipStream_t stream, const LayerMapArgs &m);

@@ -119,6 +119,7 @@ struct PanelSlots {
 struct WorkSplit {
   int64_t key[11] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
   int grid = 0;
+  int64_t tps = 0, n_cseg = 0;     // column segmentation the split was made for (chunk_segments): tiles per segment, segments
   int64_t serial = 0;
   DevBuf<int64_t> wg_begin;        // [grid + 1] device: first work item of each workgroup
   DevBuf<int32_t> c_off, c_idx;    // per column tile of the chunk: the workgroups that visit it (CSR; k_gy_reduce)
@@ -279,15 +280,32 @@ struct pmf_ctx {
 #define REG_SLOTS 1024
 #define PMF_MAX_CHUNKS 16
 
-// Geometry of one fused data pass: kernel family, row panels, column chunks.
+// The PMF_* environment switches of the data pass as fused_geometry found them (read_pass_switches in pmf_pass.hip, the one
+// place that reads them; DESIGN.md section 10 has their meanings).  -1: not set.
+struct PassSwitches {
+  bool sb2 = true, xgemm3 = true, xreg = true, plain = true;   // PMF_SB2 / PMF_XGEMM3 / PMF_XREG / PMF_PLAIN: false when = 0
+  int sb8 = 1;                                                  // PMF_SB8
+  bool rbw1 = false;                                            // PMF_RBW=1
+  bool dbg_set = false; int dbg = 0;                            // PMF_DEBUG_FLAGS: set at all (even to 0); its bits
+  int reserve_cus = -1;                                         // PMF_RESERVE_CUS, clamped to [0, n_cu / 2]
+  double tps_scale = 1.0, algbw_gbps = 60.0;                    // PMF_TPS_SCALE; PMF_COMM_ALGBW_GBPS where > 0
+  int w_bern = -1, w_pois = -1, w_hinge = -1, w_batch = -1;     // PMF_W_*: at least 16, PMF_W_BATCH at least 0
+};
+
+// One fused data pass as decided before its first launch (fused_geometry): kernel family and instance, what it computes,
+// the switches it runs under, row panels, column chunks.
 struct FusedFamily;   // a row of the family table (pmf_pass.hip): kernel, panel height, operand images, launchers
 struct FusedGeom {
   const FusedFamily *fam = nullptr;
+  bool want_gx = false, want_gy = false;
+  FusedInstance inst;   // the instance of the family's kernel: batch mode, mixed noise models, gradient mode, xw / xr
+  PassSwitches sw;
   int grid_max = 256, S = 1;
-  int bmode = 0;      // batch layers: 0 none, 1 LDS table with panel-local slots, 2 per-entry global gathers (fallback)
   PanelSlots *ps = nullptr;
   int64_t n_rp = 0, n_ct_all = 0;
   int64_t ct0[PMF_MAX_CHUNKS], nct[PMF_MAX_CHUNKS];
+  // the instance has the plain tile loop: the pass reads the plain-run table and writes the per-workgroup counts
+  bool has_plain_loop() const { return inst.xw && inst.xr; }
 };
 
 struct RegCounts { int c[4]; };
@@ -406,18 +424,18 @@ int stats_pass(pmf_ctx *c, int use_factors, bool want_cols, bool want_batch, con
 // ---- defined in pmf_pass.hip
 int harvest_events(pmf_ctx *c);
 int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy);   // the whole data pass in one go (chunks only on request)
-FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chunks);
-int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);
-int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool want_gy);
+FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chunks);   // (reads the PMF_* switches of the pass)
+int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g);
+int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s);
 // What the kernels of a prepared data pass address in every grow-only buffer against what is allocated, in bytes
 // ("Extents").  fused_pass_extents fills out[PMF_PASS_EXTENTS] and returns the count;
 // check_pass_extents fails on the first need > cap, naming the buffer; guard_fused_pass is both, between
 // prepare_fused_pass and the first launch of the pass: a few integer compares, no device work.
 struct PassExtent { const char *name; int64_t need, cap; };
 constexpr int PMF_PASS_EXTENTS = 12;   // ten rows of every pass + ptab and plain_count of a pass whose kernel has the plain loop
-int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy, PassExtent *out);
+int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, PassExtent *out);
 int check_pass_extents(const PassExtent *e, int n);
-int guard_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy);
+int guard_fused_pass(pmf_ctx *c, const FusedGeom &g);
 // ---- defined in pmf_lbfgs.hip
 void lbfgs_free(pmf_ctx *c);
 // ---- defined in pmf_netreg.hip

@@ -5,23 +5,13 @@
 #endif
 #include "pmf_common.h"
 #include "pmf_fused_sb2.hip.inc"
+#include "pmf_split_launch.h"
 
-#if PMF_DB
-#define PMF_SB2NAME pmf_launch_fused_sb2_bf16
-#else
-#define PMF_SB2NAME pmf_launch_fused_sb2
-#endif
-
-int PMF_SB2NAME(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed) {
-  void (*kern)(const FusedArgs) = nullptr;
-#define PMF_SB_PICK_G(MX, BT) (a.want_gx && a.want_gy ? pmf_fused_sb2_kernel<MX, true, true, BT, PMF_DB != 0>                                 \
-                               : a.want_gx ? pmf_fused_sb2_kernel<MX, true, false, BT, PMF_DB != 0>                                        \
-                                         : pmf_fused_sb2_kernel<MX, false, true, BT, PMF_DB != 0>)
-  kern = batch ? PMF_SB_PICK_G(true, true) : (mixed ? PMF_SB_PICK_G(true, false) : PMF_SB_PICK_G(false, false));
-#undef PMF_SB_PICK_G
-  const size_t lds = Sb2Cfg::lds_bytes + (batch ? Sb2Cfg::lds_batch(a.n_bv) : 0);
-  PMFCHK(pmf_ensure_dyn_lds(cache, (const void *)kern, lds));
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, a);
-  HIPCHK(hipGetLastError());
-  return 0;
+template <bool MIXED, bool GX, bool GY, bool BATCH>
+struct Sb2Kern {
+  static FusedKernel fn() { return pmf_fused_sb2_kernel<MIXED, GX, GY, BATCH, PMF_DB != 0>; }
+};
+template <>
+int pmf_launch_fused<2, 2, 2, PMF_DB != 0>(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, const FusedInstance &i) {
+  return pmf_launch_split<Sb2Kern>(cache, stream, a, grid, i, 256, Sb2Cfg::lds_bytes + (i.bmode ? Sb2Cfg::lds_batch(a.n_bv) : 0));
 }

@@ -10,17 +10,14 @@
 #include "pmf_common.h"
 #include "pmf_fused_sb8.hip.inc"
 
-#define PMF_CAT_(a, b, c) a##b##c
-#define PMF_CAT(a, b, c) PMF_CAT_(a, b, c)
-#if PMF_DB
-#define PMF_SB8NAME PMF_CAT(pmf_launch_fused_sb8_, PMF_KB, _bf16)
-#else
-#define PMF_SB8NAME PMF_CAT(pmf_launch_fused_sb8_, PMF_KB, )
-#endif
-
-int PMF_SB8NAME(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, bool batch, bool mixed) {
-  void (*kern)(const FusedArgs) = batch ? pmf_fused_sb8_kernel<PMF_KB, true, true, PMF_DB != 0>
-                                        : (mixed ? pmf_fused_sb8_kernel<PMF_KB, true, false, PMF_DB != 0> : pmf_fused_sb8_kernel<PMF_KB, false, false, PMF_DB != 0>);
+template <>
+int pmf_launch_fused<8, PMF_KB, Sb8Cfg<PMF_KB>::RB, PMF_DB != 0>(PmfDynLds *cache, hipStream_t stream, const FusedArgs &a, int grid, const FusedInstance &i) {
+  // both gradients only (fused_geometry sends every other pass to another family), no gather fallback, nothing of the exact kernel's
+  if (i.gm != 0 || i.bmode > 1 || i.xw || i.xr)
+    return pmf_fail("pmf_fused_sb8_kernel: no instance bmode %d, gm %d, xw %d, xr %d is built", i.bmode, i.gm, (int)i.xw, (int)i.xr);
+  const bool batch = i.bmode == 1;
+  const FusedKernel kern = batch ? pmf_fused_sb8_kernel<PMF_KB, true, true, PMF_DB != 0>
+                                 : (i.mixed ? pmf_fused_sb8_kernel<PMF_KB, true, false, PMF_DB != 0> : pmf_fused_sb8_kernel<PMF_KB, false, false, PMF_DB != 0>);
   const size_t lds = Sb8Cfg<PMF_KB>::lds_bytes + (batch ? Sb8Cfg<PMF_KB>::lds_batch(a.n_bv) : 0);
   if (lds > 160 * 1024) return pmf_fail("pmf_fused_sb8_kernel: %zu bytes of LDS", lds);
   PMFCHK(pmf_ensure_dyn_lds(cache, (const void *)kern, lds));

@@ -1,5 +1,8 @@
 // pmf_pass.hip -- host driver of the fused data pass: tile flags and the fixed-order gX / gY reductions, the work split, the
 // kernel-family table with its geometry, buffers, extents guard and launches, and the debug entries that read the pass state.
+// fused_geometry decides a pass once: the PMF_* switches (read_pass_switches), the family (fused_families) and the instance
+// of its kernel (FusedInstance, by the rules of pmf_common.h).  Buffers, extents, kernel arguments, the launcher's selection
+// and the diagnostics read that FusedGeom and decide nothing again.
 #include "pmf_ctx.h"
 
 // One workgroup per 32x32 tile of the tile-major D: flag = 1 iff all 1024 entries are finite.  The fused kernel takes
@@ -162,26 +165,26 @@ __global__ __launch_bounds__(256) void k_gx_reduce(const float *__restrict__ par
 // which lowers the Bernoulli tiles' relative weight.
 // A squared-hinge tile always runs the per-column path (its thresholds are per column).  Its weight is UNMEASURED: it starts
 // from the Poisson tile's (PMF_W_HINGE overrides it).
-static void noise_tile_weights(int KB, bool split, bool batch, int64_t &w_gauss, int64_t &w_bern, int64_t &w_pois, int64_t &w_hinge) {
+static void noise_tile_weights(const PassSwitches &sw, int KB, bool split, bool batch, int64_t &w_gauss, int64_t &w_bern, int64_t &w_pois, int64_t &w_hinge) {
   static const int64_t wb_exact[4] = {26, 22, 20, 20}, wb_split[4] = {31, 30, 24, 24};
   static const int64_t we_exact[4] = {6, 6, 5, 4}, we_split[4] = {12, 8, 6, 6};   // (swept on the all-features launch: PMF_W_BATCH)
   w_bern = (split ? wb_split : wb_exact)[KB - 1];
-  if (getenv("PMF_W_BERN")) w_bern = std::max(16, atoi(getenv("PMF_W_BERN")));
+  if (sw.w_bern >= 0) w_bern = sw.w_bern;
   w_pois = 16 + ((w_bern - 16) * 5 + 3) / 6;       // (exp only against exp + log + rcp: the exact kernel's 21 against 22)
-  if (getenv("PMF_W_POIS")) w_pois = std::max(16, atoi(getenv("PMF_W_POIS")));
+  if (sw.w_pois >= 0) w_pois = sw.w_pois;
   w_hinge = w_pois;                                // (unmeasured)
-  if (getenv("PMF_W_HINGE")) w_hinge = std::max(16, atoi(getenv("PMF_W_HINGE")));
+  if (sw.w_hinge >= 0) w_hinge = sw.w_hinge;
   int64_t w_batch = batch ? (split ? we_split : we_exact)[KB - 1] : 0;
-  if (batch && getenv("PMF_W_BATCH")) w_batch = std::max(0, atoi(getenv("PMF_W_BATCH")));
+  if (batch && sw.w_batch >= 0) w_batch = sw.w_batch;
   w_gauss = 16 + w_batch;
   w_bern += w_batch;
   w_pois += w_batch;
   w_hinge += w_batch;
 }
 
-static int compute_work_split(pmf_ctx *c, WorkSplit &ws, int grid, int64_t n_rp, int64_t ct0, int64_t n_ct, int64_t tps, int64_t n_cseg, bool split) {
+static int compute_work_split(pmf_ctx *c, const PassSwitches &sw, WorkSplit &ws, int grid, int64_t n_rp, int64_t ct0, int64_t n_ct, int64_t tps, int64_t n_cseg, bool split) {
   int64_t w_gauss, w_bern, w_pois, w_hinge;
-  noise_tile_weights(c->KB, split, c->n_bv > 0, w_gauss, w_bern, w_pois, w_hinge);
+  noise_tile_weights(sw, c->KB, split, c->n_bv > 0, w_gauss, w_bern, w_pois, w_hinge);
   const int64_t key[11] = {c->M, c->N, c->Kp, grid, n_rp, tps, n_cseg, c->kind_version, ct0, n_ct,
                            c->mixed ? ((w_gauss * 64 + w_bern) * 64 + w_pois) * 64 + w_hinge : 0};
   if (ws.wg_begin && memcmp(key, ws.key, sizeof(key)) == 0) return 0;
@@ -266,7 +269,7 @@ static int compute_work_split(pmf_ctx *c, WorkSplit &ws, int grid, int64_t n_rp,
   HIPCHK(hipMemcpyAsync(ws.c_idx, h_idx.data(), sizeof(int32_t) * h_idx.size(), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));   // the sources are pageable host memory
   memcpy(ws.key, key, sizeof(key));
-  ws.grid = grid;
+  ws.grid = grid; ws.tps = tps; ws.n_cseg = n_cseg;   // (all three are in the key)
   ws.serial = ++c->split_serial;
   return 0;
 }
@@ -352,18 +355,18 @@ struct FusedFamily {
 };
 static constexpr FusedFamily fused_families[] = {
     // kernel, KB, NW, RBW, max_bv, images, img_kb, xblk, yblk, nblk, launchers (D stored as f32, as bf16)
-    {0, 1, 8,             2,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_12, pmf_launch_fused_exact_12_bf16}},
-    {0, 1, 8,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_11, pmf_launch_fused_exact_11_bf16}},
-    {0, 2, 8,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_21, pmf_launch_fused_exact_21_bf16}},
-    {0, 3, 4,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_31, pmf_launch_fused_exact_31_bf16}},
-    {0, 4, 4,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused_exact_41, pmf_launch_fused_exact_41_bf16}},
-    {1, 1, SbCfg<1>::NW,  1,             SbCfg<1>::max_bv,  IMG_SB,   1, SbCfg<1>::BLK,   SbCfg<1>::BLK,   1,               {pmf_launch_fused_sb_1, pmf_launch_fused_sb_1_bf16}},
-    {1, 2, SbCfg<2>::NW,  1,             SbCfg<2>::max_bv,  IMG_SB,   2, SbCfg<2>::BLK,   SbCfg<2>::BLK,   1,               {pmf_launch_fused_sb_2, pmf_launch_fused_sb_2_bf16}},
-    {2, 2, 4,             2,             Sb2Cfg::max_bv,    IMG_SB,   2, SbCfg<2>::BLK,   SbCfg<2>::BLK,   1,               {pmf_launch_fused_sb2, pmf_launch_fused_sb2_bf16}},
-    {4, 3, Sb4Cfg<3>::NW, 1,             Sb4Cfg<3>::max_bv, IMG_SB4,  4, Sb4Cfg<3>::XBLK, Sb4Cfg<3>::YBLK, 1,               {pmf_launch_fused_sb4_3, pmf_launch_fused_sb4_3_bf16}},
-    {4, 4, Sb4Cfg<4>::NW, 1,             Sb4Cfg<4>::max_bv, IMG_SB4,  4, Sb4Cfg<4>::XBLK, Sb4Cfg<4>::YBLK, 1,               {pmf_launch_fused_sb4_4, pmf_launch_fused_sb4_4_bf16}},
-    {8, 2, Sb8Cfg<2>::NW, Sb8Cfg<2>::RB, Sb8Cfg<2>::max_bv, IMG_SB8,  2, Sb8Cfg<2>::XBLK, Sb8Cfg<2>::YBLK, Sb8Cfg<2>::NBLK, {pmf_launch_fused_sb8_2, pmf_launch_fused_sb8_2_bf16}},
-    {8, 4, Sb8Cfg<4>::NW, Sb8Cfg<4>::RB, Sb8Cfg<4>::max_bv, IMG_SB8,  4, Sb8Cfg<4>::XBLK, Sb8Cfg<4>::YBLK, Sb8Cfg<4>::NBLK, {pmf_launch_fused_sb8_4, pmf_launch_fused_sb8_4_bf16}},
+    {0, 1, 8,             2,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused<0, 1, 2, false>, pmf_launch_fused<0, 1, 2, true>}},
+    {0, 1, 8,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused<0, 1, 1, false>, pmf_launch_fused<0, 1, 1, true>}},
+    {0, 2, 8,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused<0, 2, 1, false>, pmf_launch_fused<0, 2, 1, true>}},
+    {0, 3, 4,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused<0, 3, 1, false>, pmf_launch_fused<0, 3, 1, true>}},
+    {0, 4, 4,             1,             PMF_MAXV,          IMG_NONE, 0, 0,               0,               1,               {pmf_launch_fused<0, 4, 1, false>, pmf_launch_fused<0, 4, 1, true>}},
+    {1, 1, SbCfg<1>::NW,  1,             SbCfg<1>::max_bv,  IMG_SB,   1, SbCfg<1>::BLK,   SbCfg<1>::BLK,   1,               {pmf_launch_fused<1, 1, 1, false>, pmf_launch_fused<1, 1, 1, true>}},
+    {1, 2, SbCfg<2>::NW,  1,             SbCfg<2>::max_bv,  IMG_SB,   2, SbCfg<2>::BLK,   SbCfg<2>::BLK,   1,               {pmf_launch_fused<1, 2, 1, false>, pmf_launch_fused<1, 2, 1, true>}},
+    {2, 2, 4,             2,             Sb2Cfg::max_bv,    IMG_SB,   2, SbCfg<2>::BLK,   SbCfg<2>::BLK,   1,               {pmf_launch_fused<2, 2, 2, false>, pmf_launch_fused<2, 2, 2, true>}},
+    {4, 3, Sb4Cfg<3>::NW, 1,             Sb4Cfg<3>::max_bv, IMG_SB4,  4, Sb4Cfg<3>::XBLK, Sb4Cfg<3>::YBLK, 1,               {pmf_launch_fused<4, 3, 1, false>, pmf_launch_fused<4, 3, 1, true>}},
+    {4, 4, Sb4Cfg<4>::NW, 1,             Sb4Cfg<4>::max_bv, IMG_SB4,  4, Sb4Cfg<4>::XBLK, Sb4Cfg<4>::YBLK, 1,               {pmf_launch_fused<4, 4, 1, false>, pmf_launch_fused<4, 4, 1, true>}},
+    {8, 2, Sb8Cfg<2>::NW, Sb8Cfg<2>::RB, Sb8Cfg<2>::max_bv, IMG_SB8,  2, Sb8Cfg<2>::XBLK, Sb8Cfg<2>::YBLK, Sb8Cfg<2>::NBLK, {pmf_launch_fused<8, 2, Sb8Cfg<2>::RB, false>, pmf_launch_fused<8, 2, Sb8Cfg<2>::RB, true>}},
+    {8, 4, Sb8Cfg<4>::NW, Sb8Cfg<4>::RB, Sb8Cfg<4>::max_bv, IMG_SB8,  4, Sb8Cfg<4>::XBLK, Sb8Cfg<4>::YBLK, Sb8Cfg<4>::NBLK, {pmf_launch_fused<8, 4, Sb8Cfg<4>::RB, false>, pmf_launch_fused<8, 4, Sb8Cfg<4>::RB, true>}},
 };
 constexpr int PMF_XSB_PAD = 16;   // xsb's image blocks beyond nRB: sb_split_x writes the last panel of every family whole
 static_assert([] { for (const FusedFamily &f : fused_families) if (f.nblk - 1 > PMF_XSB_PAD) return false; return true; }(), "PMF_XSB_PAD");
@@ -375,12 +378,23 @@ static const FusedFamily *find_family(int kernel, int KB, int RBW = 0) {
   return nullptr;
 }
 
-// Does the pass run an instance of the exact kernel that has the plain tile loop (pmf_fused.hip.inc, PLAINB: cross-wave
-// GEMM3 with register-resident X, i.e. 32 < K <= 64, both gradients, one noise model, no batch layers)?  Then it reads the
-// plain-run table and writes the per-workgroup counts.  (PMF_XGEMM3=0 / PMF_XREG=0 select instances that ignore both.)
-static bool pass_has_plain_loop(const pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy) {
-  const FusedFamily &f = *g.fam;
-  return f.kernel == 0 && f.KB == 2 && f.NW == 8 && f.RBW == 1 && want_gx && want_gy && g.bmode == 0 && !c->mixed;
+// Every PMF_* environment switch of the data pass, read here and nowhere else, once per fused_geometry, i.e. at every pass
+// (a fit reads them once, for all its epochs); each with the meaning, default and clamping DESIGN.md section 10 lists.
+static PassSwitches read_pass_switches(const pmf_ctx *c) {
+  PassSwitches sw;
+  auto num = [](const char *name, int unset) { const char *e = getenv(name); return e ? atoi(e) : unset; };
+  auto at_least = [](const char *name, int lo) { const char *e = getenv(name); return e ? std::max(lo, atoi(e)) : -1; };
+  // PMF_SB2 alone is read once per process: its first value holds for every later pass, whatever the variable is set to then
+  static const bool sb2 = num("PMF_SB2", 1) != 0;
+  sw.sb2 = sb2; sw.sb8 = num("PMF_SB8", 1); sw.rbw1 = num("PMF_RBW", 0) == 1;
+  sw.dbg_set = getenv("PMF_DEBUG_FLAGS") != nullptr; sw.dbg = num("PMF_DEBUG_FLAGS", 0);
+  sw.xgemm3 = num("PMF_XGEMM3", 1) != 0; sw.xreg = num("PMF_XREG", 1) != 0; sw.plain = num("PMF_PLAIN", 1) != 0;
+  sw.reserve_cus = std::min(at_least("PMF_RESERVE_CUS", 0), c->n_cu / 2);
+  if (const char *e = getenv("PMF_TPS_SCALE")) sw.tps_scale = atof(e);
+  if (const char *e = getenv("PMF_COMM_ALGBW_GBPS")) if (atof(e) > 0) sw.algbw_gbps = atof(e);
+  sw.w_bern = at_least("PMF_W_BERN", 16); sw.w_pois = at_least("PMF_W_POIS", 16); sw.w_hinge = at_least("PMF_W_HINGE", 16);
+  sw.w_batch = at_least("PMF_W_BATCH", 0);
+  return sw;
 }
 
 // Family and chunking of a fused data pass.
@@ -397,6 +411,10 @@ static bool pass_has_plain_loop(const pmf_ctx *c, const FusedGeom &g, bool want_
 //   chunks and of the next epoch's earlier ones, pmf_fit) or pmf_comm_set_chunks asked for it.
 FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chunks) {
   FusedGeom g;
+  g.want_gx = want_gx; g.want_gy = want_gy;
+  g.sw = read_pass_switches(c);
+  const PassSwitches &sw = g.sw;
+  int bmode = 0;
   auto batch_fits = [&](const FusedFamily *f) {
     if (c->n_bv == 0) return true;
     PanelSlots *ps = nullptr;
@@ -404,33 +422,38 @@ FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chun
     g.ps = ps;
     return true;
   };
-  if (c->precision == PMF_PREC_BF16X3 && (want_gx || want_gy) && !getenv("PMF_DEBUG_FLAGS")) {
-    static const bool sb2_off = getenv("PMF_SB2") && atoi(getenv("PMF_SB2")) == 0;   // (read once per process)
-    const char *e8 = getenv("PMF_SB8");
-    const int m8 = e8 ? atoi(e8) : 1;
+  if (c->precision == PMF_PREC_BF16X3 && (want_gx || want_gy) && !sw.dbg_set) {
     const bool both = want_gx && want_gy;
     int base = 0;       // the family without sb8
     bool sb8 = false;
     switch (c->KB) {
       case 1: base = 1; break;
-      case 2: base = sb2_off ? 1 : 2; sb8 = both && m8 != 0 && m8 != 4; break;
+      case 2: base = sw.sb2 ? 2 : 1; sb8 = both && sw.sb8 != 0 && sw.sb8 != 4; break;
       case 3: base = 4; break;
-      case 4: base = 4; sb8 = both && m8 != 0; break;
+      case 4: base = 4; sb8 = both && sw.sb8 != 0; break;
     }
     const FusedFamily *f8 = sb8 ? find_family(8, c->KB) : nullptr, *fb = find_family(base, c->KB);
     g.fam = f8 && batch_fits(f8) ? f8 : (fb && batch_fits(fb) ? fb : nullptr);
-    g.bmode = g.fam && c->n_bv > 0 ? 1 : 0;
+    bmode = g.fam && c->n_bv > 0 ? 1 : 0;
   }
   if (!g.fam) {
-    const char *rbwenv = getenv("PMF_RBW");
-    g.fam = find_family(0, c->KB, c->KB == 1 && c->n_bv == 0 && !(rbwenv && atoi(rbwenv) == 1) ? 2 : 1);
+    g.fam = find_family(0, c->KB, c->KB == 1 && c->n_bv == 0 && !sw.rbw1 ? 2 : 1);
     if (!g.fam) return g;   // (prepare_fused_pass fails)
-    if (c->n_bv > 0) g.bmode = batch_fits(g.fam) ? 1 : 2;
+    if (c->n_bv > 0) bmode = batch_fits(g.fam) ? 1 : 2;
   }
-  g.n_rp = (c->M + g.fam->BM() - 1) / g.fam->BM();
+  // the instance of the family's kernel: the split families' per gradient pair (gm 0 .. 2), the exact kernel's by the rules of
+  // pmf_common.h; PMF_XGEMM3=0 / PMF_XREG=0 keep the instance without (bit-identical results: the A/B inside one library)
+  const FusedFamily &f = *g.fam;
+  const bool db = c->store == PMF_STORE_BF16;
+  FusedInstance &in = g.inst;
+  in.bmode = bmode; in.mixed = c->mixed;
+  in.gm = pmf_exact_gm(f.kernel == 0 ? bmode : 0, want_gx, want_gy, sw.dbg);
+  in.xw = f.kernel == 0 && sw.xgemm3 && pmf_exact_has_xw(f.KB, f.NW, f.RBW, in.bmode, in.mixed, in.gm, db);
+  in.xr = in.xw && sw.xreg && pmf_exact_has_xr(f.KB, f.NW, f.RBW, in.bmode, in.mixed, in.gm, db);
+  g.n_rp = (c->M + f.BM() - 1) / f.BM();
   g.n_ct_all = (c->N + PMF_BN - 1) / PMF_BN;
   int reserve = c->comm.nranks > 1 ? c->comm.reserve_cus : 0;
-  if (const char *e = getenv("PMF_RESERVE_CUS")) reserve = std::max(0, std::min(atoi(e), c->n_cu / 2));   // (tests / A-B: a one-rank run with the multi-rank grid)
+  if (sw.reserve_cus >= 0) reserve = sw.reserve_cus;   // (tests / A-B: a one-rank run with the multi-rank grid)
   g.grid_max = std::max(1, c->n_cu - reserve);
   int S = 1;
   if (allow_chunks && want_gy) {
@@ -443,8 +466,7 @@ FusedGeom fused_geometry(pmf_ctx *c, bool want_gx, bool want_gy, bool allow_chun
       // 25000 rows x 50000, K = 64: 1 / 2 / 4 / 8 chunks = 4.27 / 4.33 / 4.45 / 4.79 ms per epoch), so: two chunks, more
       // only while a chunk's all-reduce (~30 us + bytes / algorithm bandwidth; 60 GB/s assumed for an 8-GPU xGMI ring
       // at these sizes, PMF_COMM_ALGBW_GBPS overrides) would not fit beside the rest of the pass.
-      const char *bw = getenv("PMF_COMM_ALGBW_GBPS");
-      const double algbw = (bw && atof(bw) > 0 ? atof(bw) : 60.0) * 1e9;
+      const double algbw = sw.algbw_gbps * 1e9;
       // Rank-invariant inputs only (every rank must choose the same S: it is the number and size of the collectives):
       // N, Kp, the arithmetic mode and the MEAN rows per rank that pmf_fit has all-reduced (comm.m_mean), never the local
       // row count or the kernel variant this rank's batch layout happens to allow.
@@ -486,10 +508,7 @@ static void chunk_segments(pmf_ctx *c, const FusedGeom &g, int s, int &grid, int
   const double a_cost = tiles_per_wg * 8e-6;
   const double b_cost = (double)grid * (double)c->Kp * (double)n_ct * 32.0 * 4.0 / ((double)n_ct * 4e12);
   tps = (int64_t)std::llround(std::sqrt(a_cost / std::max(b_cost, 1e-12)));
-  {
-    const char *ts = getenv("PMF_TPS_SCALE");   // development: scale the model's segment length
-    if (ts) tps = (int64_t)std::llround((double)tps * atof(ts));
-  }
+  tps = (int64_t)std::llround((double)tps * g.sw.tps_scale);   // (PMF_TPS_SCALE, development: scale the model's segment length; 1 unless set)
   tps = std::max<int64_t>(std::min<int64_t>(8, n_ct), std::min<int64_t>(tps, n_ct));
   // equal segments; the LAST one takes the remainder (it is longer, never tiny: every piece of work pays the fixed
   // prologue, so a 5-tile last segment once made one workgroup 20 % late)
@@ -497,15 +516,16 @@ static void chunk_segments(pmf_ctx *c, const FusedGeom &g, int s, int &grid, int
 }
 
 // Everything a data pass needs before its first launch: work splits of all chunks (cached), the gX slot map, buffers.
-int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy) {
+int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g) {
   if (!g.fam) return pmf_fail("unsupported KB=%d", c->KB);
   const FusedFamily &f = *g.fam;
+  const bool want_gx = g.want_gx, want_gy = g.want_gy;
   if ((int)c->splits.size() < g.S) c->splits.resize((size_t)g.S);
   int64_t grid_sum = 0, serial_sum = 0;
   for (int s = 0; s < g.S; ++s) {
     int grid; int64_t tps, n_cseg;
     chunk_segments(c, g, s, grid, tps, n_cseg);
-    PMFCHK(compute_work_split(c, c->splits[(size_t)s], grid, g.n_rp, g.ct0[s], g.nct[s], tps, n_cseg, f.kernel != 0));
+    PMFCHK(compute_work_split(c, g.sw, c->splits[(size_t)s], grid, g.n_rp, g.ct0[s], g.nct[s], tps, n_cseg, f.kernel != 0));
     grid_sum += grid;
   }
   serial_sum = c->split_serial * PMF_MAX_CHUNKS + g.S;   // (split_serial is bumped by every recomputed split)
@@ -549,7 +569,7 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     PMFCHK(c->gx_part.ensure(pieces * (size_t)f.BM() * (size_t)c->Kp, false));   // every slot is written whole by its piece before it is read
   }
   PMFCHK(ensure_tile_flags(c));
-  if (pass_has_plain_loop(c, g, want_gx, want_gy)) {
+  if (g.has_plain_loop()) {
     PMFCHK(ensure_plain_table(c, f.BM(), g.n_ct_all));
     PMFCHK(c->plain_count.ensure((size_t)grid_sum, false));   // one per workgroup and chunk, like the loss partials
   }
@@ -575,8 +595,9 @@ int prepare_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
 // Every need is taken from the index expressions of the kernels the pass launches (the fused kernel of g.fam, its operand
 // splits, k_gy_reduce, k_gx_reduce, k_loss_reduce) with the values launch_fused_chunk hands them, not from the sizing
 // formulas of prepare_fused_pass.  Bytes.
-int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy, PassExtent *out) {
+int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, PassExtent *out) {
   const FusedFamily &f = *g.fam;
+  const bool want_gx = g.want_gx, want_gy = g.want_gy;
   const int64_t Kp = c->Kp, Npad = g.n_ct_all * PMF_BN;
   int64_t pieces = 0, grid_sum = 0, grid_top = 0;
   for (int s = 0; s < g.S; ++s) {
@@ -585,7 +606,7 @@ int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
     grid_sum += ws.grid;
     grid_top = std::max<int64_t>(grid_top, ws.grid);
   }
-  const bool bt = g.bmode == 1;
+  const bool bt = g.inst.bmode == 1;
   int nbs_shift = 0;
   while ((1 << nbs_shift) < c->nbs) ++nbs_shift;
   const int64_t gx_slot_stride = (int64_t)f.BM() * Kp, slab_stride = Kp * c->N;
@@ -605,7 +626,7 @@ int fused_pass_extents(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_g
   out[n++] = {"loss_partial", grid_sum * 8, (int64_t)c->loss_partial.bytes()};
   out[n++] = {"pm", bt ? g.n_rp * c->n_bv * 16 : 0, bt ? (int64_t)g.ps->pm.bytes() : 0};
   out[n++] = {"row_slot", bt ? (int64_t)c->n_bv * c->M : 0, bt ? (int64_t)g.ps->row_slot.bytes() : 0};
-  if (pass_has_plain_loop(c, g, want_gx, want_gy)) {
+  if (g.has_plain_loop()) {
     // rows of a pass whose kernel has the plain loop only: row panel rp < n_rp reads entries [0, n_ct_all] of its line (the
     // absolute column tile of a run's end is at most n_ct_all); one count per workgroup and chunk
     out[n++] = {"ptab", g.n_rp * (g.n_ct_all + 1) * 4, c->ptab_bm == f.BM() ? (int64_t)c->ptab.bytes() : 0};
@@ -621,9 +642,9 @@ int check_pass_extents(const PassExtent *e, int n) {
                       (long long)e[i].cap);
   return 0;
 }
-int guard_fused_pass(pmf_ctx *c, const FusedGeom &g, bool want_gx, bool want_gy) {
+int guard_fused_pass(pmf_ctx *c, const FusedGeom &g) {
   PassExtent e[PMF_PASS_EXTENTS];
-  return check_pass_extents(e, fused_pass_extents(c, g, want_gx, want_gy, e));
+  return check_pass_extents(e, fused_pass_extents(c, g, e));
 }
 
 // split-bf16 operand images (k_sb_split): X once per pass, sigma*Y per chunk (its columns only: the Y step of a later
@@ -648,7 +669,7 @@ static int sb_split_x(pmf_ctx *c, const FusedFamily &f) {
     return pmf_launch_sb4_split(c->stream, s4);
   }
   SbSplitArgs sx = {c->P[0].p, nullptr, c->M, c->nRB, c->xsb};
-  return f.KB == 1 ? pmf_launch_sb_split_1(c->stream, sx) : pmf_launch_sb_split_2(c->stream, sx);
+  return f.KB == 1 ? pmf_launch_sb_split<1>(c->stream, sx) : pmf_launch_sb_split<2>(c->stream, sx);
 }
 static int sb_split_y(pmf_ctx *c, const FusedFamily &f, int64_t ct0, int64_t nct, int chunk) {
   const int64_t c0 = ct0 * 32;
@@ -660,17 +681,16 @@ static int sb_split_y(pmf_ctx *c, const FusedFamily &f, int64_t ct0, int64_t nct
     return pmf_launch_sb4_split(c->stream, s4);
   }
   SbSplitArgs sy = {src, c->colp + c0, c->N - c0, nct, out};
-  return f.KB == 1 ? pmf_launch_sb_split_1(c->stream, sy) : pmf_launch_sb_split_2(c->stream, sy);
+  return f.KB == 1 ? pmf_launch_sb_split<1>(c->stream, sy) : pmf_launch_sb_split<2>(c->stream, sy);
 }
 
 // One chunk of the data pass: the fused kernel over column tiles [ct0, ct0 + nct) and the fixed-order reduction of its
 // private gY slabs; after the LAST chunk, the fixed-order reduction of the gX partial slabs.
-int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool want_gy) {
+int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s) {
   const FusedFamily &f = *g.fam;
+  const bool want_gx = g.want_gx, want_gy = g.want_gy;
   WorkSplit &ws = c->splits[(size_t)s];
   const int grid = ws.grid;
-  int grid_dummy; int64_t tiles_per_seg, n_cseg;
-  chunk_segments(c, g, s, grid_dummy, tiles_per_seg, n_cseg);
   const int64_t n_ct = g.nct[s], n_rp = g.n_rp;
   const int64_t slab_stride = (int64_t)c->Kp * c->N;
   int64_t loss_off = 0;
@@ -681,29 +701,24 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   a.wg_begin = ws.wg_begin;
   a.D = c->D; a.X = c->P[0].p; a.Y = c->P[1].p; a.gX = c->P[0].g; a.gY = c->P[1].g;
   a.colp = c->colp; a.htab = c->htab; a.bor = c->bor; a.btab = c->btab; a.loss_partial = c->loss_partial + loss_off;
-  a.btd = g.bmode == 1 ? c->btd : nullptr; a.n_bv = c->n_bv;
-  if (g.bmode == 1) {
+  a.btd = g.inst.bmode == 1 ? c->btd : nullptr; a.n_bv = c->n_bv;
+  if (g.inst.bmode == 1) {
     a.pm = g.ps->pm; a.row_slot = g.ps->row_slot; a.colview = c->colview;
     a.nbs_shift = 0;
     while ((1 << a.nbs_shift) < c->nbs) ++a.nbs_shift;
   }
-  c->last_bmode = g.bmode;
+  c->last_bmode = g.inst.bmode;
   a.nRB = c->nRB; a.gy_slabs = c->gy_slabs; a.slab_stride = slab_stride; a.n_rp = n_rp;
-  a.M = c->M; a.N = c->N; a.n_tiles = n_rp * n_ct; a.tps = (int)tiles_per_seg; a.n_ct = (int)n_ct; a.n_cseg = (int)n_cseg;
+  a.M = c->M; a.N = c->N; a.n_tiles = n_rp * n_ct; a.tps = (int)ws.tps; a.n_ct = (int)n_ct; a.n_cseg = (int)ws.n_cseg;
   a.want_gx = want_gx; a.want_gy = want_gy;
   a.ct0 = (int32_t)g.ct0[s];
-  const bool has_plain = pass_has_plain_loop(c, g, want_gx, want_gy);
-  if (has_plain) {
-    // PMF_PLAIN=0 (read at every pass, like PMF_XREG): every run takes the general tile loop; bit-identical results
-    const char *pe = getenv("PMF_PLAIN");
-    a.ptab = c->ptab; a.ptab_stride = (int32_t)(g.n_ct_all + 1); a.plain = !(pe && atoi(pe) == 0);
+  if (g.has_plain_loop()) {
+    // PMF_PLAIN=0: every run takes the general tile loop; bit-identical results
+    a.ptab = c->ptab; a.ptab_stride = (int32_t)(g.n_ct_all + 1); a.plain = g.sw.plain;
     a.plain_count = c->plain_count + loss_off;
   }
   a.gx_part = c->gx_part; a.piece_base = ws.d_piece_base_abs; a.gx_slot_stride = (int64_t)f.BM() * c->Kp;
-  {
-    const char *dbg = getenv("PMF_DEBUG_FLAGS");
-    a.dbg = dbg ? atoi(dbg) : 0;
-  }
+  a.dbg = g.sw.dbg;
 #ifdef PMF_STAMPS
   {
     static DevBuf<unsigned long long> d_stamps;
@@ -714,7 +729,6 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   }
 #endif
   a.views = c->d_views;
-  const bool batch = c->n_bv > 0;
   if (f.img != IMG_NONE) {
     if (s == 0) PMFCHK(sb_split_x(c, f));
     PMFCHK(sb_split_y(c, f, g.ct0[s], n_ct, s));
@@ -736,11 +750,10 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
   auto &ev = c->ev_pool[c->ev_used++];
   HIPCHK(hipEventRecord(ev.first, c->stream));
   c->last_kernel = f.kernel;
-  pmf_last_xreg = 0;
-  const int rc = f.launch[c->store == PMF_STORE_BF16](&c->dyn_lds, c->stream, a, grid, batch, c->mixed);
-  c->last_xreg = pmf_last_xreg;
-  // the counts the pass leaves in plain_count: those of its chunks so far, if the instance that writes them ran
-  c->last_plain_n = has_plain && pmf_last_xreg ? loss_off + grid : -1;
+  const int rc = f.launch[c->store == PMF_STORE_BF16](&c->dyn_lds, c->stream, a, grid, g.inst);
+  c->last_xreg = g.inst.xr;
+  // the counts the pass leaves in plain_count: those of its chunks so far, if its instance writes them
+  c->last_plain_n = g.has_plain_loop() ? loss_off + grid : -1;
   if (f.kernel != 0) c->sb_launches += 1;
   PMFCHK(rc);
   HIPCHK(hipEventRecord(ev.second, c->stream));   // the events bracket pmf_fused_kernel alone (= rocprofv3's kernel duration)
@@ -762,9 +775,9 @@ int launch_fused_chunk(pmf_ctx *c, const FusedGeom &g, int s, bool want_gx, bool
 // the whole data pass in one go (step-level API, single-chunk callers)
 int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy) {
   const FusedGeom g = fused_geometry(c, want_gx, want_gy, /*allow_chunks=*/c->n_chunks_req > 0);   // (chunks only on request)
-  PMFCHK(prepare_fused_pass(c, g, want_gx, want_gy));
-  PMFCHK(guard_fused_pass(c, g, want_gx, want_gy));
-  for (int s = 0; s < g.S; ++s) PMFCHK(launch_fused_chunk(c, g, s, want_gx, want_gy));
+  PMFCHK(prepare_fused_pass(c, g));
+  PMFCHK(guard_fused_pass(c, g));
+  for (int s = 0; s < g.S; ++s) PMFCHK(launch_fused_chunk(c, g, s));
   return 0;
 }
 
@@ -772,7 +785,6 @@ int launch_fused(pmf_ctx *c, bool want_gx, bool want_gy) {
 // performance bug).  bmode: 0 none, 1 LDS table with panel-local slots, 2 per-entry gathers; layer_path: 1 MFMA layer
 // pass, 2 VALU layer kernel; slots: columns of the dense batch table; xreg: 1 = the last fused launch held its X
 // fragments in registers (the only way to tell: its results are bit-identical to the LDS-read instance's).
-thread_local int pmf_last_xreg = 0;
 extern "C" int pmf_debug_last_kernel(pmf_ctx *c, int *kernel) {
   if (!c) return pmf_fail("null context");
   if (kernel) *kernel = c->last_kernel;
@@ -824,11 +836,10 @@ extern "C" int pmf_debug_pass_extents(pmf_ctx *c, int update_X, int update_Y, co
   PMFCHK(ctx_bind(c));
   PMFCHK(check_ready(c));
   if (!c->prepared) PMFCHK(prepare(c));
-  const bool want_gx = update_X != 0, want_gy = update_Y != 0;
-  const FusedGeom g = fused_geometry(c, want_gx, want_gy, /*allow_chunks=*/c->n_chunks_req > 0);
-  PMFCHK(prepare_fused_pass(c, g, want_gx, want_gy));
+  const FusedGeom g = fused_geometry(c, update_X != 0, update_Y != 0, /*allow_chunks=*/c->n_chunks_req > 0);
+  PMFCHK(prepare_fused_pass(c, g));
   PassExtent e[PMF_PASS_EXTENTS];
-  const int n = fused_pass_extents(c, g, want_gx, want_gy, e);
+  const int n = fused_pass_extents(c, g, e);
   if (n_max < n) return pmf_fail("pmf_debug_pass_extents: room for %d entries, %d needed", n_max, n);
   for (int i = 0; i < n; ++i) {
     if (cap_override && cap_override[i] >= 0) e[i].cap = cap_override[i];

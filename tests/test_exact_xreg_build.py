@@ -2,8 +2,8 @@
 the kernel metadata of the code objects inside the built libpmf_hip.so (extracted the way tests/test_build_scan.py does).
 
 An XW instance runs two waves per SIMD, 256 registers each.  The register-resident-X variants (XR, the last template
-argument) add 96 registers to an instance and are built only where that still fits without scratch (pmf_k_fused.hip,
-pmf_xreg_instance): a variant that spills would be slower than the LDS reads it replaces, and
+argument) add 96 registers to an instance and are built only where that still fits without scratch (pmf_common.h,
+pmf_exact_has_xr, the rule the host and pmf_k_fused.hip share): a variant that spills would be slower than the LDS reads it replaces, and
 nothing but this test would notice, because the results are bit-identical.
 
 The two instances that store D as bf16 with mixed noise models and batch layers sat at 256 VGPRs with 8 and 32 bytes of
