@@ -3,6 +3,9 @@
 This is the Python counterpart of the Julia `ccall` shim (julia/PathMatFacHIP.jl): it marshals numpy arrays
 in the reference's conventions (column-major matrices, 1-based inclusive ranges) to the C ABI.  There is NO
 CPU fallback: if the shared library is missing or a call fails, a PMFError is raised.
+
+The header's mirror -- structs, constants and the signature of every function -- is _abi.py; load_library installs the
+signatures, so the calls below hand plain Python numbers over and ctypes converts them to the declared types.
 """
 import ctypes as C
 import os
@@ -10,73 +13,16 @@ from pathlib import Path
 
 import numpy as np
 
+from ._abi import (COMM_ID_BYTES, DEBATCH_FILL_MISSING, DEBATCH_LINK, EXPORTS, HINGE_THRESHOLDS,  # noqa: F401
+                   HOST_ALLREDUCE_FN, IMPUTE_BATCH, IMPUTE_KEEP_OBSERVED, IMPUTE_LINK, NOISE, OPT, PARAM, PASS_EXTENTS_MAX,
+                   STORE, TERM, Csr, EmOpts, EmResult, FitOpts, FitResult, LbfgsOpts, LbfgsResult, SimOpts, bind)
+
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libpmf_hip.so"
-
-# bernoulli_sq_hinge and ordinal_sq_hinge3 are one kind (3) with different thresholds per column (set_noise_thresholds)
-NOISE = {"normal": 0, "bernoulli": 1, "poisson": 2, "bernoulli_sq_hinge": 3, "ordinal_sq_hinge3": 3}
-# the thresholds (t0, t1, t2) a kind-3 range gets by name.  ordinal_sq_hinge3's default is OURS (symmetric about 0, unit spacing)
-HINGE_THRESHOLDS = {"bernoulli_sq_hinge": (0.0, np.inf, np.inf), "ordinal_sq_hinge3": (-np.inf, -0.5, 0.5)}
-OPT = {"adagrad": 0, "adam": 1}
-STORE = {"f32": 0, "bf16": 1}
-TERM = {0: "max_epochs", 1: "loss_increase", 2: "abs_tol", 3: "rel_tol", 4: "nonfinite"}
-IMPUTE_BATCH, IMPUTE_LINK, IMPUTE_KEEP_OBSERVED = 1, 2, 4
-DEBATCH_LINK, DEBATCH_FILL_MISSING = 1, 2
-PARAM = {"X": 0, "Y": 1, "logsigma": 2, "mu": 3, "logdelta": 4, "theta": 5}
 
 
 class PMFError(RuntimeError):
     pass
-
-
-class FitOpts(C.Structure):
-    _fields_ = [("update_X", C.c_int32), ("update_Y", C.c_int32), ("update_col_layers", C.c_int32),
-                ("frozen_layers", C.c_int32), ("frozen_regs", C.c_int32), ("max_epochs", C.c_int32),
-                ("epoch", C.c_int32), ("tol_max_iters", C.c_int32), ("keep_trace", C.c_int32),
-                ("verbosity", C.c_int32), ("print_iter", C.c_int32), ("reserved", C.c_int32),
-                ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("capacity", C.c_int64)]
-
-
-class FitResult(C.Structure):
-    _fields_ = [("term_code", C.c_int32), ("epochs", C.c_int32), ("n_trace", C.c_int32),
-                ("trace_cap", C.c_int32), ("final_loss", C.c_double), ("loss_trace", C.POINTER(C.c_double)),
-                ("seconds", C.c_double)]
-
-
-class LbfgsOpts(C.Structure):
-    _fields_ = [("m", C.c_int32), ("max_iter", C.c_int32), ("backtrack_max_iter", C.c_int32), ("keep_trace", C.c_int32),
-                ("verbosity", C.c_int32), ("print_iter", C.c_int32), ("rel_tol", C.c_double), ("abs_tol", C.c_double),
-                ("backtrack_shrinkage", C.c_double), ("c1", C.c_double), ("sy_min", C.c_double)]
-
-
-class LbfgsResult(C.Structure):
-    _fields_ = [("term_code", C.c_int32), ("iters", C.c_int32), ("loss_evals", C.c_int32), ("grad_evals", C.c_int32),
-                ("resets", C.c_int32), ("n_trace", C.c_int32), ("trace_cap", C.c_int32), ("reserved", C.c_int32),
-                ("final_loss", C.c_double), ("seconds", C.c_double), ("loss_trace", C.POINTER(C.c_double)),
-                ("trial_trace", C.POINTER(C.c_int32)), ("flag_trace", C.POINTER(C.c_int32))]
-
-
-class EmOpts(C.Structure):
-    """pmf_em_opts"""
-    _fields_ = [("update_priors", C.c_int32), ("max_iter", C.c_int32), ("verbosity", C.c_int32), ("reserved", C.c_int32),
-                ("rtol", C.c_double)]
-
-
-class EmResult(C.Structure):
-    """pmf_em_result"""
-    _fields_ = [("iters", C.c_int32), ("n_diffs", C.c_int32), ("diffs_cap", C.c_int32), ("reserved", C.c_int32),
-                ("diffs", C.POINTER(C.c_double)), ("seconds", C.c_double)]
-
-
-class SimOpts(C.Structure):
-    """pmf_sim_opts"""
-    _fields_ = [("seed", C.c_uint64), ("row_offset", C.c_int64), ("noise", C.c_float), ("frac_missing", C.c_float)]
-
-
-class Csr(C.Structure):
-    """pmf_csr: one sparse block in 0-based CSR with sorted rows."""
-    _fields_ = [("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rowptr", C.POINTER(C.c_int64)),
-                ("col", C.POINTER(C.c_int32)), ("val", C.POINTER(C.c_float))]
 
 
 def csr_arrays(A):
@@ -106,37 +52,6 @@ def dense_to_csr(S):
     return rowptr, col, S.ravel()[flat].astype(np.float32)
 
 
-# every symbol include/pmf_hip.h declares (checked by tests/test_abi.py against the header and the .so)
-EXPORTS = [
-    "pmf_last_error", "pmf_version", "pmf_device_count", "pmf_create", "pmf_destroy", "pmf_set_stream", "pmf_synchronize",
-    "pmf_set_data", "pmf_set_data_device", "pmf_set_factors", "pmf_set_X", "pmf_set_Y", "pmf_get_factors",
-    "pmf_set_col_params", "pmf_get_col_params", "pmf_set_n_batch_views", "pmf_set_batch_view",
-    "pmf_get_batch_view", "pmf_set_noise", "pmf_clear_xreg", "pmf_add_xreg_l2", "pmf_add_xreg_group",
-    "pmf_clear_yreg", "pmf_add_yreg_l2", "pmf_add_yreg_group", "pmf_add_yreg_ard", "pmf_add_yreg_fsard",
-    "pmf_set_layer_regs", "pmf_set_optimizer", "pmf_set_lr", "pmf_get_lr", "pmf_reset_optimizer_state",
-    "pmf_fit", "pmf_epoch_begin", "pmf_epoch_step_local", "pmf_epoch_step_shared", "pmf_epoch_loss",
-    "pmf_grad_device_ptr", "pmf_get_grad", "pmf_forward", "pmf_stats", "pmf_kernel_time", "pmf_synth_data",
-    "pmf_set_precision", "pmf_get_precision",
-    "pmf_comm_get_unique_id", "pmf_comm_init", "pmf_comm_init_host", "pmf_comm_destroy", "pmf_comm_set_chunks",
-    "pmf_comm_info", "pmf_comm_allreduce", "pmf_get_opt_state", "pmf_fsard_update_A", "pmf_debug_last_path", "pmf_debug_last_kernel",
-    "pmf_debug_pass_extents", "pmf_debug_live_bytes", "pmf_debug_plain_table",
-    "pmf_add_xreg_network", "pmf_add_yreg_network", "pmf_get_reg_network_state", "pmf_add_xreg_l1", "pmf_add_yreg_l1",
-    "pmf_impute", "pmf_impute_device", "pmf_impute_entries", "pmf_debug_impute_offset",
-    "pmf_loss", "pmf_fit_lbfgs", "pmf_debug_lbfgs_direction",
-    "pmf_stage_init_logsigma", "pmf_stage_reweight_col_losses", "pmf_get_noise_weights", "pmf_stage_minimal_group_weights",
-    "pmf_stage_theta_delta_em",
-    "pmf_gram", "pmf_stage_lambda_max", "pmf_stage_whiten", "pmf_stage_rotate_by_svd", "pmf_stage_reorder_by_importance",
-    "pmf_debug_postprocess_times",
-    "pmf_fsard_update_A_csr",
-    "pmf_set_noise_thresholds", "pmf_get_noise_thresholds",
-    "pmf_remove_batch_effect", "pmf_remove_batch_effect_device", "pmf_remove_batch_effect_entries",
-    "pmf_simulate_data", "pmf_simulate_data_device", "pmf_simulate_data_resident",
-]
-
-COMM_ID_BYTES = 128
-HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
-
-
 def comm_unique_id(lib_path=None):
     """ncclGetUniqueId through the library (call on ONE rank; hand the 128 bytes to every rank)."""
     lib = load_library(lib_path)
@@ -144,7 +59,6 @@ def comm_unique_id(lib_path=None):
     if lib.pmf_comm_get_unique_id(buf) != 0:
         raise PMFError(lib.pmf_last_error().decode())
     return buf.raw
-
 
 
 def live_bytes(lib_path=None):
@@ -169,7 +83,8 @@ _lib = None
 
 
 def load_library(path=None):
-    """Loads libpmf_hip.so (does not touch the GPU).  Raises PMFError when it is missing."""
+    """Loads libpmf_hip.so (does not touch the GPU) and declares every function's types.  Raises PMFError when it is
+    missing."""
     global _lib
     if _lib is not None and path is None:
         return _lib
@@ -186,12 +101,12 @@ def load_library(path=None):
             import torch  # noqa: F401
         except ImportError:
             pass
-    lib = C.CDLL(str(p))
-    lib.pmf_last_error.restype = C.c_char_p
-    for name in EXPORTS:
-        getattr(lib, name)  # AttributeError if a declared symbol is not exported
+    lib = bind(C.CDLL(str(p)))  # AttributeError if a declared symbol is not exported
     _lib = lib
     return lib
+
+
+_PF, _PD, _PI32, _PI64 = (C.POINTER(t) for t in (C.c_float, C.c_double, C.c_int32, C.c_int64))
 
 
 def _f32(a, order="F"):
@@ -199,11 +114,24 @@ def _f32(a, order="F"):
 
 
 def _fp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None else C.POINTER(C.c_float)()
+    return a.ctypes.data_as(_PF) if a is not None else _PF()
+
+
+def _dp(a):
+    return a.ctypes.data_as(_PD)
+
+
+def _i32p(a):
+    return a.ctypes.data_as(_PI32)
 
 
 def _i64p(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int64))
+    return a.ctypes.data_as(_PI64)
+
+
+def _at(addr, ptype=_PF):
+    """A raw address (an int; None or 0 for NULL) as the pointer type the header declares for it."""
+    return C.cast(addr, ptype)
 
 
 def _flat(a):
@@ -227,7 +155,7 @@ class Context:
     def __init__(self, device=0, lib_path=None):
         self.lib = load_library(lib_path)
         self._h = C.c_void_p()
-        self._chk(self.lib.pmf_create(int(device), C.byref(self._h)))
+        self._chk(self.lib.pmf_create(device, C.byref(self._h)))
         self.M = self.N = self.K = 0
         self.view_shapes = []
         self.n_noise_ranges = 0     # ranges of the last set_noise (the library forgets them with a new data shape: so does this)
@@ -254,12 +182,12 @@ class Context:
         reads as "back to the library's own (non-blocking) stream" -- kernels there would NOT be ordered with work torch
         or RCCL issue behind the default stream -- so 0 is passed on as hipStreamLegacy, the legacy default stream itself."""
         HIP_STREAM_LEGACY = 1   # hip_runtime_api.h: #define hipStreamLegacy ((hipStream_t)1)
-        self._chk(self.lib.pmf_set_stream(self._h, C.c_void_p(stream_ptr if stream_ptr else HIP_STREAM_LEGACY)))
+        self._chk(self.lib.pmf_set_stream(self._h, stream_ptr if stream_ptr else HIP_STREAM_LEGACY))
         self._stream_adopted = True
 
     def use_own_stream(self):
         """Back to the library's own non-blocking stream (pmf_set_stream(ctx, NULL))."""
-        self._chk(self.lib.pmf_set_stream(self._h, C.c_void_p(0)))
+        self._chk(self.lib.pmf_set_stream(self._h, None))
         self._stream_adopted = False
 
     def synchronize(self):
@@ -271,13 +199,13 @@ class Context:
         if D.shape != (self.M, self.N):
             self.n_noise_ranges = 0
         self.M, self.N = D.shape
-        self._chk(self.lib.pmf_set_data(self._h, _fp(D), C.c_int64(self.M), C.c_int64(self.N), STORE[store]))
+        self._chk(self.lib.pmf_set_data(self._h, _fp(D), self.M, self.N, STORE[store]))
 
     def set_data_device(self, ptr, M, N, store="f32"):
         if (int(M), int(N)) != (self.M, self.N):
             self.n_noise_ranges = 0
         self.M, self.N = int(M), int(N)
-        self._chk(self.lib.pmf_set_data_device(self._h, C.c_void_p(ptr), C.c_int64(M), C.c_int64(N), STORE[store]))
+        self._chk(self.lib.pmf_set_data_device(self._h, _at(ptr, C.c_void_p), self.M, self.N, STORE[store]))
 
     def set_factors(self, X, Y):
         X, Y = _f32(X), _f32(Y)
@@ -322,15 +250,13 @@ class Context:
             bor = np.ascontiguousarray(b["batch_of_row"], dtype=np.int32)
             if bor.shape != (self.M,):
                 raise PMFError("batch_of_row must have one entry per row")
-            self._chk(self.lib.pmf_set_batch_view(self._h, v, C.c_int64(b["start1"]), C.c_int64(b["stop1"]), nb,
-                                                  bor.ctypes.data_as(C.POINTER(C.c_int32)), _fp(ld), _fp(th)))
+            self._chk(self.lib.pmf_set_batch_view(self._h, v, b["start1"], b["stop1"], nb, _i32p(bor), _fp(ld), _fp(th)))
             self.view_shapes.append((nb, Nv))
 
     def update_batch_values(self, v, start1, stop1, batch_of_row, logdelta, theta):
         ld, th = _f32(logdelta), _f32(theta)
         bor = np.ascontiguousarray(batch_of_row, dtype=np.int32)
-        self._chk(self.lib.pmf_set_batch_view(self._h, v, C.c_int64(start1), C.c_int64(stop1), ld.shape[0],
-                                              bor.ctypes.data_as(C.POINTER(C.c_int32)), _fp(ld), _fp(th)))
+        self._chk(self.lib.pmf_set_batch_view(self._h, v, start1, stop1, ld.shape[0], _i32p(bor), _fp(ld), _fp(th)))
 
     def get_batch_view(self, v):
         nb, Nv = self.view_shapes[v]
@@ -343,8 +269,7 @@ class Context:
         s, e = _ranges(ranges)
         k = np.ascontiguousarray([NOISE[x] if isinstance(x, str) else int(x) for x in kinds], dtype=np.int32)
         w = None if weights is None else _f32(weights)
-        self._chk(self.lib.pmf_set_noise(self._h, len(k), _i64p(s), _i64p(e), k.ctypes.data_as(C.POINTER(C.c_int32)),
-                                         _fp(w)))
+        self._chk(self.lib.pmf_set_noise(self._h, len(k), _i64p(s), _i64p(e), _i32p(k), _fp(w)))
         self.n_noise_ranges = len(k)
         # a range named ordinal_sq_hinge3 gets that model's default thresholds (the library's default for kind 3 is bernoulli_sq_hinge's)
         named = [(r, HINGE_THRESHOLDS[x]) for r, x in zip(ranges, kinds) if x == "ordinal_sq_hinge3"]
@@ -374,7 +299,7 @@ class Context:
     def add_reg_l2(self, which, w, p=1.0):
         w = _f32(np.asarray(w).ravel())
         f = self.lib.pmf_add_xreg_l2 if which == "X" else self.lib.pmf_add_yreg_l2
-        self._chk(f(self._h, _fp(w), C.c_float(p)))
+        self._chk(f(self._h, _fp(w), p))
 
     def add_reg_group(self, which, ranges, w, p=1.0):
         s, e = _ranges(ranges)
@@ -382,18 +307,18 @@ class Context:
         if w.shape != (len(s), self.K):
             raise PMFError(f"group weights must be (n_groups, K) = ({len(s)}, {self.K}); got {w.shape}")
         f = self.lib.pmf_add_xreg_group if which == "X" else self.lib.pmf_add_yreg_group
-        self._chk(f(self._h, len(s), _i64p(s), _i64p(e), _fp(w), C.c_float(p)))
+        self._chk(f(self._h, len(s), _i64p(s), _i64p(e), _fp(w), p))
 
     def add_yreg_ard(self, ranges, alpha, beta, p=1.0):
         s, e = _ranges(ranges)
         a, b = _f32(np.asarray(alpha).ravel()), _f32(np.asarray(beta).ravel())
-        self._chk(self.lib.pmf_add_yreg_ard(self._h, len(s), _i64p(s), _i64p(e), _fp(a), _fp(b), C.c_float(p)))
+        self._chk(self.lib.pmf_add_yreg_ard(self._h, len(s), _i64p(s), _i64p(e), _fp(a), _fp(b), p))
 
     def add_yreg_fsard(self, alpha, beta, p=1.0):
         a, b = _f32(np.asarray(alpha).ravel()), _f32(beta)
         if a.shape != (self.N,) or b.shape != (self.K, self.N):
             raise PMFError("FeatureSetARD: alpha must be N, beta K x N")
-        self._chk(self.lib.pmf_add_yreg_fsard(self._h, _fp(a), _fp(b), C.c_float(p)))
+        self._chk(self.lib.pmf_add_yreg_fsard(self._h, _fp(a), _fp(b), p))
 
     def add_reg_network(self, which, AA, AB, BB, u0=None, p=1.0):
         """NetworkRegularizer: per factor the scipy sparse blocks AA (n x n), AB (n x v_k), BB (v_k x v_k); u0: per factor
@@ -405,8 +330,7 @@ class Context:
             for k, A in enumerate(mats):
                 shape, rp, col, val = csr_arrays(A)
                 keep.append((rp, col, val))
-                arr[k] = Csr(shape[0], shape[1], rp.ctypes.data_as(C.POINTER(C.c_int64)),
-                             col.ctypes.data_as(C.POINTER(C.c_int32)), _fp(val))
+                arr[k] = Csr(shape[0], shape[1], _i64p(rp), _i32p(col), _fp(val))
             blocks.append(arr)
         up = None
         if u0 is not None:
@@ -415,9 +339,9 @@ class Context:
                 if u.shape != (B.shape[0],):
                     raise PMFError(f"network regularizer: u0[{k}] has {u.shape[0]} entries, BB[{k}] {B.shape[0]} rows")
             keep.append(us)
-            up = (C.POINTER(C.c_float) * K)(*[_fp(u) for u in us])
+            up = (_PF * K)(*[_fp(u) for u in us])
         f = self.lib.pmf_add_xreg_network if which == "X" else self.lib.pmf_add_yreg_network
-        self._chk(f(self._h, K, blocks[0], blocks[1], blocks[2], up, C.c_float(p)))
+        self._chk(f(self._h, K, blocks[0], blocks[1], blocks[2], up, p))
         if not hasattr(self, "_net_v"):
             self._net_v = {}
         self._net_v[which] = [int(B.shape[0]) for B in BB]
@@ -428,7 +352,7 @@ class Context:
         n = v[k] if v is not None and 0 <= k < len(v) else 0
         u = np.zeros(n, np.float32)
         it = C.c_int(0)
-        self._chk(self.lib.pmf_get_reg_network_state(self._h, PARAM[which], int(k), _fp(u) if n else None, C.byref(it)))
+        self._chk(self.lib.pmf_get_reg_network_state(self._h, PARAM[which], k, _fp(u) if n else None, C.byref(it)))
         return u, it.value
 
     def add_reg_l1(self, which, w, mask=None, p=1.0):
@@ -444,7 +368,7 @@ class Context:
                 raise PMFError(f"L1 mask must be K x n = ({self.K}, {n}); got {m.shape}")
             mp = m.ctypes.data_as(C.POINTER(C.c_uint8))
         f = self.lib.pmf_add_xreg_l1 if which == "X" else self.lib.pmf_add_yreg_l1
-        self._chk(f(self._h, _fp(w), mp, C.c_float(p)))
+        self._chk(f(self._h, _fp(w), mp, p))
 
     def set_layer_regs(self, ranges=None, w_logsigma=None, c_logsigma=None, w_mu=None, c_mu=None,
                        w_logdelta=None, c_logdelta=None, w_theta=None, c_theta=None):
@@ -456,11 +380,10 @@ class Context:
 
     # ---- optimizer
     def set_optimizer(self, kind="adagrad", lr=1.0, eps=1e-8, beta1=0.9, beta2=0.999):
-        self._chk(self.lib.pmf_set_optimizer(self._h, OPT[kind], C.c_float(lr), C.c_float(eps), C.c_float(beta1),
-                                             C.c_float(beta2)))
+        self._chk(self.lib.pmf_set_optimizer(self._h, OPT[kind], lr, eps, beta1, beta2))
 
     def set_lr(self, lr):
-        self._chk(self.lib.pmf_set_lr(self._h, C.c_float(lr)))
+        self._chk(self.lib.pmf_set_lr(self._h, lr))
 
     def get_lr(self):
         v = C.c_float(0)
@@ -489,7 +412,7 @@ class Context:
         trace = np.zeros(cap, np.float64)
         r = FitResult()
         r.trace_cap = cap
-        r.loss_trace = trace.ctypes.data_as(C.POINTER(C.c_double))
+        r.loss_trace = _dp(trace)
         self._chk(self.lib.pmf_fit(self._h, C.byref(o), C.byref(r)))
         return {"term_code": TERM[r.term_code], "epochs": r.epochs, "loss": trace[:r.n_trace].copy(),
                 "final_loss": r.final_loss, "seconds": r.seconds}
@@ -509,9 +432,7 @@ class Context:
         loss, trials, flags = np.zeros(cap, np.float64), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
         r = LbfgsResult()
         r.trace_cap = cap
-        r.loss_trace = loss.ctypes.data_as(C.POINTER(C.c_double))
-        r.trial_trace = trials.ctypes.data_as(C.POINTER(C.c_int32))
-        r.flag_trace = flags.ctypes.data_as(C.POINTER(C.c_int32))
+        r.loss_trace, r.trial_trace, r.flag_trace = _dp(loss), _i32p(trials), _i32p(flags)
         self._chk(self.lib.pmf_fit_lbfgs(self._h, C.byref(o), C.byref(r)))
         n = r.n_trace
         return {"term_code": TERM[r.term_code], "iters": r.iters, "loss": loss[:n].copy(), "trials": trials[:n].copy(),
@@ -553,30 +474,22 @@ class Context:
         self._chk(self.lib.pmf_grad_device_ptr(self._h, PARAM[which], C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def _param_shape(self, which, view):
+        """The shape of a parameter group (view: the batch view of logdelta / theta)."""
+        if which in ("X", "Y"):
+            return (self.K, self.M if which == "X" else self.N)
+        return (self.N,) if which in ("logsigma", "mu") else self.view_shapes[view]
+
     def get_grad(self, which, view=0):
-        if which == "X":
-            out = np.zeros((self.K, self.M), np.float32, order="F")
-        elif which == "Y":
-            out = np.zeros((self.K, self.N), np.float32, order="F")
-        elif which in ("logsigma", "mu"):
-            out = np.zeros(self.N, np.float32)
-        else:
-            out = np.zeros(self.view_shapes[view], np.float32, order="F")
-        self._chk(self.lib.pmf_get_grad(self._h, PARAM[which], int(view), _fp(out)))
+        out = np.zeros(self._param_shape(which, view), np.float32, order="F")
+        self._chk(self.lib.pmf_get_grad(self._h, PARAM[which], view, _fp(out)))
         return out
 
     def get_opt_state(self, which, view=0):
         """(acc, mom) of a parameter group in the parameter's shape (pmf_get_opt_state)."""
-        if which == "X":
-            shape = (self.K, self.M)
-        elif which == "Y":
-            shape = (self.K, self.N)
-        elif which in ("logsigma", "mu"):
-            shape = (self.N,)
-        else:
-            shape = self.view_shapes[view]
+        shape = self._param_shape(which, view)
         acc, mom = np.zeros(shape, np.float32, order="F"), np.zeros(shape, np.float32, order="F")
-        self._chk(self.lib.pmf_get_opt_state(self._h, PARAM[which], int(view), _fp(acc), _fp(mom)))
+        self._chk(self.lib.pmf_get_opt_state(self._h, PARAM[which], view, _fp(acc), _fp(mom)))
         return acc, mom
 
     def _fsard_call(self, entry, start1, stop1, L, Nv, s_args, alpha, lam, alpha0, v0, lr, ssq_grad, max_epochs, term_iter,
@@ -590,9 +503,8 @@ class Context:
         A = np.zeros((L, self.K), np.float32)
         beta = np.zeros((self.K, max(Nv, 0)), np.float32, order="F")
         best, ep = C.c_double(0), C.c_int(0)
-        self._chk(entry(self._h, C.c_int64(start1), C.c_int64(stop1), int(L), *s_args, _fp(al), _fp(lm), C.c_float(alpha0),
-                        C.c_float(v0), C.c_float(lr), _fp(ssq_grad), _fp(A), int(max_epochs), int(term_iter),
-                        C.c_double(atol), C.byref(best), C.byref(ep), _fp(beta)))
+        self._chk(entry(self._h, start1, stop1, L, *s_args, _fp(al), _fp(lm), alpha0, v0, lr, _fp(ssq_grad), _fp(A),
+                        int(max_epochs), int(term_iter), atol, C.byref(best), C.byref(ep), _fp(beta)))
         return A, beta, best.value, ep.value
 
     def fsard_update_A(self, start1, stop1, S, alpha, lam, alpha0, v0, lr, ssq_grad, max_epochs=1000, term_iter=20,
@@ -633,14 +545,39 @@ class Context:
         lm = np.ascontiguousarray(lam, dtype=np.float32)
         if al.size != Nv or lm.size != self.K:
             raise PMFError("alpha must have one entry per column of the view and lambda one per factor")
-        s_args = (_i64p(rowptr), col.ctypes.data_as(C.POINTER(C.c_int32)), _fp(val))
-        return self._fsard_call(self.lib.pmf_fsard_update_A_csr, start1, stop1, L, Nv, s_args, al, lm, alpha0, v0, lr,
-                                ssq_grad, max_epochs, term_iter, atol)
+        return self._fsard_call(self.lib.pmf_fsard_update_A_csr, start1, stop1, L, Nv, (_i64p(rowptr), _i32p(col), _fp(val)),
+                                al, lm, alpha0, v0, lr, ssq_grad, max_epochs, term_iter, atol)
 
     def forward(self):
         Z = np.zeros((self.M, self.N), np.float32, order="F")
         self._chk(self.lib.pmf_forward(self._h, _fp(Z)))
         return Z
+
+    # ---- what the predictions, the simulated data and the batch-corrected data share
+    def _rows(self, row_start1, row_stop1):
+        """-> (row_stop1, defaulting to the last row; the number of rows of the 1-based inclusive range, possibly <= 0)."""
+        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
+        return row_stop1, row_stop1 - int(row_start1) + 1
+
+    def _row_block(self, name, rows, out, out_row):
+        """The host output of a block of `rows` rows x N columns: `out`, allocated when None and validated otherwise, the
+        block's first row in it and the pointer to that row of its first column -> (out, out_row, pointer)."""
+        if out is None:
+            out, out_row = np.zeros((rows, self.N), np.float32, order="F"), 0
+        elif out.dtype != np.float32 or out.ndim != 2 or not out.flags.f_contiguous or out.shape[1] != self.N:
+            raise PMFError(f"{name}: out must be a Fortran-ordered float32 array with N columns")
+        if out_row < 0 or out_row + rows > out.shape[0]:
+            raise PMFError(f"{name}: the block does not fit in out")
+        return out, out_row, _at(out.ctypes.data + 4 * int(out_row) if out.size else None)
+
+    @staticmethod
+    def _entries(name, rows1, cols1):
+        """The 1-based entry lists as the library takes them, and the output vector -> (rows, cols, out)."""
+        r = np.ascontiguousarray(rows1, dtype=np.int64).ravel()
+        c = np.ascontiguousarray(cols1, dtype=np.int64).ravel()
+        if r.shape != c.shape:
+            raise PMFError(f"{name}: rows and columns must have the same length")
+        return r, c, np.zeros(max(r.size, 1), np.float32)
 
     # ---- predictions
     @staticmethod
@@ -653,34 +590,21 @@ class Context:
         `out` (optional): a float32 Fortran-ordered array with N columns; the block is written to its rows out_row ..
         out_row + rows - 1 with its row count as the leading dimension, and nothing else in it is touched.
         Returns the rows x N block."""
-        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
-        rows = max(row_stop1 - int(row_start1) + 1, 0)
-        if out is None:
-            out, out_row = np.zeros((rows, self.N), np.float32, order="F"), 0
-        elif out.dtype != np.float32 or out.ndim != 2 or not out.flags.f_contiguous or out.shape[1] != self.N:
-            raise PMFError("impute: out must be a Fortran-ordered float32 array with N columns")
-        if out_row < 0 or out_row + rows > out.shape[0]:
-            raise PMFError("impute: the block does not fit in out")
-        ptr = C.c_void_p(out.ctypes.data + 4 * int(out_row)) if out.size else None
-        self._chk(self.lib.pmf_impute(self._h, int(flags), C.c_int64(row_start1), C.c_int64(row_stop1), ptr,
-                                      C.c_int64(out.shape[0])))
+        row_stop1, rows = self._rows(row_start1, row_stop1)
+        rows = max(rows, 0)
+        out, out_row, ptr = self._row_block("impute", rows, out, out_row)
+        self._chk(self.lib.pmf_impute(self._h, flags, row_start1, row_stop1, ptr, out.shape[0]))
         return out[out_row:out_row + rows]
 
     def impute_device(self, ptr, flags=0, row_start1=1, row_stop1=None, ld=None):
         """pmf_impute_device: the same into device memory at address `ptr` (e.g. a torch tensor's data_ptr())."""
-        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
-        ld = row_stop1 - int(row_start1) + 1 if ld is None else int(ld)
-        self._chk(self.lib.pmf_impute_device(self._h, int(flags), C.c_int64(row_start1), C.c_int64(row_stop1),
-                                             C.c_void_p(ptr), C.c_int64(ld)))
+        row_stop1, rows = self._rows(row_start1, row_stop1)
+        self._chk(self.lib.pmf_impute_device(self._h, flags, row_start1, row_stop1, _at(ptr), rows if ld is None else ld))
 
     def impute_entries(self, rows1, cols1, flags=0):
         """pmf_impute_entries: the predictions at the listed (row, column) entries, 1-based."""
-        r = np.ascontiguousarray(rows1, dtype=np.int64).ravel()
-        c = np.ascontiguousarray(cols1, dtype=np.int64).ravel()
-        if r.shape != c.shape:
-            raise PMFError("impute_entries: rows and columns must have the same length")
-        out = np.zeros(max(r.size, 1), np.float32)
-        self._chk(self.lib.pmf_impute_entries(self._h, int(flags), C.c_int64(r.size), _i64p(r), _i64p(c), _fp(out)))
+        r, c, out = self._entries("impute_entries", rows1, cols1)
+        self._chk(self.lib.pmf_impute_entries(self._h, flags, r.size, _i64p(r), _i64p(c), _fp(out)))
         return out[:r.size]
 
     # ---- simulated data
@@ -692,28 +616,20 @@ class Context:
                       out_row=0):
         """pmf_simulate_data: rows row_start1..row_stop1 (1-based, inclusive; default all) x all columns drawn from the
         current parameters; `out` and `out_row` as in `impute`.  row_offset: the global index of local row 1."""
-        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
-        rows = max(row_stop1 - int(row_start1) + 1, 0)
-        if out is None:
-            out, out_row = np.zeros((rows, self.N), np.float32, order="F"), 0
-        elif out.dtype != np.float32 or out.ndim != 2 or not out.flags.f_contiguous or out.shape[1] != self.N:
-            raise PMFError("simulate_data: out must be a Fortran-ordered float32 array with N columns")
-        if out_row < 0 or out_row + rows > out.shape[0]:
-            raise PMFError("simulate_data: the block does not fit in out")
-        ptr = C.c_void_p(out.ctypes.data + 4 * int(out_row)) if out.size else None
+        row_stop1, rows = self._rows(row_start1, row_stop1)
+        rows = max(rows, 0)
+        out, out_row, ptr = self._row_block("simulate_data", rows, out, out_row)
         o = self.sim_opts(seed, noise, frac_missing, row_offset)
-        self._chk(self.lib.pmf_simulate_data(self._h, C.byref(o), C.c_int64(row_start1), C.c_int64(row_stop1), ptr,
-                                             C.c_int64(out.shape[0])))
+        self._chk(self.lib.pmf_simulate_data(self._h, C.byref(o), row_start1, row_stop1, ptr, out.shape[0]))
         return out[out_row:out_row + rows]
 
     def simulate_data_device(self, ptr, seed=0, noise=0.1, frac_missing=0.0, row_offset=0, row_start1=1, row_stop1=None,
                              ld=None):
         """pmf_simulate_data_device: the same into device memory at address `ptr`."""
-        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
-        ld = row_stop1 - int(row_start1) + 1 if ld is None else int(ld)
+        row_stop1, rows = self._rows(row_start1, row_stop1)
         o = self.sim_opts(seed, noise, frac_missing, row_offset)
-        self._chk(self.lib.pmf_simulate_data_device(self._h, C.byref(o), C.c_int64(row_start1), C.c_int64(row_stop1),
-                                                    C.c_void_p(ptr), C.c_int64(ld)))
+        self._chk(self.lib.pmf_simulate_data_device(self._h, C.byref(o), row_start1, row_stop1, _at(ptr),
+                                                    rows if ld is None else ld))
 
     def simulate_data_resident(self, seed=0, noise=0.1, frac_missing=0.0, row_offset=0):
         """pmf_simulate_data_resident: overwrites the data matrix resident on the device."""
@@ -731,43 +647,29 @@ class Context:
         array unless it is one), or None for the data matrix resident on the device.  `out` as in `impute`; passing the same
         Fortran-ordered array as Z and out (out_row = 0, its row count = rows) corrects it in place.  Returns the rows x N
         block."""
-        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
-        rows = max(row_stop1 - int(row_start1) + 1, 0)
-        zp, ldz = None, 0
+        row_stop1, rows = self._rows(row_start1, row_stop1)
+        rows = max(rows, 0)
+        Zf, ldz = None, 0
         if Z is not None:
-            Zf = _f32(Z)
+            Zf, ldz = _f32(Z), max(rows, 1)
             if Zf.shape != (rows, self.N):
                 raise PMFError(f"remove_batch_effect: Z must be rows x N = {rows} x {self.N}")
-            zp, ldz = C.c_void_p(Zf.ctypes.data), max(rows, 1)
-        if out is None:
-            out, out_row = np.zeros((rows, self.N), np.float32, order="F"), 0
-        elif out.dtype != np.float32 or out.ndim != 2 or not out.flags.f_contiguous or out.shape[1] != self.N:
-            raise PMFError("remove_batch_effect: out must be a Fortran-ordered float32 array with N columns")
-        if out_row < 0 or out_row + rows > out.shape[0]:
-            raise PMFError("remove_batch_effect: the block does not fit in out")
-        ptr = C.c_void_p(out.ctypes.data + 4 * int(out_row)) if out.size else None
-        self._chk(self.lib.pmf_remove_batch_effect(self._h, int(flags), C.c_int64(row_start1), C.c_int64(row_stop1), zp,
-                                                   C.c_int64(ldz), ptr, C.c_int64(out.shape[0])))
+        out, out_row, ptr = self._row_block("remove_batch_effect", rows, out, out_row)
+        self._chk(self.lib.pmf_remove_batch_effect(self._h, flags, row_start1, row_stop1, _fp(Zf), ldz, ptr, out.shape[0]))
         return out[out_row:out_row + rows]
 
     def remove_batch_effect_device(self, out_ptr, flags=0, row_start1=1, row_stop1=None, z_ptr=None, ldz=None, ld=None):
         """pmf_remove_batch_effect_device: the same between device matrices (addresses, e.g. a torch tensor's data_ptr());
         z_ptr = None: the resident data matrix."""
-        row_stop1 = self.M if row_stop1 is None else int(row_stop1)
-        rows = row_stop1 - int(row_start1) + 1
-        ld = rows if ld is None else int(ld)
-        ldz = rows if ldz is None else int(ldz)
-        self._chk(self.lib.pmf_remove_batch_effect_device(self._h, int(flags), C.c_int64(row_start1), C.c_int64(row_stop1),
-                                                          C.c_void_p(z_ptr) if z_ptr else None, C.c_int64(ldz),
-                                                          C.c_void_p(out_ptr), C.c_int64(ld)))
+        row_stop1, rows = self._rows(row_start1, row_stop1)
+        self._chk(self.lib.pmf_remove_batch_effect_device(self._h, flags, row_start1, row_stop1, _at(z_ptr),
+                                                          rows if ldz is None else ldz, _at(out_ptr),
+                                                          rows if ld is None else ld))
 
     def remove_batch_effect_entries(self, rows1, cols1, values=None, flags=0):
         """pmf_remove_batch_effect_entries: the corrected values at the listed (row, column) entries, 1-based; values = None:
         the entries of the resident data matrix."""
-        r = np.ascontiguousarray(rows1, dtype=np.int64).ravel()
-        c = np.ascontiguousarray(cols1, dtype=np.int64).ravel()
-        if r.shape != c.shape:
-            raise PMFError("remove_batch_effect_entries: rows and columns must have the same length")
+        r, c, out = self._entries("remove_batch_effect_entries", rows1, cols1)
         v = None
         if values is not None:
             v = np.ascontiguousarray(values, dtype=np.float32).ravel()
@@ -775,10 +677,16 @@ class Context:
                 raise PMFError("remove_batch_effect_entries: one value per entry")
             if v.size == 0:
                 v = np.zeros(1, np.float32)
-        out = np.zeros(max(r.size, 1), np.float32)
-        self._chk(self.lib.pmf_remove_batch_effect_entries(self._h, int(flags), C.c_int64(r.size), _i64p(r), _i64p(c), _fp(v),
-                                                           _fp(out)))
+        self._chk(self.lib.pmf_remove_batch_effect_entries(self._h, flags, r.size, _i64p(r), _i64p(c), _fp(v), _fp(out)))
         return out[:r.size]
+
+    def _by_view(self, flat):
+        """A vector flat over (view, column, batch) -> per view its nb x N_v array (a copy)."""
+        out, off = [], 0
+        for nb, nv in self.view_shapes:
+            out.append(flat[off:off + nb * nv].reshape((nb, nv), order="F").copy())
+            off += nb * nv
+        return out
 
     def stats(self, use_factors=False):
         """Masked column and (batch, column) statistics (pmf_stats).  Returns a dict of float32 arrays."""
@@ -788,12 +696,7 @@ class Context:
         bc, bs = np.zeros(max(nbt, 1), np.float32), np.zeros(max(nbt, 1), np.float32)
         self._chk(self.lib.pmf_stats(self._h, int(use_factors), _fp(out["n"]), _fp(out["sum"]), _fp(out["sumsq"]),
                                      _fp(out["sqerr"]), _fp(out["ssq_grad"]), _fp(bc), _fp(bs)))
-        off, cnt, sq = 0, [], []
-        for nb, nv in self.view_shapes:
-            cnt.append(bc[off:off + nb * nv].reshape((nb, nv), order="F").copy())
-            sq.append(bs[off:off + nb * nv].reshape((nb, nv), order="F").copy())
-            off += nb * nv
-        out["batch_count"], out["batch_sqerr"] = cnt, sq
+        out["batch_count"], out["batch_sqerr"] = self._by_view(bc), self._by_view(bs)
         return out
 
     # ---- the closed-form stages in the library (pmf_stage_*): the statistics never leave the device
@@ -803,7 +706,7 @@ class Context:
 
     def stage_reweight_col_losses(self, M_total):
         """pmf_stage_reweight_col_losses: the noise weights <- 1 / (rms column gradient * sigma) (get_noise_weights)."""
-        self._chk(self.lib.pmf_stage_reweight_col_losses(self._h, C.c_int64(int(M_total))))
+        self._chk(self.lib.pmf_stage_reweight_col_losses(self._h, int(M_total)))
 
     def get_noise_weights(self):
         w = np.zeros(self.N, np.float32)
@@ -814,7 +717,7 @@ class Context:
         """pmf_stage_minimal_group_weights: one weight per column range of the noise model (as many as the last set_noise
         on this data shape passed; without one the library refuses and writes nothing)."""
         w = np.zeros(max(self.n_noise_ranges, 1), np.float32)
-        self._chk(self.lib.pmf_stage_minimal_group_weights(self._h, C.c_int64(int(M_total)), _fp(w)))
+        self._chk(self.lib.pmf_stage_minimal_group_weights(self._h, int(M_total), _fp(w)))
         return w[:self.n_noise_ranges]
 
     def stage_theta_delta_em(self, delta2, sigma2, update_priors=True, max_iter=100, rtol=1e-8, verbosity=0):
@@ -832,53 +735,44 @@ class Context:
         o = EmOpts(int(bool(update_priors)), int(max_iter), int(verbosity), 0, float(rtol))
         r = EmResult()
         r.diffs_cap = cap
-        r.diffs = diffs.ctypes.data_as(C.POINTER(C.c_double))
-        self._chk(self.lib.pmf_stage_theta_delta_em(self._h, C.byref(o), _fp(s2), flat.ctypes.data_as(C.POINTER(C.c_double)),
-                                                    C.byref(r)))
-        out, off = [], 0
-        for nb, nv in self.view_shapes:
-            out.append(flat[off:off + nb * nv].reshape((nb, nv), order="F").copy())
-            off += nb * nv
+        r.diffs = _dp(diffs)
+        self._chk(self.lib.pmf_stage_theta_delta_em(self._h, C.byref(o), _fp(s2), _dp(flat), C.byref(r)))
         theta = [self.get_batch_view(v)[1] for v in range(len(self.view_shapes))]
-        return dict(theta=theta, delta2=out, diffs=diffs[:r.n_diffs].copy(), iters=r.iters, seconds=r.seconds)
+        return dict(theta=theta, delta2=self._by_view(flat), diffs=diffs[:r.n_diffs].copy(), iters=r.iters, seconds=r.seconds)
 
     # ---- the factor post-processing stages in the library: X and Y never leave the device
-    @staticmethod
-    def _dp(a):
-        return a.ctypes.data_as(C.POINTER(C.c_double))
-
     def gram(self, which, ranges, diag_only=False):
         """pmf_gram of X (which = 0) or Y (1) over 1-based inclusive column ranges: (n_groups, K, K) float64, or with
         diag_only (n_groups, K).  X on a communicator of more than one rank: summed over the ranks."""
         s, e = _ranges(ranges)
         out = np.zeros((len(s), self.K) if diag_only else (len(s), self.K, self.K), np.float64)
-        self._chk(self.lib.pmf_gram(self._h, int(which), len(s), _i64p(s), _i64p(e), int(bool(diag_only)), self._dp(out)))
+        self._chk(self.lib.pmf_gram(self._h, which, len(s), _i64p(s), _i64p(e), int(bool(diag_only)), _dp(out)))
         return out
 
     def stage_lambda_max(self, which, ranges):
         """pmf_stage_lambda_max: the largest eigenvalue of each range's Gram matrix (float64)."""
         s, e = _ranges(ranges)
         lam = np.zeros(max(len(s), 1), np.float64)
-        self._chk(self.lib.pmf_stage_lambda_max(self._h, int(which), len(s), _i64p(s), _i64p(e), self._dp(lam)))
+        self._chk(self.lib.pmf_stage_lambda_max(self._h, which, len(s), _i64p(s), _i64p(e), _dp(lam)))
         return lam[:len(s)]
 
     def stage_whiten(self, M_total, view_ranges):
         """pmf_stage_whiten on the context's X, Y and logsigma.  Returns (x_rms [K], y_rms_max [views])."""
         s, e = _ranges(view_ranges)
         xr, c = np.zeros(max(self.K, 1), np.float64), np.zeros(max(len(s), 1), np.float64)
-        self._chk(self.lib.pmf_stage_whiten(self._h, C.c_int64(int(M_total)), len(s), _i64p(s), _i64p(e), self._dp(xr), self._dp(c)))
+        self._chk(self.lib.pmf_stage_whiten(self._h, int(M_total), len(s), _i64p(s), _i64p(e), _dp(xr), _dp(c)))
         return xr[:self.K], c[:len(s)]
 
     def stage_rotate_by_svd(self):
         """pmf_stage_rotate_by_svd on the context's X and Y.  Returns (singular values [K], U [K x K], U[:, r] the r-th vector)."""
         sing, U = np.zeros(max(self.K, 1), np.float64), np.zeros((max(self.K, 1),) * 2, np.float64)
-        self._chk(self.lib.pmf_stage_rotate_by_svd(self._h, self._dp(sing), self._dp(U)))
+        self._chk(self.lib.pmf_stage_rotate_by_svd(self._h, _dp(sing), _dp(U)))
         return sing[:self.K], U[:self.K, :self.K]
 
     def stage_reorder_by_importance(self):
         """pmf_stage_reorder_by_importance on the context's X and Y.  Returns the 0-based permutation (new row r = old row p[r])."""
         p = np.zeros(max(self.K, 1), np.int32)
-        self._chk(self.lib.pmf_stage_reorder_by_importance(self._h, p.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._chk(self.lib.pmf_stage_reorder_by_importance(self._h, _i32p(p)))
         return p[:self.K].astype(np.int64)
 
     def postprocess_times(self):
@@ -892,14 +786,13 @@ class Context:
         """Attaches an RCCL communicator (pmf_comm_init; collective over the ranks).  pmf_fit then shards by rows."""
         if len(unique_id) != COMM_ID_BYTES:
             raise PMFError("unique id must be 128 bytes (comm_unique_id())")
-        self._chk(self.lib.pmf_comm_init(self._h, int(rank), int(nranks), C.c_char_p(bytes(unique_id))))
+        self._chk(self.lib.pmf_comm_init(self._h, rank, nranks, bytes(unique_id)))
 
     def comm_init_host(self, rank, nranks, allreduce):
         """Host-staged transport: `allreduce(array)` must sum a numpy array in place over the ranks (tests: gloo)."""
         def _cb(_user, buf, count, dtype):
             try:
-                ct = C.c_double if dtype == 1 else C.c_float
-                arr = np.ctypeslib.as_array(C.cast(buf, C.POINTER(ct)), shape=(int(count),))
+                arr = np.ctypeslib.as_array(_at(buf, _PD if dtype == 1 else _PF), shape=(int(count),))
                 allreduce(arr)
                 return 0
             except Exception:   # never unwind through the C frames
@@ -907,20 +800,20 @@ class Context:
                 traceback.print_exc()
                 return -1
         self._host_cb = HOST_ALLREDUCE_FN(_cb)   # keep alive as long as the communicator
-        self._chk(self.lib.pmf_comm_init_host(self._h, int(rank), int(nranks), self._host_cb, None))
+        self._chk(self.lib.pmf_comm_init_host(self._h, rank, nranks, self._host_cb, None))
 
     def comm_destroy(self):
         self._chk(self.lib.pmf_comm_destroy(self._h))
         self._host_cb = None
 
     def comm_set_chunks(self, n):
-        self._chk(self.lib.pmf_comm_set_chunks(self._h, int(n)))
+        self._chk(self.lib.pmf_comm_set_chunks(self._h, n))
 
     def comm_allreduce(self, arr, op="sum"):
         """In-place sum / max over the ranks of a float32 or float64 numpy array (pmf_comm_allreduce)."""
         if arr.dtype not in (np.float32, np.float64) or not arr.flags.c_contiguous:
             raise PMFError("comm_allreduce needs a contiguous float32 / float64 array")
-        self._chk(self.lib.pmf_comm_allreduce(self._h, arr.ctypes.data_as(C.c_void_p), C.c_int64(arr.size),
+        self._chk(self.lib.pmf_comm_allreduce(self._h, arr.ctypes.data_as(C.c_void_p), arr.size,
                                               1 if arr.dtype == np.float64 else 0, {"sum": 0, "max": 1}[op]))
         return arr
 
@@ -943,9 +836,9 @@ class Context:
         """pmf_debug_plain_table: int32 [row panels of 256 rows][column tiles + 1], the running counts of not-all-finite
         tiles that the exact kernel chooses its plain tile loop from."""
         n_rp, n_ct = C.c_int64(0), C.c_int64(0)
-        self._chk(self.lib.pmf_debug_plain_table(self._h, None, C.c_int64(0), C.byref(n_rp), C.byref(n_ct)))
+        self._chk(self.lib.pmf_debug_plain_table(self._h, None, 0, C.byref(n_rp), C.byref(n_ct)))
         out = np.zeros((n_rp.value, n_ct.value + 1), np.int32)
-        self._chk(self.lib.pmf_debug_plain_table(self._h, out.ctypes.data_as(C.c_void_p), C.c_int64(out.size), None, None))
+        self._chk(self.lib.pmf_debug_plain_table(self._h, _i32p(out), out.size, None, None))
         return out
 
     def last_kernel(self):
@@ -958,7 +851,7 @@ class Context:
         """pmf_debug_pass_extents: {buffer: dict(need=bytes, capacity=bytes)} of the data pass epoch_begin would run with
         these flags, prepared but not launched.  capacity_override ({buffer: bytes}, tests of the refusal) replaces recorded
         capacities and makes the call end with the pass's own check: PMFError naming the buffer if it would be refused."""
-        n_max = 16
+        n_max = PASS_EXTENTS_MAX
         names, n = (C.c_char_p * n_max)(), C.c_int(0)
         need, cap = (C.c_int64 * n_max)(), (C.c_int64 * n_max)()
         ov = None
@@ -989,4 +882,4 @@ class Context:
         return ms.value, n.value
 
     def synth_data(self, seed=20260104, noise=0.1, frac_nan=0.0):
-        self._chk(self.lib.pmf_synth_data(self._h, C.c_uint64(seed), C.c_float(noise), C.c_float(frac_nan)))
+        self._chk(self.lib.pmf_synth_data(self._h, seed, noise, frac_nan))

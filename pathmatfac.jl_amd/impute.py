@@ -10,6 +10,21 @@ def row_blocks(n_rows, N, capacity):
     return [(r0, min(step, n_rows - r0)) for r0 in range(0, n_rows, step)]
 
 
+def row_range(name, rows, M):
+    """`rows` of `name` (None: all M; a contiguous range; or a (start, stop) pair; 0-based, stop exclusive) -> (lo, hi)."""
+    if rows is None:
+        lo, hi = 0, M
+    elif isinstance(rows, range):
+        if rows.step != 1:
+            raise ValueError(f"{name}: rows must be a contiguous range")
+        lo, hi = rows.start, rows.stop
+    else:
+        lo, hi = int(rows[0]), int(rows[1])
+    if lo < 0 or hi > M or lo >= hi:
+        raise ValueError(f"{name}: rows {lo}:{hi} are empty or outside 0:{M}")
+    return lo, hi
+
+
 def _context(model, device):
     ctx = model.device_context(device)
     MF.marshal(model.matfac, ctx, with_xreg=False, with_yreg=False)
@@ -25,17 +40,8 @@ def impute(model, include_batch_effects=False, link=False, keep_observed=False, 
     len(rows) x N float32.  The device computes blocks of capacity // N rows, so a caller bounds host memory with `rows`.
     On a row-sharded model this is per rank: the rows are the local ones and nothing is exchanged."""
     ctx = _context(model, device)
-    M, N = ctx.M, ctx.N
-    if rows is None:
-        lo, hi = 0, M
-    elif isinstance(rows, range):
-        if rows.step != 1:
-            raise ValueError("impute: rows must be a contiguous range")
-        lo, hi = rows.start, rows.stop
-    else:
-        lo, hi = int(rows[0]), int(rows[1])
-    if lo < 0 or hi > M or lo >= hi:
-        raise ValueError(f"impute: rows {lo}:{hi} are empty or outside 0:{M}")
+    N = ctx.N
+    lo, hi = row_range("impute", rows, ctx.M)
     flags = ctx.impute_flags(include_batch_effects, link, keep_observed)
     out = np.empty((hi - lo, N), np.float32, order="F")
     for r0, nr in row_blocks(hi - lo, N, capacity):

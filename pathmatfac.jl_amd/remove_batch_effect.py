@@ -1,7 +1,7 @@
 """remove_batch_effect (src/remove_batch_effect.jl): the data with the fitted batch effects taken out, on the device."""
 import numpy as np
 
-from .impute import _context, row_blocks
+from .impute import _context, row_blocks, row_range
 
 
 def remove_batch_effect(model, Z=None, link=False, fill_missing=False, capacity=10 ** 8, rows=None, device=0):
@@ -15,17 +15,8 @@ def remove_batch_effect(model, Z=None, link=False, fill_missing=False, capacity=
     (impute(model)) instead of NaN.  rows, capacity: as in `impute`; the result is len(rows) x N float32.
     On a row-sharded model this is per rank: the rows are the local ones and nothing is exchanged."""
     ctx = _context(model, device)
-    M, N = ctx.M, ctx.N
-    if rows is None:
-        lo, hi = 0, M
-    elif isinstance(rows, range):
-        if rows.step != 1:
-            raise ValueError("remove_batch_effect: rows must be a contiguous range")
-        lo, hi = rows.start, rows.stop
-    else:
-        lo, hi = int(rows[0]), int(rows[1])
-    if lo < 0 or hi > M or lo >= hi:
-        raise ValueError(f"remove_batch_effect: rows {lo}:{hi} are empty or outside 0:{M}")
+    N = ctx.N
+    lo, hi = row_range("remove_batch_effect", rows, ctx.M)
     if Z is not None:
         Z = np.asarray(Z)
         if Z.shape != (hi - lo, N):

@@ -5,7 +5,7 @@ device (pmf_simulate_data*, include/pmf_hip.h); average_precision / Y_average_pr
 feature sets.  The study of analyses/scripts/julia/simulate_matfac.jl is simulate_params_, simulate_data_, fit_, score."""
 import numpy as np
 
-from .impute import _context, row_blocks
+from .impute import _context, row_blocks, row_range
 from .layers import BatchScale, BatchShift, ColScale, ColShift, FrozenLayer, Identity
 from .regularizers import ARDRegularizer, FeatureSetARDReg, GroupRegularizer, L2Regularizer
 from .util import unique
@@ -149,7 +149,7 @@ def simulate_data_(model, noise=0.1, seed=0, frac_missing=0.0, to="host", rows=N
                this context: a following fit_ runs on it.  model.data on the host is NOT updated and is stale until the
                next simulate_data_(to="host") or assignment."""
     ctx = _context(model, device)
-    M, N = ctx.M, ctx.N
+    N = ctx.N
     off = int(model.row_shard[0])
     if to == "device":
         if rows is not None:
@@ -160,16 +160,7 @@ def simulate_data_(model, noise=0.1, seed=0, frac_missing=0.0, to="host", rows=N
         return None
     if to != "host":
         raise ValueError(f"simulate_data_: to={to!r} (host | device)")
-    if rows is None:
-        lo, hi = 0, M
-    elif isinstance(rows, range):
-        if rows.step != 1:
-            raise ValueError("simulate_data_: rows must be a contiguous range")
-        lo, hi = rows.start, rows.stop
-    else:
-        lo, hi = int(rows[0]), int(rows[1])
-    if lo < 0 or hi > M or lo >= hi:
-        raise ValueError(f"simulate_data_: rows {lo}:{hi} are empty or outside 0:{M}")
+    lo, hi = row_range("simulate_data_", rows, ctx.M)
     data = model.data
     direct = isinstance(data, np.ndarray) and data.dtype == np.float32 and data.flags.f_contiguous and data.flags.writeable
     out = data if direct else np.empty((hi - lo, N), np.float32, order="F")

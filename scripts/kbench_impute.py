@@ -94,7 +94,7 @@ def main():
     ts = []
     for _ in range(rounds):
         if Z is not None:
-            ctx.lib.pmf_forward(ctx._h, Z.ctypes.data_as(__import__("ctypes").c_void_p))
+            ctx.lib.pmf_forward(ctx._h, Z.ctypes.data_as(__import__("ctypes").POINTER(__import__("ctypes").c_float)))
         t0 = time.perf_counter()
         ctx.impute_device(t.data_ptr(), flags)
         ts.append((time.perf_counter() - t0) * 1e3)

@@ -228,8 +228,8 @@ def test_ld_padding_is_left_alone(ctx, range_case):
             # a host input wider than the range: ldz > rows
             Zw = np.asfortranarray(np.vstack([D[s1 - 1:e1], np.full((7, p["N"]), SENTINEL, np.float32)]))
             o2 = np.zeros((n, p["N"]), np.float32, order="F")
-            rc = ctx.lib.pmf_remove_batch_effect(ctx._h, flags, C.c_int64(s1), C.c_int64(e1), C.c_void_p(Zw.ctypes.data),
-                                                 C.c_int64(n + 7), C.c_void_p(o2.ctypes.data), C.c_int64(n))
+            rc = ctx.lib.pmf_remove_batch_effect(ctx._h, flags, C.c_int64(s1), C.c_int64(e1), Zw.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 C.c_int64(n + 7), o2.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(n))
             assert rc == 0 and same_bits(o2, full[s1 - 1:e1])
 
 
@@ -308,9 +308,9 @@ def test_refusals_leave_the_context_usable(pkg):
     M, N = p["M"], p["N"]
     out = np.full((M, N), SENTINEL, np.float32, order="F")
     Z = np.asfortranarray(np.asarray(p["D"], np.float32))
-    op, zp = out.ctypes.data_as(C.c_void_p), Z.ctypes.data_as(C.c_void_p)
+    op, zp = out.ctypes.data_as(C.POINTER(C.c_float)), Z.ctypes.data_as(C.POINTER(C.c_float))
     i64 = lambda *v: np.array(v, np.int64)    # noqa: E731
-    ip = lambda a: a.ctypes.data_as(C.c_void_p)    # noqa: E731
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))    # noqa: E731
     c = pkg.Context(0)
     try:
         L, h = c.lib, c._h

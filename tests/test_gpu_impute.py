@@ -411,9 +411,9 @@ def test_refusals_leave_the_context_usable(pkg):
     p = case_problem(20, 70, 40, seed=811)
     M, N = p["M"], p["N"]
     out = np.full((M, N), SENTINEL, np.float32, order="F")
-    op = out.ctypes.data_as(C.c_void_p)
+    op = out.ctypes.data_as(C.POINTER(C.c_float))
     i64 = lambda *v: np.array(v, np.int64)    # noqa: E731
-    ip = lambda a: a.ctypes.data_as(C.c_void_p)    # noqa: E731
+    ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))    # noqa: E731
     c = pkg.Context(0)
     try:
         L, h = c.lib, c._h

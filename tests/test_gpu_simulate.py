@@ -256,7 +256,7 @@ def test_refusals_leave_the_context_usable(pkg):
     p = sr.sim_case(20, 70, 40, seed=811)
     M, N = p["M"], p["N"]
     out = np.full((M, N), SENTINEL, np.float32, order="F")
-    op = out.ctypes.data_as(C.c_void_p)
+    op = out.ctypes.data_as(C.POINTER(C.c_float))
     c = pkg.Context(0)
     try:
         L, h = c.lib, c._h

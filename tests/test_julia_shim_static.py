@@ -12,11 +12,11 @@ from pathlib import Path
 
 import pytest
 
+from abi_header import HEADER, _c_class, header  # noqa: F401  (the other shim checks read these through this module)
+
 ROOT = Path(__file__).resolve().parent.parent
 SHIM = ROOT / "pathmatfac.jl_amd" / "julia" / "PathMatFacHIP.jl"
-HEADER = ROOT / "include" / "pmf_hip.h"
 
-C_CLASS = {"int": "i32", "int32_t": "i32", "int64_t": "i64", "float": "f32", "double": "f64", "uint64_t": "u64"}
 JL_CLASS = {"Cint": "i32", "Int64": "i64", "Cfloat": "f32", "Cdouble": "f64", "UInt64": "u64", "Cstring": "ptr"}
 STRUCTS = {"FitOpts": "pmf_fit_opts", "FitResult": "pmf_fit_result", "LbfgsOpts": "pmf_lbfgs_opts",
            "LbfgsResult": "pmf_lbfgs_result", "EmOpts": "pmf_em_opts", "EmResult": "pmf_em_result"}
@@ -26,36 +26,6 @@ BOUND = ["pmf_stats", "pmf_get_precision", "pmf_comm_info", "pmf_reset_optimizer
          "pmf_stage_init_logsigma", "pmf_stage_reweight_col_losses", "pmf_stage_minimal_group_weights",
          "pmf_stage_theta_delta_em", "pmf_add_xreg_l2", "pmf_add_yreg_l2", "pmf_add_xreg_group", "pmf_add_yreg_group",
          "pmf_fit", "pmf_fit_lbfgs", "pmf_impute", "pmf_fsard_update_A"]
-
-
-# ---- the header ------------------------------------------------------------------------------------------------------
-def _c_class(decl):
-    """'const float *w' -> 'ptr'; 'int64_t M' -> 'i64'; a function-pointer typedef counts as a pointer."""
-    if "*" in decl or "pmf_host_allreduce_fn" in decl:
-        return "ptr"
-    words = [w for w in decl.replace("const", " ").split()]
-    assert len(words) == 2 and words[0] in C_CLASS, decl
-    return C_CLASS[words[0]]
-
-
-def header():
-    txt = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    protos = {}
-    for ret, name, params in re.findall(r"\b(int|const char \*)\s*(pmf_\w+)\s*\(([^()]*)\)\s*;", txt):
-        params = params.strip()
-        protos[name] = ("ptr" if "*" in ret else "i32",
-                        [] if params in ("", "void") else [_c_class(" ".join(p.split())) for p in params.split(",")])
-    structs = {}
-    for body, name in re.findall(r"typedef struct \w+\s*\{(.*?)\}\s*(\w+)\s*;", txt, flags=re.S):
-        if name not in STRUCTS.values():
-            continue
-        fields = []
-        for decl in body.split(";"):
-            decl = " ".join(decl.split())
-            if decl:
-                fields.append((re.findall(r"\w+", decl)[-1], _c_class(decl)))
-        structs[name] = fields
-    return protos, structs
 
 
 # ---- the shim --------------------------------------------------------------------------------------------------------
