@@ -12,7 +12,7 @@ from .model import PathMatFacModel, make_model  # noqa: F401
 from .fit import (mf_fit_, mf_fit_adapt_lr_, init_theta_, init_factors_, construct_optimizer, init_mu_, init_logsigma_,  # noqa: F401
                   reweight_col_losses_, construct_minimal_regularizer, init_batch_effects_, theta_delta_em, whiten_,
                   rotate_by_svd_, reorder_by_importance_, reweight_eb_, basic_fit_, fit_ard_, fit_non_ard_,
-                  fit_feature_set_ard_, fit_)
+                  fit_feature_set_ard_, fit_, init_ordinal_thresholds_)
 from . import fit_lbfgs as _fit_lbfgs  # noqa: F401
 from .fit_lbfgs import fit_lbfgs_  # noqa: F401
 from . import featureset_ard  # noqa: F401

@@ -189,10 +189,21 @@ SIGNATURES = {
 # every symbol include/pmf_hip.h declares (checked by tests/test_abi.py against the header and the .so)
 EXPORTS = list(SIGNATURES)
 
+# include/pmf_hip_thresholds.h, the extension header of the trainable squared-hinge thresholds, in its order
+# (tests/test_threshold_cases.py compares this table with that header)
+THRESHOLD_SIGNATURES = {
+    "pmf_set_threshold_training": _int(ctx, i),
+    "pmf_get_threshold_groups": _int(ctx, pi, pi64, pi64, i),
+    "pmf_threshold_grad": _int(ctx, pf, pf),
+    "pmf_get_threshold_state": _int(ctx, pf, pf, pf),
+    "pmf_class_counts": _int(ctx, i, pi64, pi64, pi64),
+    "pmf_debug_threshold_pass": _int(ctx, pi, pi, pi, pi64),
+}
+
 
 def bind(lib):
-    """Installs SIGNATURES on a CDLL.  AttributeError if a declared symbol is not exported."""
-    for name, (restype, argtypes) in SIGNATURES.items():
+    """Installs SIGNATURES and THRESHOLD_SIGNATURES on a CDLL.  AttributeError if a declared symbol is not exported."""
+    for name, (restype, argtypes) in {**SIGNATURES, **THRESHOLD_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype, f.argtypes = restype, argtypes
     return lib

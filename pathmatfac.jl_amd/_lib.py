@@ -406,16 +406,62 @@ class Context:
         o.abs_tol, o.rel_tol, o.capacity = float(abs_tol), float(rel_tol), int(capacity)
         return o
 
-    def fit(self, **kw):
+    def fit(self, update_noise_models=False, **kw):
+        """pmf_fit.  update_noise_models: the squared-hinge thresholds train in this call (set_threshold_training for its
+        duration; include/pmf_hip_thresholds.h); False leaves the context's switch as it is."""
         o = self.make_opts(**kw)
         cap = max(o.max_epochs - o.epoch + 1, 1)
         trace = np.zeros(cap, np.float64)
         r = FitResult()
         r.trace_cap = cap
         r.loss_trace = _dp(trace)
-        self._chk(self.lib.pmf_fit(self._h, C.byref(o), C.byref(r)))
+        if update_noise_models:
+            self.set_threshold_training(True)
+        try:
+            self._chk(self.lib.pmf_fit(self._h, C.byref(o), C.byref(r)))
+        finally:
+            if update_noise_models:
+                self.set_threshold_training(False)
         return {"term_code": TERM[r.term_code], "epochs": r.epochs, "loss": trace[:r.n_trace].copy(),
                 "final_loss": r.final_loss, "seconds": r.seconds}
+
+    # ---- trainable squared-hinge thresholds (include/pmf_hip_thresholds.h)
+    def set_threshold_training(self, on):
+        self._chk(self.lib.pmf_set_threshold_training(self._h, int(bool(on))))
+
+    def get_threshold_groups(self):
+        """The 1-based inclusive column ranges whose thresholds train as one triple (the all-kind-3 noise ranges)."""
+        n = C.c_int(0)
+        self._chk(self.lib.pmf_get_threshold_groups(self._h, C.byref(n), None, None, 0))
+        s, e = np.zeros(max(n.value, 1), np.int64), np.zeros(max(n.value, 1), np.int64)
+        self._chk(self.lib.pmf_get_threshold_groups(self._h, C.byref(n), _i64p(s), _i64p(e), n.value))
+        return [(int(a), int(b)) for a, b in zip(s[:n.value], e[:n.value])]
+
+    def threshold_grad(self, per_column=True):
+        """pmf_threshold_grad: (groups x 3, N x 3 or None) -- one threshold pass at the current parameters."""
+        g = np.zeros((len(self.get_threshold_groups()), 3), np.float32)
+        gc = np.zeros((self.N, 3), np.float32) if per_column else None
+        self._chk(self.lib.pmf_threshold_grad(self._h, _fp(g), _fp(gc)))
+        return g, gc
+
+    def get_threshold_state(self):
+        """pmf_get_threshold_state: dict(thr, acc, mom), each groups x 3."""
+        out = {k: np.zeros((len(self.get_threshold_groups()), 3), np.float32) for k in ("thr", "acc", "mom")}
+        self._chk(self.lib.pmf_get_threshold_state(self._h, _fp(out["thr"]), _fp(out["acc"]), _fp(out["mom"])))
+        return out
+
+    def class_counts(self, ranges):
+        """pmf_class_counts: (ranges x 4) int64 counts of the observed entries of class 0..3 in the local rows."""
+        s, e = _ranges(ranges)
+        n = np.zeros((len(s), 4), np.int64)
+        self._chk(self.lib.pmf_class_counts(self._h, len(s), _i64p(s), _i64p(e), _i64p(n)))
+        return n
+
+    def debug_threshold_pass(self):
+        """pmf_debug_threshold_pass: dict(n_tiles, n_units, grid, passes) of the last threshold pass."""
+        a, b, c, p = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int64(0)
+        self._chk(self.lib.pmf_debug_threshold_pass(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(p)))
+        return dict(n_tiles=a.value, n_units=b.value, grid=c.value, passes=p.value)
 
     def loss(self):
         """pmf_loss: dict(total, data, xreg, yreg) at the current parameters (full_loss, src/fit_lbfgs.jl:3-8)."""

@@ -87,7 +87,7 @@ int comm_release(pmf_ctx *c) {
   if (m.nccl && g_rccl.CommDestroy) (void)g_rccl.CommDestroy((ncclComm_t)m.nccl);
   for (auto e : m.ev_ready) (void)hipEventDestroy(e);
   for (auto e : m.ev_done) (void)hipEventDestroy(e);
-  for (auto e : {m.ev_loss_ready, m.ev_loss_done, m.ev_layer_ready, m.ev_layer_done})
+  for (auto e : {m.ev_loss_ready, m.ev_loss_done, m.ev_layer_ready, m.ev_layer_done, m.ev_thr_ready, m.ev_thr_done})
     if (e) (void)hipEventDestroy(e);
   if (m.stream) (void)hipStreamDestroy(m.stream);
   const int64_t n_allreduce = m.n_allreduce;   // (a diagnostic of the context, not of the communicator)
@@ -101,7 +101,7 @@ static int comm_common_init(pmf_ctx *c, int rank, int nranks) {
   Comm &m = c->comm;
   m.rank = rank; m.nranks = nranks;
   HIPCHK(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
-  hipEvent_t *evs[4] = {&m.ev_loss_ready, &m.ev_loss_done, &m.ev_layer_ready, &m.ev_layer_done};
+  hipEvent_t *evs[6] = {&m.ev_loss_ready, &m.ev_loss_done, &m.ev_layer_ready, &m.ev_layer_done, &m.ev_thr_ready, &m.ev_thr_done};
   for (auto pe : evs) HIPCHK(hipEventCreateWithFlags(pe, hipEventDisableTiming));
   return 0;
 }
@@ -253,7 +253,7 @@ static int compute_after_comm(pmf_ctx *c, hipEvent_t ev) {
 //     gradients when they train).
 // A data pass only writes gradient buffers, never parameters: when epoch e terminates the fit, the speculative pass of
 // e+1 is simply dropped and the parameters are exactly those after epoch e's steps (same results as the plain loop).
-static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res);
+static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool th_on);
 
 // Error exits.  Inside the pipelined loop a speculative data pass and collectives may already be enqueued when a call
 // fails.  Every error exit therefore drains both streams before returning (the context's buffers are not written behind
@@ -269,7 +269,18 @@ extern "C" int pmf_fit(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
   // regularizers and refuses alike, before any collective of this fit is issued (the communicator stays usable).
   if (o->update_X && c->net[0] && comm_active(c) && c->comm.nranks > 1)
     return pmf_fail("a NetworkRegularizer on X is not supported with %d ranks: X is sharded by rows and the network couples rows across ranks (drop the term or fit on one rank)", c->comm.nranks);
-  return comm_error_exit(c, fit_loop(c, o, res));
+  // trainable squared-hinge thresholds (include/pmf_hip_thresholds.h): a group with different triples is refused here, before
+  // anything is launched; every rank holds the same noise model and refuses alike
+  bool th_on = false;
+  PMFCHK(thresh_fit_check(c, &th_on));
+  const int rc = comm_error_exit(c, fit_loop(c, o, res, th_on));
+  if (th_on) {   // (both streams are idle) the host copy follows the device, after a failed fit too
+    const std::string msg = rc < 0 ? pmf_last_error() : "";
+    const int rt = thresh_fit_end(c);
+    if (rc < 0) pmf_fail("%s", msg.c_str());
+    else if (rt < 0) return rt;
+  }
+  return rc;
 }
 int comm_error_exit(pmf_ctx *c, int rc) {
   if (rc < 0) {
@@ -283,7 +294,7 @@ int comm_error_exit(pmf_ctx *c, int rc) {
   return rc;
 }
 
-static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
+static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool th_on) {
   const auto t0 = std::chrono::steady_clock::now();
   const bool ux = o->update_X != 0, uy = o->update_Y != 0, ul = o->update_col_layers != 0;
   const bool fused = ux || uy || !ul;
@@ -303,6 +314,7 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
   // (the first epoch is opened before the geometry is chosen: prepare() decides whether the dense batch table exists,
   //  which decides the kernel variant and with it the row-panel height)
   if (o->epoch <= o->max_epochs) PMFCHK(epoch_open(c, o));
+  if (th_on && o->epoch <= o->max_epochs) PMFCHK(thresh_fit_begin(c));
   FusedGeom g;
   if (fused) g = fused_geometry(c, ux, uy, /*allow_chunks=*/!ul);
   const int S = fused ? g.S : 1;
@@ -341,6 +353,16 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
         for (int w = 2; w < 6; ++w) PMFCHK(comm_allreduce(c, c->P[w].g, c->P[w].n, false));
         if (m.nccl) PMFCHK(rccl_chk(g_rccl.GroupEnd(), "ncclGroupEnd", (ncclComm_t)m.nccl));
         PMFCHK(comm_mark(c, m.ev_layer_done));
+      }
+    }
+    // the threshold pass, at the parameters the data pass saw; its float64 group sums are summed over the ranks before
+    // they are rounded (one small collective per epoch, of its own)
+    if (th_on && s == S - 1) {
+      PMFCHK(thresh_pass(c));
+      if (cm) {
+        PMFCHK(comm_after_compute(c, m.ev_thr_ready));
+        PMFCHK(comm_allreduce(c, c->th.G, 3 * (int64_t)c->th.g_s1.size(), true));
+        PMFCHK(comm_mark(c, m.ev_thr_done));
       }
     }
     return 0;
@@ -382,6 +404,11 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
         const int64_t col0 = fused ? g.ct0[s] * 32 : 0;
         const int64_t col1 = fused ? std::min<int64_t>(c->N, (g.ct0[s] + g.nct[s]) * 32) : c->N;
         PMFCHK(step_param_range(c, 1, col0 * c->Kp, (col1 - col0) * c->Kp, true, true, 1, &rc.c[1], y_blocks, s == S - 1));
+      }
+      // the thresholds step from this epoch's pass before the first chunk of the next epoch's data pass reads their images
+      if (th_on && s == 0) {
+        if (cm) PMFCHK(compute_after_comm(c, m.ev_thr_done));
+        PMFCHK(thresh_step(c));
       }
       if (s == S - 1) {
         if (ul) {

@@ -148,6 +148,7 @@ struct Comm {
   int64_t m_mean = 0;              // rows per rank averaged over the ranks (pmf_fit): the rank-invariant size behind the chunk count
   std::vector<hipEvent_t> ev_ready, ev_done;   // per chunk: gY slice complete / its all-reduce complete
   hipEvent_t ev_loss_ready = nullptr, ev_loss_done = nullptr, ev_layer_ready = nullptr, ev_layer_done = nullptr;
+  hipEvent_t ev_thr_ready = nullptr, ev_thr_done = nullptr;   // the threshold group sums of a training fit (pmf_thresh.hip)
   int64_t n_allreduce = 0;         // collectives issued (diagnostics / tests)
 };
 
@@ -172,6 +173,24 @@ struct NetReg {
   DevBuf<double> uloss;            // [K] t'u + 0.5 u'BB u of the last solve
   int rb = 1;                      // row blocks per factor of the gradient kernel (= loss partials per factor)
   int64_t vmax = 0;                // largest v_k
+};
+
+// Trainable thresholds of the squared-hinge noise models (pmf_thresh.hip; include/pmf_hip_thresholds.h).  A group is a
+// noise range whose columns are all of kind 3; the triples and their optimizer state live per group, the per-column images
+// (thr, htab) are rebuilt from them on the device after every step.
+struct ThreshState {
+  bool train = false;                   // pmf_set_threshold_training
+  std::vector<int64_t> g_s1, g_e1;      // the groups (1-based inclusive) the state below belongs to
+  DevBuf<float> t, acc, mom;            // [3 groups] thresholds, optimizer state
+  float bp1 = 0.f, bp2 = 0.f;           // Adam's running beta powers
+  bool state_init = false;              // (init_opt_state clears it with the other parameters' state)
+  std::vector<int32_t> h_tiles;         // the column tiles that hold a kind-3 column, ascending
+  DevBuf<int32_t> tiles, col_group;     // device copy; [N] group of every column (-1: none)
+  DevBuf<int64_t> g_c0, g_c1;           // [groups] 0-based first column, one past the last
+  DevBuf<float> slots;                  // [R * waves][tiles][PMF_TSLOT] private partial sums of the pass
+  DevBuf<double> gcol, G;               // [3 N] per column, [3 groups] per group: float64 sums of the last pass
+  int n_tiles = 0, n_units = 0, grid = 0;   // geometry of the last pass (pmf_debug_threshold_pass)
+  int64_t passes = 0;
 };
 
 struct pmf_ctx {
@@ -275,6 +294,7 @@ struct pmf_ctx {
   PmfDynLds dyn_lds;
   double pp_seconds[3] = {0.0, 0.0, 0.0};   // phases of the last post-processing call (pmf_postprocess.hip, PpClock)
   struct LbfgsState *lbfgs = nullptr;   // vectors and scalars of pmf_fit_lbfgs (pmf_lbfgs.hip), allocated on its first call
+  ThreshState th;                       // trainable squared-hinge thresholds (pmf_thresh.hip)
 };
 
 #define REG_SLOTS 1024
@@ -443,6 +463,14 @@ void netreg_free(pmf_ctx *c, int which);   // drops the network term of X (0) / 
 // evaluates the network term from the current parameter: u_k, its gradient buffer and its loss partials (appended to
 // slab `which`, *reg_count moved on).  No-op without a term.
 int netreg_eval(pmf_ctx *c, int which, int *reg_count);
+// ---- defined in pmf_thresh.hip: the thresholds inside pmf_fit (include/pmf_hip_thresholds.h)
+// what a training fit checks before anything is launched: *active = training is on and the noise model has a group; fails
+// when a group's columns do not all hold the same triple.  Brings the groups' device state up to date with the noise model.
+int thresh_fit_check(pmf_ctx *c, bool *active);
+int thresh_fit_begin(pmf_ctx *c);   // after the first epoch_open: the pass's own refusals, the optimizer state
+int thresh_pass(pmf_ctx *c);        // one threshold pass at the current parameters: th.gcol, th.G (float64, on the stream)
+int thresh_step(pmf_ctx *c);        // optimizer step from th.G, order clamp, the per-column images
+int thresh_fit_end(pmf_ctx *c);     // h_thr <- the groups' triples (the stream is idle)
 // ---- defined in pmf_comm_fit.hip
 int comm_release(pmf_ctx *c);
 bool comm_active(const pmf_ctx *c);

@@ -1144,6 +1144,7 @@ static int init_opt_state(pmf_ctx *c) {
     b.bp2 = c->b2;
   }
   c->state_init = true;
+  c->th.state_init = false;   // the thresholds' state resets with every other parameter's (thresh_fit_begin)
   return 0;
 }
 

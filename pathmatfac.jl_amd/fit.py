@@ -32,7 +32,7 @@ def mf_fit_(model, scale_column_losses=False, update_X=False, update_Y=False, up
     """mf_fit! (src/fit.jl:9-38): the drop-in boundary.  MF.fit! is replaced by the HIP library."""
     ctx = model.device_context(device)
     return MF.fit_(model.matfac, ctx, update_X=update_X, update_Y=update_Y, update_col_layers=update_col_layers,
-                   keep_history=keep_history, **kwargs)
+                   update_noise_models=update_noise_models, keep_history=keep_history, **kwargs)
 
 
 def construct_optimizer(model, lr):
@@ -666,6 +666,45 @@ def reweight_eb_(reg, P, mixture_p=1.0, model=None, postprocess="host"):
     # pure functions (x -> 0) and FeatureSetARDReg have no adjustable weights (regularizers.jl:941-943)
 
 
+# ---- init_ordinal_thresholds! (src/fit.jl:190-246) ------------------------------------------------------
+def inv_logistic(x):
+    """The reference's own (src/util.jl:8-10): log(0.5 + 0.99 (x / (1 - x) - 0.5))."""
+    return np.log(0.5 + 0.99 * (x / (1.0 - x) - 0.5))
+
+
+def ordinal_thresholds_from_counts(counts, thresholds):
+    """The triple of one squared-hinge range from the counts n_c of its observed entries of class c = 0..3 (DESIGN.md section 2,
+    Deviation 5).  The finite thresholds separate the allowed classes (class c lies between t_{c-1} and t_c; a class
+    between two infinite thresholds of the same sign cannot occur and its count is ignored); p_c = (n_c + 1) / sum (n_c + 1)
+    over the allowed classes and every finite t_m = inv_logistic(sum of p_c over the allowed c <= m).  float64, rounded once
+    to float32."""
+    t = np.asarray(thresholds, np.float64)
+    ext = np.concatenate([[-np.inf], t, [np.inf]])
+    allowed = np.array([not (np.isinf(ext[c]) and np.isinf(ext[c + 1]) and ext[c] == ext[c + 1]) for c in range(4)])
+    n1 = np.where(allowed, np.asarray(counts, np.float64) + 1.0, 0.0)
+    p = n1 / n1.sum()
+    out = t.copy()
+    for m in range(3):
+        if np.isfinite(t[m]):
+            out[m] = inv_logistic(p[:m + 1].sum())
+    return tuple(float(np.float32(x)) for x in out)
+
+
+def init_ordinal_thresholds_(model, device=0):
+    """init_ordinal_thresholds! + rec_set_thresholds: the thresholds of every ordinal_sq_hinge3 range from the class counts
+    of its observed entries (counted on the device, summed exactly over the ranks of a row-sharded model)."""
+    nm = model.matfac.noise_model
+    idx = [r for r, d in enumerate(nm.noises) if d == "ordinal_sq_hinge3"]
+    if not idx:
+        return
+    ctx = model.device_context(device)
+    counts = ctx.class_counts([(nm.col_ranges[r].start, nm.col_ranges[r].stop) for r in idx]).astype(np.float64)
+    counts = np.ascontiguousarray(counts)          # (below 2^53: the float64 sum over the ranks is exact)
+    model.allreduce(counts)
+    for k, r in enumerate(idx):
+        nm.set_thresholds_(r, ordinal_thresholds_from_counts(counts[k], nm.thresholds[r]))
+
+
 # ---- stage drivers (src/fit.jl:564-892) -----------------------------------------------------------------
 def basic_fit_(model, fit_batch=False, batch_method="EM", fit_mu=False, fit_logsigma=False, reweight_losses=False,
                init_factors=False, init_factors_method="adagrad", fit_factors=False, init_ordinal=False,
@@ -677,7 +716,7 @@ def basic_fit_(model, fit_batch=False, batch_method="EM", fit_mu=False, fit_logs
     n_prefix = print_prefix + "    "
     ct = model.matfac.col_transform
     if init_ordinal:
-        raise NotImplementedError("ordinal noise models are out of scope")
+        init_ordinal_thresholds_(model)
     if fit_batch:
         assert isinstance(ct.unwrapped(2), BatchScale) and isinstance(ct.unwrapped(4), BatchShift), \
             "Model must have batch parameters whenever `fit_batch` is true"

@@ -20,7 +20,9 @@ HINGE_THRESHOLDS = {"bernoulli_sq_hinge": (0.0, np.inf, np.inf), "ordinal_sq_hin
 class CompositeNoise:
     """MatFac's CompositeNoise{noises, col_ranges} as used at src/fit.jl:227, plus the per-column weights set by
     MF.set_weight! (src/fit.jl:157, 180).  `thresholds` has one entry per range: None, or the (t0, t1, t2) of a
-    squared-hinge range (constants of the fit, set_thresholds_)."""
+    squared-hinge range (set_thresholds_): constants of the fit unless `train_thresholds` is on (train_thresholds_), in
+    which case a fit called with update_noise_models=True trains them, one triple per range (DESIGN.md section 2,
+    Deviation 5), and writes the trained triples back here."""
 
     def __init__(self, feature_distributions):
         dists = list(feature_distributions)
@@ -33,7 +35,13 @@ class CompositeNoise:
                 raise NotImplementedError(f"noise model {d!r} is not implemented by the HIP path "
                                           f"(supported: {SUPPORTED_LOSSES}); see DESIGN.md 'out of scope'")
         self.thresholds = [HINGE_THRESHOLDS.get(d) for d in self.noises]
+        self.train_thresholds = False
         self.weights = np.ones(len(dists), dtype=np.float32)
+
+    def train_thresholds_(self, on=True):
+        """Lets the fits that are called with update_noise_models=True (mf_fit!'s default) train the thresholds."""
+        self.train_thresholds = bool(on)
+        return self
 
     def set_weight_(self, w):
         self.weights = np.asarray(w, dtype=np.float32).copy()
@@ -134,8 +142,13 @@ def marshal(mf, ctx, with_xreg=True, with_yreg=True):
     ctx.set_layer_regs(**kw)
 
 
-def unmarshal(mf, ctx, update_X, update_Y, update_col_layers):
+def unmarshal(mf, ctx, update_X, update_Y, update_col_layers, update_thresholds=False):
     """Device -> host for the parameter groups that were trained."""
+    if update_thresholds:
+        nm, t = mf.noise_model, ctx.get_noise_thresholds()
+        for r, cr in enumerate(nm.col_ranges):
+            if nm.thresholds[r] is not None:
+                nm.thresholds[r] = tuple(float(x) for x in t[cr.start - 1])
     if update_X or update_Y:
         X, Y = ctx.get_factors()
         if update_X:
@@ -161,8 +174,11 @@ def unmarshal(mf, ctx, update_X, update_Y, update_col_layers):
 
 def fit_(mf, ctx, opt=None, lr=0.01, update_X=False, update_Y=False, update_col_layers=False, max_epochs=1000,
          epoch=1, abs_tol=1e-9, rel_tol=1e-6, tol_max_iters=3, verbosity=0, print_iter=10, capacity=10 ** 8,
-         keep_history=True, dist=None, group=None, **ignored):
-    """MF.fit!(matfac, data; ...) -> history dict with "term_code", "epochs", "loss" (src/fit.jl:24-38, 61-69)."""
+         keep_history=True, dist=None, group=None, update_noise_models=False, **ignored):
+    """MF.fit!(matfac, data; ...) -> history dict with "term_code", "epochs", "loss" (src/fit.jl:24-38, 61-69).
+    update_noise_models is honoured only when the noise model says so (CompositeNoise.train_thresholds_): the squared-hinge
+    thresholds then train inside pmf_fit and the trained triples are written into noise_model.thresholds.  The row-sharded
+    loop of parallel.py runs on the step-level API, which keeps thresholds constant."""
     opt = opt if opt is not None else AdaGrad(lr)
     marshal(mf, ctx, with_xreg=update_X, with_yreg=update_Y)
     if opt._bound_ctx != id(ctx):          # a new optimizer object: fresh accumulators (src/fit.jl:55)
@@ -179,9 +195,11 @@ def fit_(mf, ctx, opt=None, lr=0.01, update_X=False, update_Y=False, update_col_
     if dist is not None and dist.is_initialized() and dist.get_world_size(group) > 1:
         from . import parallel
         h = parallel.fit_distributed(ctx, dist=dist, group=group, **kw)
+        train_thr = False
     else:
-        h = ctx.fit(capacity=capacity, **kw)
-    unmarshal(mf, ctx, update_X, update_Y, update_col_layers)
+        train_thr = bool(update_noise_models and mf.noise_model.train_thresholds)
+        h = ctx.fit(capacity=capacity, update_noise_models=train_thr, **kw)
+    unmarshal(mf, ctx, update_X, update_Y, update_col_layers, update_thresholds=train_thr)
     for reg, which, on in ((mf.X_reg, "X", update_X), (mf.Y_reg, "Y", update_Y)):
         if on and hasattr(reg, "read_back"):      # the network term's virtual nodes (NetworkRegularizer.x_virtual)
             reg.read_back(ctx, which)

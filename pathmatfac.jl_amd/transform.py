@@ -38,6 +38,7 @@ def transform(model, D, use_gpu=True, feature_ids=None, sample_ids=None, verbosi
     mf.col_transform.set_layer_(4, Identity())              # :65
     mf.X = np.zeros((K, M_new), dtype=np.float32, order="F")  # :68-69
     mf.X_reg = ZeroReg()                                    # :70
+    mf.noise_model.train_thresholds_(False)                 # embedding new samples must not move the model's thresholds
     new_model = PathMatFacModel(mf, new_data, sample_ids, None, list(model.feature_ids), list(model.feature_views),
                                 np.array(model.data_idx))
     freeze_layer_(mf.col_transform, [1, 2, 3, 4])           # :84
