@@ -57,7 +57,9 @@ int pmf_get_threshold_state(pmf_ctx *ctx, float *thr, float *acc, float *mom);
 int pmf_class_counts(pmf_ctx *ctx, int n_ranges, const int64_t *starts1, const int64_t *stops1, int64_t *counts);
 
 /* geometry of the last threshold pass: column tiles that hold a kind-3 column, units (tiles x row ranges), workgroups
- * launched (PMF_THRESH_GRID=n caps them), and the passes run on this context so far.  Any pointer may be NULL. */
+ * launched (PMF_THRESH_GRID=n caps them), and the passes run on this context so far.  PMF_THRESH_RANGES=n caps the row
+ * ranges R (units = tiles x R), so that a unit of a small problem sweeps several row panels.  Both are test hooks, read at
+ * every pass.  Any pointer may be NULL. */
 int pmf_debug_threshold_pass(pmf_ctx *ctx, int *n_tiles, int *n_units, int *grid, int64_t *passes);
 
 #ifdef __cplusplus

@@ -212,8 +212,8 @@ class Context:
         K = X.shape[0]
         if X.shape != (K, self.M) or Y.shape != (K, self.N):
             raise PMFError(f"factor shapes {X.shape}, {Y.shape} do not match data {self.M} x {self.N}")
-        self.K = K
         self._chk(self.lib.pmf_set_factors(self._h, _fp(X), _fp(Y), K))
+        self.K = K   # (after the call: a refused K leaves the context, and this mirror of it, at the factors it had)
 
     def set_X(self, X):
         X = _f32(X)

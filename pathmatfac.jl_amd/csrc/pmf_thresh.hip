@@ -90,7 +90,9 @@ int thresh_pass(pmf_ctx *c) {
   while ((1 << nbs_shift) < nbs) ++nbs_shift;
   const int64_t n_tiles = (int64_t)t.h_tiles.size(), n_rp = (c->M + 32 * nw - 1) / (32 * nw);
   // row ranges: enough units to fill the device a few times over while the tiles alone do not
-  const int64_t R = std::max<int64_t>(1, std::min<int64_t>(n_rp, (4ll * c->n_cu + n_tiles - 1) / n_tiles));
+  int64_t R = std::max<int64_t>(1, std::min<int64_t>(n_rp, (4ll * c->n_cu + n_tiles - 1) / n_tiles));
+  const char *re = getenv("PMF_THRESH_RANGES");   // test hook, read at every pass: caps the row ranges so that small shapes sweep several panels per unit
+  if (re && atoi(re) > 0) R = std::min<int64_t>(R, atoi(re));
   int grid = (int)std::min<int64_t>(n_tiles * R, c->n_cu);
   const char *ge = getenv("PMF_THRESH_GRID");   // test hook, read at every pass: caps the grid so that small shapes reach the unit loop
   if (ge && atoi(ge) > 0) grid = std::min(grid, atoi(ge));

@@ -244,21 +244,15 @@ def factor_scale(K):
     return 0.4 * (20.0 / K) ** 0.25
 
 
-@functools.lru_cache(maxsize=None)
-def layout(name, K, batch=False):
-    """Layout A (N = 173, the reference's sorted order, kinds by name) or B (N = 77, raw kind 3 with explicit thresholds),
-    M = 70, column weights, logsigma, mu, 10 % NaN; X and Y scaled by 0.4 (20 / K)^(1/4); the data of the kind-3 columns are
-    the class of z + 0.5 N(0, 1) under the column's thresholds.  batch: two batch views (4 sorted batches with a few rows
-    in no batch; 6 scrambled) whose seam falls inside a kind-3 tile; D does not follow the batch effects."""
-    spec = LAYOUT_A if name == "A" else LAYOUT_B
+def layout_from(spec, M, K, seed, views=None, **make_kw):
+    """The problem of a spec [((start1, stop1), kind, triple or None)] at M rows: make_problem(M, N, K, seed, **make_kw) with
+    column weights, logsigma, mu, 10 % NaN; X and Y scaled by 0.4 (20 / K)^(1/4); the data of the kind-3 columns are the class
+    of z + 0.5 N(0, 1) under the column's thresholds, those of a Bernoulli range that make_problem did not draw as one are
+    1[D > 0].  views: None, or a function (M, N, rng) -> [(start1, stop1, batch_of_row, nb)] called after the classes are
+    drawn (it may draw from rng); D does not follow the batch effects."""
     N = spec[-1][0][1]
-    seed = 1000 + K + (0 if name == "A" else 500)
-    if name == "A":
-        p = make_problem(M=M, N=N, K=K, seed=seed, bernoulli_frac=20 / N, poisson_frac=8 / N, nan_frac=0.1, weights=True,
-                         col_params=True, scale=factor_scale(K))
-        assert p["noise_ranges"] == [(1, 20), (21, 165), (166, 173)]
-    else:
-        p = make_problem(M=M, N=N, K=K, seed=seed, nan_frac=0.1, weights=True, col_params=True, scale=factor_scale(K))
+    p = make_problem(M=M, N=N, K=K, seed=seed, nan_frac=0.1, weights=True, col_params=True, scale=factor_scale(K), **make_kw)
+    drawn = kinds_of(p)
     p["noise_ranges"] = [r for r, _, _ in spec]
     p["noise_kinds"] = [k for _, k, _ in spec]
     p["noise_thr"] = [t if t is not None else THR.get(k) for _, k, t in spec]
@@ -269,19 +263,37 @@ def layout(name, K, batch=False):
     for j in np.flatnonzero(kinds_of(p) == 3):
         cls = (t[j][None, :] < (z[:, j] + 0.5 * rng.standard_normal(M))[:, None]).sum(1)
         D[:, j] = np.where(np.isnan(D[:, j]), np.nan, cls)
+    for j in np.flatnonzero((kinds_of(p) == 1) & (drawn != 1)):
+        D[:, j] = np.where(np.isnan(D[:, j]), np.nan, D[:, j] > 0)
     p["D"] = np.asfortranarray(D)
-    if batch:
-        b0 = bc.sorted_rows(M, 4)
-        b0[[0, 33, M - 1]] = -1
-        views = [(1, SEAMS[name], b0, 4), (SEAMS[name] + 1, N, bc.scrambled_rows(M, 6, rng), 6)]
+    if views is not None:
         bvs = []
-        for s, e, bor, nb in views:
+        for s, e, bor, nb in views(M, N, rng):
             cd, ct = rng.standard_normal(nb)[:, None] * 0.25, rng.standard_normal(nb)[:, None] * 0.25
             bvs.append(dict(start1=s, stop1=e, batch_of_row=np.asarray(bor, np.int32),
                             logdelta=(cd + 0.25 * rng.standard_normal((nb, e - s + 1))).astype(np.float32),
                             theta=(ct + 0.25 * rng.standard_normal((nb, e - s + 1))).astype(np.float32)))
         p["batch_views"] = bvs
     return p
+
+
+@functools.lru_cache(maxsize=None)
+def layout(name, K, batch=False):
+    """Layout A (N = 173, the reference's sorted order, kinds by name) or B (N = 77, raw kind 3 with explicit thresholds),
+    M = 70, column weights, logsigma, mu, 10 % NaN; X and Y scaled by 0.4 (20 / K)^(1/4); the data of the kind-3 columns are
+    the class of z + 0.5 N(0, 1) under the column's thresholds.  batch: two batch views (4 sorted batches with a few rows
+    in no batch; 6 scrambled) whose seam falls inside a kind-3 tile; D does not follow the batch effects."""
+    spec = LAYOUT_A if name == "A" else LAYOUT_B
+    N = spec[-1][0][1]
+    seed = 1000 + K + (0 if name == "A" else 500)
+
+    def views(M, N, rng):
+        b0 = bc.sorted_rows(M, 4)
+        b0[[0, 33, M - 1]] = -1
+        return [(1, SEAMS[name], b0, 4), (SEAMS[name] + 1, N, bc.scrambled_rows(M, 6, rng), 6)]
+
+    kw = dict(bernoulli_frac=20 / N, poisson_frac=8 / N) if name == "A" else {}
+    return layout_from(spec, M, K, seed, views if batch else None, **kw)
 
 
 def all_problems():
