@@ -15,6 +15,9 @@
  *  - every function returns 0 on success, <0 on error; pmf_last_error() gives the (thread-local) message.
  *    (The reference throws Julia exceptions / @assert: src/model.jl:125-184, src/util.jl:189.)
  *  - matrices are COLUMN-MAJOR as in Julia.  D is M x N float32 with NaN = missing; X is K x M; Y is K x N.
+ *    "Missing" is decided on the entry AS STORED on the device, and it means "not finite": +Inf and -Inf are missing exactly
+ *    as NaN is (counts, loss, gradients and PMF_IMPUTE_KEEP_OBSERVED treat the three alike), and under PMF_STORE_BF16 so is a
+ *    finite float32 that rounds to a bf16 infinity (|d| >= 0x7f7f8000 = 3.3961775e38).
  *  - column / row ranges are 1-BASED INCLUSIVE (Julia UnitRange, src/util.jl:187-197) so the shim passes
  *    ranges verbatim; `batch_of_row` is 0-based int32 (rowval-1 of the one-hot CSC row_batches matrix,
  *    src/util.jl:200-210, 588-593).
@@ -45,7 +48,10 @@ typedef struct pmf_ctx pmf_ctx;
 #define PMF_OPT_ADAGRAD 0
 #define PMF_OPT_ADAM 1
 
-/* storage type of the data matrix on the device */
+/* storage type of the data matrix on the device.  PMF_STORE_BF16 rounds every entry once, at upload, to the nearest
+ * bfloat16, ties to even: float32 subnormals round like any other value (nothing is flushed to zero), every NaN stays a
+ * NaN whatever its payload, and a finite entry at or above the overflow point 0x7f7f8000 (3.3961775e38, the tie between the
+ * largest bf16 and 2^128) becomes an infinity, which is a MISSING entry like every non-finite one (conventions above). */
 #define PMF_STORE_F32 0
 #define PMF_STORE_BF16 1
 
@@ -110,8 +116,19 @@ int pmf_destroy(pmf_ctx *ctx);
 int pmf_set_stream(pmf_ctx *ctx, void *hip_stream);
 int pmf_synchronize(pmf_ctx *ctx);
 
-/* model.data (src/model.jl:12).  Host copy-in, or adopt a device-resident matrix without copying.
- * `M` is the number of LOCAL rows when the samples are sharded across GPUs. */
+/* model.data (src/model.jl:12), from host or from device memory.  Either way the library COPIES: the matrix is re-laid out
+ * (and rounded under PMF_STORE_BF16) into a tile-major buffer that the context owns, and the source may be changed or freed
+ * as soon as the call returns.  `M` is the number of LOCAL rows when the samples are sharded across GPUs.
+ *   pmf_set_data        : a host matrix, uploaded in column chunks of at most 64 Mi floats (256 MiB; one column where a
+ *                         column alone is longer) through a staging buffer of that size that the context keeps.
+ *                         PMF_SET_DATA_CHUNK_FLOATS=n, read at every call, replaces the 64 Mi: a test hook that makes small
+ *                         shapes upload in several chunks.
+ *   pmf_set_data_device : D_device is a column-major M x N float32 matrix in DEVICE memory (leading dimension M, 4-byte
+ *                         alignment is enough), read by one kernel on the context's stream.  It must be COMPLETE before the
+ *                         call: the copy is ordered behind the work that produced it only if that work ran on the stream the
+ *                         context has adopted (pmf_set_stream); in every other case the caller synchronizes first.
+ *                         D_device = NULL allocates the buffer for an M x N matrix and leaves it all-missing
+ *                         (pmf_synth_data, pmf_simulate_data_resident fill it). */
 int pmf_set_data(pmf_ctx *ctx, const float *D_colmajor, int64_t M, int64_t N, int store);
 int pmf_set_data_device(pmf_ctx *ctx, const void *D_device, int64_t M, int64_t N, int store);
 

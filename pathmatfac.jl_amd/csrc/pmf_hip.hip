@@ -152,7 +152,8 @@ __global__ void k_pad_copy(float *dst, const float *src, int Kp, int K, int64_t 
 }
 
 // column-major source block (rows 0..M-1, columns col0..col0+ncols-1, leading dimension M) -> tile-major D
-// (bf16 storage: round to nearest even, NaN stays NaN)
+// (bf16 storage: the cast is one v_cvt_pk_bf16_f32 under the kernel's default mode: round to nearest even, f32 subnormals
+// kept, every NaN stays NaN whatever its payload; held to that by tests/test_gpu_data_ingest.py)
 __global__ void k_tile_D(const float *src, int64_t M, int64_t col0, int64_t ncols, void *dst, int64_t nRB, int bf16) {
   const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (e >= M * ncols) return;
@@ -692,8 +693,12 @@ extern "C" int pmf_set_data(pmf_ctx *c, const float *D, int64_t M, int64_t N, in
   if (store != PMF_STORE_F32 && store != PMF_STORE_BF16) return pmf_fail("unknown storage type %d", store);
   PMFCHK(data_shape_changed(c, M, N));
   PMFCHK(alloc_tiled_D(c, M, N, store));
-  // upload in column chunks of <= 256 MiB through a staging buffer, tiling each chunk on the device
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (64ll << 20) / std::max<int64_t>(M, 1)));
+  // upload in column chunks of <= 256 MiB (one column where a column alone is longer) through a staging buffer, tiling
+  // each chunk on the device
+  int64_t chunk_floats = 64ll << 20;
+  const char *ce = getenv("PMF_SET_DATA_CHUNK_FLOATS");   // test hook, read at every call: small shapes upload in several chunks
+  if (ce && atoll(ce) > 0) chunk_floats = atoll(ce);
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, chunk_floats / std::max<int64_t>(M, 1)));
   PMFCHK(c->scratch.ensure(sizeof(float) * (size_t)(M * chunk), false));
   for (int64_t c0 = 0; c0 < N; c0 += chunk) {
     const int64_t nc = std::min(chunk, N - c0);
