@@ -201,9 +201,19 @@ THRESHOLD_SIGNATURES = {
 }
 
 
+# include/pmf_hip_importance.h, the extension header of factor importance, in its order
+# (tests/test_importance_cases.py compares this table with that header)
+IMPORTANCE_CHAIN = 512                                     # PMF_IMPORTANCE_CHAIN
+IMPORTANCE_SIGNATURES = {
+    "pmf_factor_importance": _int(ctx, pd, pd, pd, pi64),
+    "pmf_debug_factor_importance": _int(ctx, pi, pi, pi, pi, pi, pi, pi, pi, pi64),
+}
+
+
 def bind(lib):
-    """Installs SIGNATURES and THRESHOLD_SIGNATURES on a CDLL.  AttributeError if a declared symbol is not exported."""
-    for name, (restype, argtypes) in {**SIGNATURES, **THRESHOLD_SIGNATURES}.items():
+    """Installs SIGNATURES, THRESHOLD_SIGNATURES and IMPORTANCE_SIGNATURES on a CDLL.  AttributeError if a declared symbol
+    is not exported."""
+    for name, (restype, argtypes) in {**SIGNATURES, **THRESHOLD_SIGNATURES, **IMPORTANCE_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype, f.argtypes = restype, argtypes
     return lib

@@ -463,6 +463,26 @@ class Context:
         self._chk(self.lib.pmf_debug_threshold_pass(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(p)))
         return dict(n_tiles=a.value, n_units=b.value, grid=c.value, passes=p.value)
 
+    # ---- factor importance (include/pmf_hip_importance.h)
+    def factor_importance(self, delta=True, full=True, null=True, n_obs=True):
+        """pmf_factor_importance at the current parameters over the local rows: (delta (K, N) float64, full (N,), null (N,),
+        n_obs (N,) int64).  An output switched off is passed as NULL and returned as None."""
+        K, N = self.K, self.N
+        d = np.zeros((N, K), np.float64) if delta else None            # factor fastest: delta[j * K + k]
+        f, z = (np.zeros(N, np.float64) if w else None for w in (full, null))
+        n = np.zeros(N, np.int64) if n_obs else None
+        self._chk(self.lib.pmf_factor_importance(self._h, _dp(d) if delta else None, _dp(f) if full else None,
+                                                 _dp(z) if null else None, _i64p(n) if n_obs else None))
+        return (np.ascontiguousarray(d.T) if delta else None), f, z, n
+
+    def debug_factor_importance(self):
+        """pmf_debug_factor_importance: dict(kb, nw, db, ranges, n_units, grid, launches, flushes, calls) of the last call."""
+        v = [C.c_int(0) for _ in range(8)]
+        calls = C.c_int64(0)
+        self._chk(self.lib.pmf_debug_factor_importance(self._h, *[C.byref(x) for x in v], C.byref(calls)))
+        names = ("kb", "nw", "db", "ranges", "n_units", "grid", "launches", "flushes")
+        return dict(zip(names, (x.value for x in v)), calls=calls.value)
+
     def loss(self):
         """pmf_loss: dict(total, data, xreg, yreg) at the current parameters (full_loss, src/fit_lbfgs.jl:3-8)."""
         v = [C.c_double(0) for _ in range(4)]

@@ -193,6 +193,15 @@ struct ThreshState {
   int64_t passes = 0;
 };
 
+// Factor importance (pmf_factor_importance, pmf_outputs.hip; include/pmf_hip_importance.h): the private float64 slabs of the
+// pass, its device outputs, and the geometry of the last call (pmf_debug_factor_importance).
+struct ImportanceState {
+  DevBuf<double> slabs;                 // [column tiles of a launch][R][Kp + 4][32]
+  DevBuf<double> out;                   // [K N] delta | [N] full | [N] null | [N] n_obs
+  int kb = 0, nw = 0, db = 0, R = 0, n_units = 0, grid = 0, launches = 0, flushes = 0;
+  int64_t calls = 0;
+};
+
 struct pmf_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -295,6 +304,7 @@ struct pmf_ctx {
   double pp_seconds[3] = {0.0, 0.0, 0.0};   // phases of the last post-processing call (pmf_postprocess.hip, PpClock)
   struct LbfgsState *lbfgs = nullptr;   // vectors and scalars of pmf_fit_lbfgs (pmf_lbfgs.hip), allocated on its first call
   ThreshState th;                       // trainable squared-hinge thresholds (pmf_thresh.hip)
+  ImportanceState imp;                  // factor importance (pmf_outputs.hip)
 };
 
 #define REG_SLOTS 1024

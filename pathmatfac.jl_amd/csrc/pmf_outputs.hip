@@ -1,6 +1,9 @@
 // pmf_outputs.hip -- what a fitted model gives back: pmf_forward / pmf_synth_data (k_forward), pmf_impute* (pmf_impute.hip.inc),
-// pmf_simulate_data* (pmf_simulate.hip.inc) and pmf_remove_batch_effect* (pmf_debatch.hip.inc) with the one host path their staged calls share.
+// pmf_simulate_data* (pmf_simulate.hip.inc) and pmf_remove_batch_effect* (pmf_debatch.hip.inc) with the one host path their staged calls share,
+// and pmf_factor_importance (pmf_importance.hip.inc).
 #include "pmf_ctx.h"
+#include "pmf_importance.h"
+#include "../../include/pmf_hip_importance.h"
 
 // Z = layers(X'Y) materialised (MF.forward, simulate_params.jl:247); also used by pmf_synth_data.
 struct ForwardArgs {
@@ -319,6 +322,85 @@ extern "C" int pmf_simulate_data_resident(pmf_ctx *c, const pmf_sim_opts *opts) 
 extern "C" int pmf_debug_impute_offset(int64_t row, int64_t col, int64_t ld, int64_t *offset) {
   if (!offset) return pmf_fail("null output");
   *offset = pmf_impute_off(row, col, ld);
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// factor importance (include/pmf_hip_importance.h; not in the reference): pmf_importance.hip.inc
+// ------------------------------------------------------------------------------------------------
+// The cap on the pass's private float64 slabs, one of (Kp + 4) x 32 doubles per (column tile, row range): what pmf_set_data's
+// upload chunks and impute's stage are held to.  The row ranges R are lowered to stay under it, and where the column tiles
+// alone exceed it at R = 1 (N above 480 000 at K = 64) the tiles are walked in several launches.
+#define PMF_IMPORTANCE_SLAB_MAX ((size_t)256 << 20)
+
+static int env_cap(const char *name, int64_t v) {
+  const char *e = getenv(name);   // test hooks, read at every call
+  return (int)(e && atoll(e) > 0 ? std::min<int64_t>(v, atoll(e)) : v);
+}
+
+extern "C" int pmf_factor_importance(pmf_ctx *c, double *delta, double *full, double *null_, int64_t *n_obs) {
+  PMFCHK(ctx_bind(c));
+  PMFCHK(check_ready(c));
+  if (c->KB < 1 || c->KB > 4) return pmf_fail("pmf_factor_importance: built for K <= 128 (K = %d)", c->K);
+  PMFCHK(prepare(c));
+  ImportanceState &s = c->imp;
+  const int nw = pmf_importance_waves(c->KB);
+  const int64_t K = c->K, N = c->N, n_ct = (N + PMF_BN - 1) / PMF_BN, n_rp = (c->M + 32 * nw - 1) / (32 * nw);
+  const size_t slab = sizeof(double) * (size_t)pmf_imp_rows(c->KB) * 32;
+  // column tiles per launch (all of them unless the slabs of R = 1 exceed the cap), then the row ranges: about eight units per
+  // CU, so that the tail of the persistent grid stays short, as far as the cap allows
+  const int64_t tiles = env_cap("PMF_IMPORTANCE_TILES", std::min<int64_t>(n_ct, std::max<int64_t>(1, (int64_t)(PMF_IMPORTANCE_SLAB_MAX / slab))));
+  int64_t R = std::max<int64_t>(1, std::min<int64_t>(n_rp, (8ll * c->n_cu + tiles - 1) / tiles));
+  R = std::max<int64_t>(1, std::min<int64_t>(R, (int64_t)(PMF_IMPORTANCE_SLAB_MAX / slab) / tiles));
+  R = env_cap("PMF_IMPORTANCE_RANGES", R);
+  if (tiles * R >= (1ll << 31)) return pmf_fail("pmf_factor_importance: too many units");
+  PMFCHK(s.slabs.ensure((size_t)(tiles * R) * (slab / sizeof(double)), false, "the factor-importance slabs"));
+  PMFCHK(s.out.ensure((size_t)((K + 3) * N), false, "the factor-importance sums"));
+  ImportanceArgs a;
+  memset(&a, 0, sizeof(a));
+  a.D = c->D; a.nRB = c->nRB; a.X = c->P[0].p; a.Y = c->P[1].p; a.colp = c->colp; a.bor = c->bor; a.btab = c->btab;
+  a.htab = c->mixed ? c->htab.p : nullptr;   // (the tables follow the noise model only while it has a column that is not normal)
+  a.views = c->d_views; a.slabs = s.slabs; a.M = c->M; a.N = N; a.K = c->K; a.n_bv = c->n_bv; a.n_rp = (int)n_rp; a.R = (int)R;
+  ImportanceReduceArgs r;
+  memset(&r, 0, sizeof(r));
+  r.slabs = s.slabs; r.R = (int)R; r.KB = c->KB; r.K = c->K; r.N = N;
+  r.delta = s.out.p; r.full = s.out.p + K * N; r.null_ = r.full + N; r.n_obs = r.null_ + N;
+  s.kb = c->KB; s.nw = nw; s.db = c->store == PMF_STORE_BF16; s.R = (int)R; s.n_units = 0; s.grid = 0; s.launches = 0;
+  s.flushes = (int)(((n_rp + R - 1) / R + PMF_IMP_FLUSH - 1) / PMF_IMP_FLUSH);   // (the host's arithmetic on the geometry: not observed in the kernel)
+  for (int64_t ct0 = 0; ct0 < n_ct; ct0 += tiles) {
+    a.ct0 = r.ct0 = (int)ct0;
+    a.n_ct = r.n_ct = (int)std::min(tiles, n_ct - ct0);
+    const int grid = env_cap("PMF_IMPORTANCE_GRID", std::min<int64_t>((int64_t)a.n_ct * R, c->n_cu));
+    PMFCHK(pmf_launch_importance(&c->dyn_lds, c->stream, c->KB, s.db != 0, grid, a));
+    PMFCHK(pmf_launch_importance_reduce(c->stream, r));   // (stream order: the next launch reuses the slabs after it)
+    s.n_units += a.n_ct * (int)R; s.grid = std::max(s.grid, grid); s.launches++;
+  }
+  s.calls++;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (delta) HIPCHK(hipMemcpy(delta, r.delta, sizeof(double) * (size_t)(K * N), hipMemcpyDeviceToHost));
+  if (full) HIPCHK(hipMemcpy(full, r.full, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+  if (null_) HIPCHK(hipMemcpy(null_, r.null_, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+  if (n_obs) {
+    std::vector<double> cnt((size_t)N);
+    HIPCHK(hipMemcpy(cnt.data(), r.n_obs, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost));
+    for (int64_t j = 0; j < N; ++j) n_obs[j] = (int64_t)cnt[(size_t)j];   // (exact: sums of small integers in float64)
+  }
+  return 0;
+}
+
+extern "C" int pmf_debug_factor_importance(pmf_ctx *c, int *kb, int *nw, int *db, int *n_ranges, int *n_units, int *grid, int *launches,
+                                           int *flushes, int64_t *calls) {
+  PMFCHK(ctx_bind(c));
+  const ImportanceState &s = c->imp;
+  if (kb) *kb = s.kb;
+  if (nw) *nw = s.nw;
+  if (db) *db = s.db;
+  if (n_ranges) *n_ranges = s.R;
+  if (n_units) *n_units = s.n_units;
+  if (grid) *grid = s.grid;
+  if (launches) *launches = s.launches;
+  if (flushes) *flushes = s.flushes;
+  if (calls) *calls = s.calls;
   return 0;
 }
 
