@@ -22,6 +22,8 @@ from . import impute as _impute  # noqa: F401
 from .impute import impute, impute_entries  # noqa: F401
 from . import importance as _importance  # noqa: F401
 from .importance import factor_importance, explained_deviance, FactorImportance  # noqa: F401
+from . import holdout as _holdout  # noqa: F401
+from .holdout import sample_holdout, set_holdout_, clear_holdout_, holdout_scores, ensure_device_holdout_  # noqa: F401
 from . import remove_batch_effect as _remove_batch_effect  # noqa: F401
 from .remove_batch_effect import remove_batch_effect, remove_batch_effect_entries  # noqa: F401
 from . import simulate as _simulate  # noqa: F401

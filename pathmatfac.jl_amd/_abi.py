@@ -13,7 +13,8 @@ NOISE = {"normal": 0, "bernoulli": 1, "poisson": 2, "bernoulli_sq_hinge": 3, "or
 HINGE_THRESHOLDS = {"bernoulli_sq_hinge": (0.0, inf, inf), "ordinal_sq_hinge3": (-inf, -0.5, 0.5)}
 OPT = {"adagrad": 0, "adam": 1}
 STORE = {"f32": 0, "bf16": 1}
-TERM = {0: "max_epochs", 1: "loss_increase", 2: "abs_tol", 3: "rel_tol", 4: "nonfinite"}
+TERM = {0: "max_epochs", 1: "loss_increase", 2: "abs_tol", 3: "rel_tol", 4: "nonfinite",
+        5: "holdout_increase"}                             # PMF_TERM_HOLDOUT (include/pmf_hip_holdout.h)
 IMPUTE_BATCH, IMPUTE_LINK, IMPUTE_KEEP_OBSERVED = 1, 2, 4
 DEBATCH_LINK, DEBATCH_FILL_MISSING = 1, 2
 PARAM = {"X": 0, "Y": 1, "logsigma": 2, "mu": 3, "logdelta": 4, "theta": 5}
@@ -210,10 +211,34 @@ IMPORTANCE_SIGNATURES = {
 }
 
 
+# include/pmf_hip_holdout.h, the extension header of the hold-out entries, in its order
+# (tests/test_holdout_cases.py compares this table and the struct with that header)
+TERM_HOLDOUT = 5                                           # PMF_TERM_HOLDOUT
+
+
+class HoldoutOpts(C.Structure):
+    """pmf_holdout_opts"""
+    _fields_ = [("every", C.c_int32), ("patience", C.c_int32), ("restore_best", C.c_int32), ("reserved", C.c_int32),
+                ("min_delta", C.c_double)]
+
+
+HOLDOUT_STRUCTS = {"pmf_holdout_opts": HoldoutOpts}
+HOLDOUT_SIGNATURES = {
+    "pmf_set_holdout": _int(ctx, i64, pi64, pi64, pi64),
+    "pmf_clear_holdout": _int(ctx, i),
+    "pmf_get_holdout": _int(ctx, pi64, pi64, pi64, pf, i64),
+    "pmf_holdout_loss": _int(ctx, pd, pd, pi64),
+    "pmf_debug_holdout_pass": _int(ctx, pi, pi, pi64),
+    "pmf_set_holdout_tracking": _int(ctx, _P(HoldoutOpts)),
+    "pmf_get_holdout_trace": _int(ctx, pi, pi, pd, pi32, pd, i),
+}
+
+
 def bind(lib):
-    """Installs SIGNATURES, THRESHOLD_SIGNATURES and IMPORTANCE_SIGNATURES on a CDLL.  AttributeError if a declared symbol
-    is not exported."""
-    for name, (restype, argtypes) in {**SIGNATURES, **THRESHOLD_SIGNATURES, **IMPORTANCE_SIGNATURES}.items():
+    """Installs SIGNATURES and the extension headers' tables on a CDLL.  AttributeError if a declared symbol is not
+    exported."""
+    for name, (restype, argtypes) in {**SIGNATURES, **THRESHOLD_SIGNATURES, **IMPORTANCE_SIGNATURES,
+                                      **HOLDOUT_SIGNATURES}.items():
         f = getattr(lib, name)
         f.restype, f.argtypes = restype, argtypes
     return lib

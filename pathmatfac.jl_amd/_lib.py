@@ -15,7 +15,7 @@ import numpy as np
 
 from ._abi import (COMM_ID_BYTES, DEBATCH_FILL_MISSING, DEBATCH_LINK, EXPORTS, HINGE_THRESHOLDS,  # noqa: F401
                    HOST_ALLREDUCE_FN, IMPUTE_BATCH, IMPUTE_KEEP_OBSERVED, IMPUTE_LINK, NOISE, OPT, PARAM, PASS_EXTENTS_MAX,
-                   STORE, TERM, Csr, EmOpts, EmResult, FitOpts, FitResult, LbfgsOpts, LbfgsResult, SimOpts, bind)
+                   STORE, TERM, Csr, EmOpts, EmResult, FitOpts, FitResult, HoldoutOpts, LbfgsOpts, LbfgsResult, SimOpts, bind)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = _HERE / "libpmf_hip.so"
@@ -159,6 +159,7 @@ class Context:
         self.M = self.N = self.K = 0
         self.view_shapes = []
         self.n_noise_ranges = 0     # ranges of the last set_noise (the library forgets them with a new data shape: so does this)
+        self.holdout_tracking = dict(every=0)   # the options of the last set_holdout_tracking
 
     def _chk(self, rc):
         if rc != 0:
@@ -422,8 +423,66 @@ class Context:
         finally:
             if update_noise_models:
                 self.set_threshold_training(False)
-        return {"term_code": TERM[r.term_code], "epochs": r.epochs, "loss": trace[:r.n_trace].copy(),
-                "final_loss": r.final_loss, "seconds": r.seconds}
+        h = {"term_code": TERM[r.term_code], "epochs": r.epochs, "loss": trace[:r.n_trace].copy(),
+             "final_loss": r.final_loss, "seconds": r.seconds}
+        ho = self.get_holdout_trace()
+        if len(ho["epochs"]):                          # hold-out tracking ran in this fit (include/pmf_hip_holdout.h)
+            h.update(holdout_loss=ho["losses"], holdout_epochs=ho["epochs"], best_epoch=ho["best_epoch"])
+        return h
+
+    # ---- hold-out entries (include/pmf_hip_holdout.h)
+    def set_holdout(self, rows1, cols1):
+        """pmf_set_holdout: holds the 1-based entries out of the resident data; returns how many were observed and are held."""
+        r, c, _ = self._entries("set_holdout", rows1, cols1)
+        n = C.c_int64(0)
+        self._chk(self.lib.pmf_set_holdout(self._h, len(r), _i64p(r), _i64p(c), C.byref(n)))
+        return n.value
+
+    def clear_holdout(self, restore=True):
+        self._chk(self.lib.pmf_clear_holdout(self._h, int(bool(restore))))
+
+    def get_holdout(self):
+        """pmf_get_holdout: (rows1, cols1, values) in the library's (column, row) order."""
+        n = C.c_int64(0)
+        self._chk(self.lib.pmf_get_holdout(self._h, C.byref(n), None, None, None, 0))
+        r, c, v = np.zeros(n.value, np.int64), np.zeros(n.value, np.int64), np.zeros(n.value, np.float32)
+        if n.value:
+            self._chk(self.lib.pmf_get_holdout(self._h, C.byref(n), _i64p(r), _i64p(c), _fp(v), n.value))
+        return r, c, v
+
+    def holdout_loss(self):
+        """pmf_holdout_loss at the current parameters: (total, loss_col (N,) float64, n_col (N,) int64)."""
+        t, lc, nc = C.c_double(0), np.zeros(self.N, np.float64), np.zeros(self.N, np.int64)
+        self._chk(self.lib.pmf_holdout_loss(self._h, C.byref(t), _dp(lc), _i64p(nc)))
+        return t.value, lc, nc
+
+    def debug_holdout_pass(self):
+        """pmf_debug_holdout_pass: dict(n_units, grid, passes) of the last hold-out pass."""
+        a, b, p = C.c_int(0), C.c_int(0), C.c_int64(0)
+        self._chk(self.lib.pmf_debug_holdout_pass(self._h, C.byref(a), C.byref(b), C.byref(p)))
+        return dict(n_units=a.value, grid=b.value, passes=p.value)
+
+    def set_holdout_tracking(self, every=0, patience=0, min_delta=0.0, restore_best=False):
+        """pmf_set_holdout_tracking (sticky): every = 0 turns tracking off.  holdout_tracking holds what was last set."""
+        o = HoldoutOpts(int(every), int(patience), int(bool(restore_best)), 0, float(min_delta))
+        self._chk(self.lib.pmf_set_holdout_tracking(self._h, C.byref(o) if every else None))
+        self.holdout_tracking = dict(every=int(every), patience=int(patience), min_delta=float(min_delta),
+                                     restore_best=bool(restore_best)) if every else dict(every=0)
+
+    def holdout_count(self):
+        """The number of entries the context holds out (0: no set)."""
+        n = C.c_int64(0)
+        self._chk(self.lib.pmf_get_holdout(self._h, C.byref(n), None, None, None, 0))
+        return n.value
+
+    def get_holdout_trace(self):
+        """pmf_get_holdout_trace: dict(epochs, losses, best_epoch, best_loss) of the last fit's evaluations."""
+        n, be, bl = C.c_int(0), C.c_int(0), C.c_double(0)
+        self._chk(self.lib.pmf_get_holdout_trace(self._h, C.byref(n), C.byref(be), C.byref(bl), None, None, 0))
+        ep, ls = np.zeros(n.value, np.int32), np.zeros(n.value, np.float64)
+        if n.value:
+            self._chk(self.lib.pmf_get_holdout_trace(self._h, C.byref(n), C.byref(be), C.byref(bl), _i32p(ep), _dp(ls), n.value))
+        return dict(epochs=ep, losses=ls, best_epoch=be.value, best_loss=bl.value)
 
     # ---- trainable squared-hinge thresholds (include/pmf_hip_thresholds.h)
     def set_threshold_training(self, on):

@@ -2,6 +2,7 @@
 #include <rccl/rccl.h>   // types and enums only: the entry points are resolved with dlopen at pmf_comm_init (no link dependency)
 #include <dlfcn.h>
 
+#include "../../include/pmf_hip_holdout.h"   // PMF_TERM_HOLDOUT
 #include "pmf_ctx.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -253,7 +254,7 @@ static int compute_after_comm(pmf_ctx *c, hipEvent_t ev) {
 //     gradients when they train).
 // A data pass only writes gradient buffers, never parameters: when epoch e terminates the fit, the speculative pass of
 // e+1 is simply dropped and the parameters are exactly those after epoch e's steps (same results as the plain loop).
-static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool th_on);
+static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool th_on, bool ho_on);
 
 // Error exits.  Inside the pipelined loop a speculative data pass and collectives may already be enqueued when a call
 // fails.  Every error exit therefore drains both streams before returning (the context's buffers are not written behind
@@ -273,7 +274,11 @@ extern "C" int pmf_fit(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res) {
   // anything is launched; every rank holds the same noise model and refuses alike
   bool th_on = false;
   PMFCHK(thresh_fit_check(c, &th_on));
-  const int rc = comm_error_exit(c, fit_loop(c, o, res, th_on));
+  // hold-out tracking (include/pmf_hip_holdout.h): its refusals, its buffers and its unit table, before anything is launched
+  bool ho_on = false;
+  PMFCHK(holdout_fit_check(c, o, th_on, &ho_on));
+  int rc = comm_error_exit(c, fit_loop(c, o, res, th_on, ho_on));
+  if (ho_on && rc == 0) rc = holdout_fit_end(c, o->update_X != 0, o->update_Y != 0);   // (both streams are idle)
   if (th_on) {   // (both streams are idle) the host copy follows the device, after a failed fit too
     const std::string msg = rc < 0 ? pmf_last_error() : "";
     const int rt = thresh_fit_end(c);
@@ -294,7 +299,7 @@ int comm_error_exit(pmf_ctx *c, int rc) {
   return rc;
 }
 
-static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool th_on) {
+static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool th_on, bool ho_on) {
   const auto t0 = std::chrono::steady_clock::now();
   const bool ux = o->update_X != 0, uy = o->update_Y != 0, ul = o->update_col_layers != 0;
   const bool fused = ux || uy || !ul;
@@ -381,6 +386,13 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool
     const bool more = epoch < o->max_epochs;
     RegCounts rc;
     for (int q = 0; q < 4; ++q) rc.c[q] = 0;
+    // ---- the hold-out pass, at the parameters this epoch's data pass saw (nothing has been stepped yet); its total rides
+    // in slot 5 of the epoch's loss copy.  restore_best: the factors as they are now are the epoch's candidate.
+    const bool ho_eval = ho_on && (epoch - o->epoch) % c->ho.every == 0;
+    if (ho_eval) {
+      PMFCHK(holdout_pass(c, c->d_loss + 5));
+      PMFCHK(holdout_fit_snapshot(c, ux, uy));
+    }
     // ---- X step (row-local) and the rank-local part of the loss: data term + X regularizer
     if (ux) {
       PMFCHK(netreg_eval(c, 0, &rc.c[0]));
@@ -417,7 +429,7 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool
         }
         if (cm) PMFCHK(compute_after_comm(c, m.ev_loss_done));
         PMFCHK(launch_loss_reduce(c, rc, 0x1c));
-        HIPCHK(hipMemcpyAsync(c->h_loss, c->d_loss, sizeof(double) * 5, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_loss, c->d_loss, sizeof(double) * (ho_eval ? 6 : 5), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipEventRecord(c->ev_host, c->stream));
       }
       if (more) {
@@ -452,6 +464,8 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool
     last_epoch = epoch;
     if (o->verbosity > 0 && o->print_iter > 0 && (epoch % o->print_iter == 0))
       fprintf(stderr, "(%d) Loss=%.8g\n", epoch, loss);
+    // the evaluation is recorded whatever ends the epoch; the checks on the training loss run first and win
+    const bool ho_stop = ho_eval && holdout_fit_record(c, epoch, c->h_loss[5]);
     if (!std::isfinite(loss)) { term = PMF_TERM_NONFINITE; break; }
     if (n > 1) {
       const double diff = prev - loss;
@@ -465,6 +479,7 @@ static int fit_loop(pmf_ctx *c, const pmf_fit_opts *o, pmf_fit_result *res, bool
         tol_iters = 0;
       }
     }
+    if (ho_stop) { term = PMF_TERM_HOLDOUT; break; }
     prev = loss;
   }
   // a speculative data pass (and its collectives: every rank took the same decision on the same loss, so every rank

@@ -12,6 +12,7 @@
 //   pmf_lbfgs.hip     L-BFGS over (X, Y): total gradient, history, two-loop recursion, backtracking (pmf_fit_lbfgs)
 //   pmf_stages.hip    the closed-form stages between the GD stages on the device statistics (pmf_stage_*)
 //   pmf_postprocess.hip  the factor post-processing stages (whiten, rotate_by_svd, reorder, lambda_max) on the resident X, Y
+//   pmf_holdout.hip   hold-out entries: the set beside the resident D, the hold-out loss, tracking inside pmf_fit
 #ifndef PMF_CTX_H
 #define PMF_CTX_H
 #include <hip/hip_runtime.h>
@@ -202,6 +203,33 @@ struct ImportanceState {
   int64_t calls = 0;
 };
 
+// Hold-out entries (pmf_holdout.hip; include/pmf_hip_holdout.h): the set in CSC form beside the resident D, the work units
+// and outputs of the hold-out pass, the tracking options, and what the last pmf_fit recorded.
+struct HoldoutState {
+  int64_t n = 0;                        // entries held (0: no set)
+  std::vector<int64_t> h_colptr;        // [N + 1] host copy of colptr (unit table, n_col)
+  DevBuf<int64_t> colptr;               // [N + 1]
+  DevBuf<int32_t> rows;                 // [n] 0-based, sorted by (column, row)
+  DevBuf<float> vals;                   // [n] the values D held (bf16 store: the stored, rounded ones)
+  int unit_cap = 0;                     // PMF_HOLDOUT_UNIT the unit table was built for (0: not built)
+  int n_units = 0, grid = 0;            // geometry of the last pass (pmf_debug_holdout_pass)
+  DevBuf<int32_t> u_col, u_cnt;         // [n_units]
+  DevBuf<int64_t> u_e0;
+  DevBuf<float> lbuf;                   // [n] per-entry losses of the last pass
+  DevBuf<double> loss_col;              // [N]
+  DevBuf<double> d_total;               // [1] the total of a pmf_holdout_loss call (a fit's goes to d_loss[5])
+  int64_t passes = 0;
+  // tracking (pmf_set_holdout_tracking)
+  int every = 0, patience = 0, restore_best = 0;
+  double min_delta = 0.0;
+  // the last pmf_fit
+  std::vector<int32_t> tr_epoch;
+  std::vector<double> tr_loss;
+  int best_epoch = 0;
+  double best_loss = 0.0;
+  DevBuf<float> cand[2], best[2];       // X / Y of the evaluation epoch under way, of the best one (restore_best only)
+};
+
 struct pmf_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -305,6 +333,7 @@ struct pmf_ctx {
   struct LbfgsState *lbfgs = nullptr;   // vectors and scalars of pmf_fit_lbfgs (pmf_lbfgs.hip), allocated on its first call
   ThreshState th;                       // trainable squared-hinge thresholds (pmf_thresh.hip)
   ImportanceState imp;                  // factor importance (pmf_outputs.hip)
+  HoldoutState ho;                      // hold-out entries (pmf_holdout.hip)
 };
 
 #define REG_SLOTS 1024
@@ -481,6 +510,17 @@ int thresh_fit_begin(pmf_ctx *c);   // after the first epoch_open: the pass's ow
 int thresh_pass(pmf_ctx *c);        // one threshold pass at the current parameters: th.gcol, th.G (float64, on the stream)
 int thresh_step(pmf_ctx *c);        // optimizer step from th.G, order clamp, the per-column images
 int thresh_fit_end(pmf_ctx *c);     // h_thr <- the groups' triples (the stream is idle)
+// ---- defined in pmf_holdout.hip: the hold-out set inside pmf_fit and beside the data (include/pmf_hip_holdout.h)
+void holdout_drop(pmf_ctx *c);        // the resident data is being replaced: the set goes, nothing is written back
+// what a tracking fit checks before anything is launched: *active = tracking is on and a set is held; the refusals of
+// pmf_hip_holdout.h; clears the last fit's trace, builds the unit table and the restore buffers
+int holdout_fit_check(pmf_ctx *c, const pmf_fit_opts *o, bool th_on, bool *active);
+// one hold-out pass at the current parameters on the stream: ho.loss_col, and the total at *d_total (device).  No host sync.
+int holdout_pass(pmf_ctx *c, double *d_total);
+int holdout_fit_snapshot(pmf_ctx *c, bool ux, bool uy);   // restore_best: the factors about to be stepped -> the candidate
+// the evaluation of `epoch` has reached the host: records it; true when `patience` evaluations in a row did not improve
+bool holdout_fit_record(pmf_ctx *c, int epoch, double H);
+int holdout_fit_end(pmf_ctx *c, bool ux, bool uy);        // (the stream is idle) restore_best: X, Y <- the best epoch's
 // ---- defined in pmf_comm_fit.hip
 int comm_release(pmf_ctx *c);
 bool comm_active(const pmf_ctx *c);

@@ -672,6 +672,7 @@ static int alloc_tiled_D(pmf_ctx *c, int64_t M, int64_t N, int store) {
     c->nRB = nRB;
   }
   c->tflags_valid = false;
+  holdout_drop(c);   // a hold-out set belonged to the old values: it goes without write-back (pmf_hip_holdout.h)
   c->store = store;
   if (store == PMF_STORE_BF16) k_fill16<<<(int)std::min<int64_t>(nblocks(nfl, 256), 65536), 256, 0, c->stream>>>((uint16_t *)c->D.p, nfl, (uint16_t)0x7fc0);
   else k_fill<<<(int)std::min<int64_t>(nblocks(nfl, 256), 65536), 256, 0, c->stream>>>((float *)c->D.p, nfl, __builtin_nanf(""));

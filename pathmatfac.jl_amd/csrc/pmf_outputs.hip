@@ -97,6 +97,7 @@ extern "C" int pmf_synth_data(pmf_ctx *c, uint64_t seed, float noise, float frac
   PMFCHK(ctx_bind(c));
   if (!c->D) return pmf_fail("data buffer not allocated (pmf_set_data_device(ctx, NULL, M, N, store))");
   c->tflags_valid = false;
+  holdout_drop(c);
   PMFCHK(run_forward(c, (float *)c->D.p, 1, seed, noise, frac_nan, c->nRB));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
@@ -314,6 +315,7 @@ extern "C" int pmf_simulate_data_resident(pmf_ctx *c, const pmf_sim_opts *opts) 
   if (!c->D) return pmf_fail("%s: data buffer not allocated (pmf_set_data_device(ctx, NULL, M, N, store) or pmf_set_data)", fn);
   PMFCHK(prepare(c));
   c->tflags_valid = false;   // what pmf_set_data invalidates: the per-tile all-finite flags of the old values
+  holdout_drop(c);           // ... and a hold-out set, without write-back
   PMFCHK(simulate_launch(c, opts, c->store == PMF_STORE_BF16 ? PMF_SIM_TILE_BF16 : PMF_SIM_TILE_F32, 0, c->M, (float *)c->D.p, c->M));
   HIPCHK(hipStreamSynchronize(c->stream));
   return 0;

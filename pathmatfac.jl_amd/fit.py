@@ -30,7 +30,11 @@ def mf_fit_(model, scale_column_losses=False, update_X=False, update_Y=False, up
             update_Y_reg=False, update_row_layers_reg=False, update_col_layers_reg=False, keep_history=True,
             device=0, **kwargs):
     """mf_fit! (src/fit.jl:9-38): the drop-in boundary.  MF.fit! is replaced by the HIP library."""
-    ctx = model.device_context(device)
+    if getattr(model, "holdout", None) is not None:        # a context that lost its set with its data takes it again
+        from .holdout import ensure_device_holdout_
+        ctx = ensure_device_holdout_(model, device)
+    else:
+        ctx = model.device_context(device)
     return MF.fit_(model.matfac, ctx, update_X=update_X, update_Y=update_Y, update_col_layers=update_col_layers,
                    update_noise_models=update_noise_models, keep_history=keep_history, **kwargs)
 
@@ -42,7 +46,8 @@ def construct_optimizer(model, lr):
 
 def mf_fit_adapt_lr_(model, lr=1.0, min_lr=0.001, max_epochs=1000, history=None, keep_history=True, verbosity=1,
                      print_prefix="", **kwargs):
-    """mf_fit_adapt_lr! (src/fit.jl:46-75): halve eta on "loss_increase" until eta < min_lr, resuming the epoch count."""
+    """mf_fit_adapt_lr! (src/fit.jl:46-75): halve eta on "loss_increase" until eta < min_lr, resuming the epoch count.
+    The holdout_* options of matfac.fit_ pass through; "holdout_increase" ends the loop like every other code."""
     opt = construct_optimizer(model, lr)
     epoch = 1
     last = None

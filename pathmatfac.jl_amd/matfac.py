@@ -174,8 +174,14 @@ def unmarshal(mf, ctx, update_X, update_Y, update_col_layers, update_thresholds=
 
 def fit_(mf, ctx, opt=None, lr=0.01, update_X=False, update_Y=False, update_col_layers=False, max_epochs=1000,
          epoch=1, abs_tol=1e-9, rel_tol=1e-6, tol_max_iters=3, verbosity=0, print_iter=10, capacity=10 ** 8,
-         keep_history=True, dist=None, group=None, update_noise_models=False, **ignored):
+         keep_history=True, dist=None, group=None, update_noise_models=False, holdout_every=0, holdout_patience=0,
+         holdout_min_delta=0.0, holdout_restore_best=False, **ignored):
     """MF.fit!(matfac, data; ...) -> history dict with "term_code", "epochs", "loss" (src/fit.jl:24-38, 61-69).
+    holdout_every > 0: the fit tracks the loss of the context's hold-out set (holdout.set_holdout_) every so many epochs,
+    ends with "holdout_increase" after holdout_patience > 0 evaluations without an improvement of more than
+    holdout_min_delta, and with holdout_restore_best returns the factors of the best evaluation (the optimizer state is
+    not rolled back); the history gains "holdout_loss", "holdout_epochs" and "best_epoch".  Not on a row-sharded fit.
+    The options hold for this call: tracking that the caller set on the context itself is put back afterwards.
     update_noise_models is honoured only when the noise model says so (CompositeNoise.train_thresholds_): the squared-hinge
     thresholds then train inside pmf_fit and the trained triples are written into noise_model.thresholds.  The row-sharded
     loop of parallel.py runs on the step-level API, which keeps thresholds constant."""
@@ -193,12 +199,22 @@ def fit_(mf, ctx, opt=None, lr=0.01, update_X=False, update_Y=False, update_col_
               max_epochs=max_epochs, epoch=epoch, abs_tol=abs_tol, rel_tol=rel_tol, tol_max_iters=tol_max_iters,
               verbosity=verbosity, print_iter=print_iter)
     if dist is not None and dist.is_initialized() and dist.get_world_size(group) > 1:
+        if holdout_every:
+            raise ValueError("hold-out tracking (holdout_every > 0) is not supported on a row-sharded fit: "
+                             "score with holdout.holdout_scores between fits instead")
         from . import parallel
         h = parallel.fit_distributed(ctx, dist=dist, group=group, **kw)
         train_thr = False
     else:
         train_thr = bool(update_noise_models and mf.noise_model.train_thresholds)
-        h = ctx.fit(capacity=capacity, update_noise_models=train_thr, **kw)
+        sticky = dict(ctx.holdout_tracking)
+        if holdout_every:
+            ctx.set_holdout_tracking(holdout_every, holdout_patience, holdout_min_delta, holdout_restore_best)
+        try:
+            h = ctx.fit(capacity=capacity, update_noise_models=train_thr, **kw)
+        finally:
+            if holdout_every:
+                ctx.set_holdout_tracking(**sticky)
     unmarshal(mf, ctx, update_X, update_Y, update_col_layers, update_thresholds=train_thr)
     for reg, which, on in ((mf.X_reg, "X", update_X), (mf.Y_reg, "Y", update_Y)):
         if on and hasattr(reg, "read_back"):      # the network term's virtual nodes (NetworkRegularizer.x_virtual)
